@@ -20,6 +20,8 @@ The JSON line also carries:
                (what a caller who just allocates and runs gets), measured in the same process before the search.
   cpu_baseline the oracle (NumPy restatement in the reference's operation order) timed on this box's
                host cores on a bounded row-slab of the same workload (rank 0, N=1 only).
+  dump_outputs with --dump-outputs DIR: the .npy files written from the last timed step's result, their shapes and
+               which pixels the images keep.
 """
 import argparse
 import json
@@ -38,6 +40,9 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E vendor peak (MI355X_MICROARCH.md)
 TRAFFIC_FILE = os.path.join("profiles", "traffic.json")
+DUMP_FULL_MB = 48              # --dump-outputs: pseudo + matched up to this size are written whole, larger ones sampled
+DUMP_SAMPLE_PIXELS = 1 << 18   # pixels of the fixed sample (16 bands x 2 images x 4 B x 256 Ki = 32 MB at most)
+DUMP_SEED = 0
 
 
 def parse_args(argv=None):
@@ -124,7 +129,16 @@ def parse_args(argv=None):
     ap.add_argument("--deadline", type=float, default=900.0,
                     help="N > 1: hard limit per rank in seconds - a rank still alive then dumps its stacks and exits non-zero "
                          "(0: none).  The self-launching parent gives the whole job this long plus a minute.")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0, last tile) as DIR/<name>.npy: "
+                         "coeffs and moments (float64), pseudo and matched (float32, band-major).  Images of more than "
+                         f"{DUMP_FULL_MB} MB together are sampled at {DUMP_SAMPLE_PIXELS} fixed pixels (seeded, sorted; see "
+                         "dump_pixel_sample); the inputs are seeded, so two builds can be compared file for file.  "
+                         "bench_outputs/ is the directory git ignores for this")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -338,6 +352,52 @@ def cpu_baseline(args, pool, nworkers, cube_host, real_host, gpu_pseudo, gpu_mat
 
 
 # ----------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ----------------------------------------------------------------------------------------------------------
+def dump_pixel_sample(npix: int, nb: int):
+    """Pixel indices the dumped images keep: None (all of them) while pseudo + matched stay within DUMP_FULL_MB, else
+    DUMP_SAMPLE_PIXELS distinct indices drawn with a fixed seed and sorted - the same for every run of the same shape."""
+    import numpy as np
+    if 2 * nb * npix * 4 <= DUMP_FULL_MB << 20:
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.sort(rng.choice(npix, size=DUMP_SAMPLE_PIXELS, replace=False))
+
+
+def snapshot_outputs(last, nb: int, H: int, W: int):
+    """Device copies of what the last timed step returned to its caller, taken before any later launch reuses the plan's
+    buffers (enqueued on the current stream, no host synchronisation).  ``last`` is a FusionOutput (step(), submit() /
+    flush()) or fuse_mosaic()'s (coeffs, moments, outputs) - then its last tile.  Images come back band-major (nb, ...)."""
+    import torch
+    fo = last[2][-1] if isinstance(last, tuple) else last
+    idx = dump_pixel_sample(H * W, nb)
+    idx_t = None if idx is None else torch.from_numpy(idx).to(fo.pseudo.device)
+    snap = {"coeffs": fo.coeffs.clone(), "moments": fo.moments.clone()}
+    for name in ("pseudo", "matched"):
+        p = fo.planes(name)
+        snap[name] = p.clone().reshape(nb, H, W) if idx_t is None else p.index_select(1, idx_t)
+    return snap, idx
+
+
+def write_outputs(directory: str, snap, idx, npix: int):
+    """Writes the snapshot as <directory>/<name>.npy (float32 images, float64 fit); returns the record for the JSON line."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    files, total = {}, 0
+    for name, t in snap.items():
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        files[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    return {"dir": os.path.abspath(directory), "files": files, "bytes": total,
+            "pixels": ("all" if idx is None else
+                       f"{len(idx)} of {npix}: np.sort(np.random.default_rng({DUMP_SEED}).choice({npix}, {len(idx)}, replace=False))"),
+            "what": "the last timed step's result (rank 0, last tile): coefficients, moments, pseudo and matched images"}
+
+
+# ----------------------------------------------------------------------------------------------------------
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
@@ -532,7 +592,8 @@ def main(argv=None):
     host_issue = [0.0]
 
     def timed_region(plan_, run_step, steps, warm, settle_steps):
-        """settle (untimed load) -> W warm-up steps -> barrier -> exactly `steps` timed steps -> barrier."""
+        """settle (untimed load) -> W warm-up steps -> barrier -> exactly `steps` timed steps -> barrier.  Returns the time,
+        the events and what the last timed step returned (for a pipeline: the tile flush() finished)."""
         for i in range(settle_steps):
             run_step()
             if (i + 1) % 50 == 0:
@@ -545,14 +606,15 @@ def main(argv=None):
         every = max(1, args.event_every)
         ev = {i: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
               for i in range(0, steps, every)}
+        last = None
         t0 = time.perf_counter()
         for i in range(steps):
-            run_step(ev.get(i))
+            last = run_step(ev.get(i))
         host_issue[0] = (time.perf_counter() - t0) / max(1, steps)      # host time to ISSUE a step (the GPU runs behind)
         if pipelined or mosaic_fused:
-            plan_.flush()            # the last tile's apply belongs to the timed region
+            last = plan_.flush()     # the last tile's apply belongs to the timed region
         barrier()
-        return time.perf_counter() - t0, ev
+        return time.perf_counter() - t0, ev, last
 
     def max_over_ranks(x):
         tt = torch.tensor([x], dtype=torch.float64, device=device)
@@ -572,7 +634,7 @@ def main(argv=None):
     cold = None
     if args.cold_steps > 0 and ntl == 1:
         cold_plan = make_plan(0)
-        dtc, evc = timed_region(cold_plan, runner(cold_plan, cube, real, None), args.cold_steps, 1, 0)
+        dtc, evc, _ = timed_region(cold_plan, runner(cold_plan, cube, real, None), args.cold_steps, 1, 0)
         dtc = max_over_ranks(dtc)
         kc = [a.elapsed_time(b) for a, b in evc.values()]
         cold = {"ms_per_step": round(dtc / args.cold_steps * 1e3, 4), "kernel_ms": round(sum(kc) / max(1, len(kc)), 4),
@@ -635,7 +697,11 @@ def main(argv=None):
     # collective, and ranks that looped "until 250 ms have passed" would issue different numbers of them.
     per_step_ms = 0.25 * ntl * H / Hfull
     settle_steps = int(args.settle_ms / max(per_step_ms, 0.02) + 0.5) if args.settle_ms > 0 else 0
-    dt, ev = timed_region(plan, run_step, args.steps, args.warmup, settle_steps)
+    dt, ev, last = timed_region(plan, run_step, args.steps, args.warmup, settle_steps)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = snapshot_outputs(last, len(prob.names), H, W)      # before the launches below reuse the plan's buffers
+    del last
     gc.enable()
 
     # the same K1+K2 launch, event-bracketed every time, outside the timed region: >= 20 launches for roofline.frac
@@ -770,6 +836,8 @@ def main(argv=None):
             gm = fo.planes("matched").cpu().numpy().reshape(nb, H, W)
             line["cpu_baseline"], line["max_rel_err"] = cpu_baseline(args, pool, nworkers, cube_host, real_host, gp, gm)
             pool.shutdown()
+        if dump is not None:
+            line["dump_outputs"] = write_outputs(args.dump_outputs, dump[0], dump[1], H * W)
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
     if world > 1 or args.force_exchange:
         dist.barrier()

@@ -91,3 +91,30 @@ def test_bench_self_launch_relays_one_line_and_the_exit_status(tmp_path, monkeyp
             assert rc != 0 and buf.getvalue() == ""
         else:
             assert rc == want and buf.getvalue() == ""
+
+
+def test_bench_dump_outputs_contract(tmp_path):
+    """--dump-outputs DIR: the option parses, --steps really is a positive step count, the pixel sample of large images is
+    fixed (seeded, sorted, distinct) and keeps the files within 64 MB, and the writer stores float32 / float64 .npy files."""
+    import contextlib, io
+    import numpy as np
+    import pytest
+    import torch
+    bench = _load_bench()
+    a = bench.parse_args(["--dump-outputs", str(tmp_path), "--steps", "3"])
+    assert a.dump_outputs == str(tmp_path) and a.steps == 3 and bench.parse_args([]).dump_outputs is None
+    for bad in ("0", "-2"):
+        with contextlib.redirect_stderr(io.StringIO()), pytest.raises(SystemExit):
+            bench.parse_args(["--steps", bad])
+    assert bench.dump_pixel_sample(256 * 256, 13) is None                       # small images are written whole
+    idx = bench.dump_pixel_sample(1024 * 1024, 13)
+    assert np.array_equal(idx, bench.dump_pixel_sample(1024 * 1024, 13))
+    assert len(idx) == len(np.unique(idx)) == bench.DUMP_SAMPLE_PIXELS and np.all(np.diff(idx) > 0) and idx[-1] < 1024 * 1024
+    assert 2 * 16 * 4 * len(idx) + (1 << 20) <= 64 << 20
+    snap = {"coeffs": torch.ones(13, 4, dtype=torch.float64), "moments": torch.zeros(13, 11, dtype=torch.float64),
+            "pseudo": torch.rand(13, 64), "matched": torch.rand(13, 64)}
+    rec = bench.write_outputs(str(tmp_path / "d"), snap, None, 64)
+    for name, t in snap.items():
+        got = np.load(tmp_path / "d" / (name + ".npy"))
+        assert got.dtype == t.numpy().dtype and np.array_equal(got, t.numpy()) and rec["files"][name]["shape"] == list(got.shape)
+    assert rec["pixels"] == "all" and rec["bytes"] == sum(t.numel() * t.element_size() for t in snap.values())

@@ -2343,6 +2343,42 @@ def test_bench_line_carries_full_size_parity(torch_gpu):
     assert err["pixels_checked"] == 1024 * 1024 and err["pseudo"] < 2e-6 and err["matched"] < 1e-4, err
 
 
+def test_bench_dump_outputs(torch_gpu, tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's result as .npy files - whole images for a small tile (the same
+    bits in two runs: the inputs are seeded), a fixed pixel sample within 64 MB for the headline tile - and the dumped
+    matched image is the dumped polynomial applied to the dumped pseudo image."""
+    import json, subprocess
+    from conftest import ROOT
+    quick = ["--steps", "3", "--warmup", "1", "--settle-ms", "0", "--no-cpu-baseline", "--no-probe", "--placement-trials", "0",
+             "--cold-steps", "0", "--k1-launches", "0"]
+
+    def run(d, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *quick, *extra, "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        files = {n: np.load(d / (n + ".npy")) for n in ("coeffs", "moments", "pseudo", "matched")}
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in files)
+        assert sum(a.nbytes for a in files.values()) == line["dump_outputs"]["bytes"] <= 64 << 20
+        for n, a in files.items():
+            assert a.dtype == (np.float64 if n in ("coeffs", "moments") else np.float32) and np.isfinite(a).all(), n
+            assert list(a.shape) == line["dump_outputs"]["files"][n]["shape"]
+        nb = files["coeffs"].shape[0]
+        assert files["coeffs"].shape == (nb, 4) and files["moments"].shape == (nb, 11)
+        ref = onp.apply_poly_planes(files["pseudo"], files["coeffs"], None, clip=True)
+        assert np.max(np.abs(files["matched"] - ref)) < 1e-5
+        return files, nb
+
+    a, nb = run(tmp_path / "a", "--height", "256", "--width", "256")
+    assert a["pseudo"].shape == a["matched"].shape == (nb, 256, 256)
+    b, _ = run(tmp_path / "b", "--height", "256", "--width", "256")
+    for n in a:
+        assert a[n].tobytes() == b[n].tobytes(), n
+    c, _ = run(tmp_path / "c")
+    assert c["pseudo"].shape == c["matched"].shape == (nb, 1 << 18)
+
+
 def test_integration_md_stub_runs(torch_gpu):
     """The ctypes stub printed in INTEGRATION.md, exactly as a maintainer of the reference would write it (nothing
     from this package but the shared library), gives the package's own planes."""
