@@ -15,44 +15,51 @@
 #include "hsr_solve.h"
 #include "hsr_sync_dev.h"
 
+// The prepared launches of one tile and nothing else: creating a plan makes no HIP call.
 struct hsr_step_plan {
   hsr_step_desc d;
   int32_t k0[HSR_MAX_BANDS], klen[HSR_MAX_BANDS];
-  int32_t slots;
-  hipEvent_t ev_k1, ev_fit;       // pipeline: K1 of this slot enqueued / fit of this slot done
-  bool pending;                   // pipeline: K1 + fit enqueued, K3 not yet
-  bool fitted;                    // fused pipelines: the slot reduction (+ solve, without an exchange) of this slot's tile has been enqueued
-  bool exchanged;                 // four slots: gate -> collective -> solve of this slot's tile has been enqueued on the side stream
-  unsigned int seq;               // four slots: sequence number of the tile in this slot (the value of its "ready" word)
+  int32_t slots;                  // partial slots of the last K1 launch
 };
 
 enum { kTwoSlot = 0, kFused = 1, kExchange = 2, kGroup = 3 };
+
+// One slot of a pipeline: the plan it launches and the state of the tile it holds.
+struct pipe_slot {
+  hsr_step_plan* p = nullptr;
+  hipEvent_t ev_k1 = nullptr;     // two slots: K1 of this slot's tile enqueued
+  hipEvent_t ev_fit = nullptr;    // two slots, exchange: fit of this slot's tile done
+  bool pending = false;           // K1 + fit enqueued, K3 not yet
+  bool fitted = false;            // fused forms: the slot reduction (+ solve, without an exchange) of this slot's tile has been enqueued
+  bool exchanged = false;         // exchange: gate -> collective -> solve of this slot's tile has been enqueued on the side stream
+  unsigned int seq = 0;           // exchange: sequence number of the tile in this slot (the value of its "ready" word)
+};
+
 struct hsr_pipeline {
-  std::vector<hsr_step_plan*> slot;
-  int kind;                       // kTwoSlot: K3(i-1) as its own launch behind K1(i);  kFused (3 slots): K3(i-2) inside K1(i)'s launch;
+  std::vector<pipe_slot> slot;
+  int kind = kTwoSlot;            // kTwoSlot: K3(i-1) as its own launch behind K1(i);  kFused (3 slots): K3(i-2) inside K1(i)'s launch;
                                   // kExchange (4 slots): K3(i-3) inside K1(i)'s launch, exchange issued from C (hsr_pipeline_create_exchange);
                                   // kGroup (T + 2 slots): one fit per group of T tiles, K3(i-T-1) inside K1(i)'s launch (hsr_pipeline_create_group)
-  int nslots;
-  int group_T;                    // kGroup: tiles per fit
-  double* group_moments;          // kGroup: [2][T][nb][M] per-tile moments, by group parity
-  double* group_total;            //         [2][nb][M]
-  double* group_coeffs;           //         [2][nb][deg+1]
-  hipStream_t side;
-  int64_t n;                      // tiles submitted
-  int exchange;                   // two slots, 1: the caller runs the fit (reduce -> collective -> solve) itself between
+  int nslots = 0;
+  int group_T = 0;                // kGroup: tiles per fit
+  double* group_moments = nullptr;  // kGroup: [2][T][nb][M] per-tile moments, by group parity
+  double* group_total = nullptr;    //         [2][nb][M]
+  double* group_coeffs = nullptr;   //         [2][nb][deg+1]
+  hipStream_t side = nullptr;
+  int64_t n = 0;                  // tiles submitted
+  int exchange = 0;               // two slots, 1: the caller runs the fit (reduce -> collective -> solve) itself between
                                   //    hsr_pipeline_submit and hsr_pipeline_fit_done
-  unsigned int* counter;          // fused: ticket counter of the tail fits (device), and what it holds
-  unsigned int tickets;
+  unsigned int* sync = nullptr;   // fused forms, device words: [0] ticket counter of the tail fits, [1] bands whose moments are published,
+                                  //   [2] error code, [4 + k] "coefficients ready" word of slot k (holds the sequence number of its tile)
+  unsigned int tickets = 0;       // value sync[0] reaches once every launch enqueued so far has run
   // ---- four slots: the exchange is issued from here ----
-  hsr_exchange x;
-  unsigned int* sync;             // device words: [0] tickets (= counter), [1] bands whose moments are published, [2] error code,
-                                  //               [4 + k] "coefficients ready" word of slot k (holds the sequence number of its tile)
-  unsigned int published;         // value sync[1] reaches once every reduction enqueued so far has run (nb per tile)
-  int deferred;                   // slot whose solve + publish is not enqueued yet: it rides in the launch that gates the NEXT tile's
-  int deferred_solve;             // collective (one side-stream launch per step instead of two), or goes out alone at a drain; -1: none
-  double* host_moments[4];        // pinned staging of the host_sum transport, one per slot
-  struct host_job { hsr_pipeline* pl; double* values; int32_t count; } host_jobs[4];
-  volatile int host_error;        // host_sum returned non-zero
+  hsr_exchange x{};
+  unsigned int published = 0;     // value sync[1] reaches once every reduction enqueued so far has run (nb per tile)
+  int deferred = -1;              // slot whose solve + publish is not enqueued yet: it rides in the launch that gates the NEXT tile's
+  int deferred_solve = 0;         // collective (one side-stream launch per step instead of two), or goes out alone at a drain; -1: none
+  double* host_moments[4] = {};   // pinned staging of the host_sum transport, one per slot
+  struct host_job { hsr_pipeline* pl; double* values; int32_t count; } host_jobs[4] = {};
+  volatile int host_error = 0;    // host_sum returned non-zero
 };
 
 namespace {
@@ -123,9 +130,9 @@ int run_k1(hsr_step_plan* p, const void* cube, const float* real, const uint8_t*
                                    d.partials_dev, &p->slots, &d.opts, s);
 }
 
-int run_apply(hsr_step_plan* p, const uint8_t* mask, hipStream_t s) {
+int run_apply(const hsr_step_plan* p, const double* coeffs, const uint8_t* mask, hipStream_t s) {
   const hsr_step_desc& d = p->d;
-  return hsr_poly_apply(d.pseudo_dev, d.out_bs, d.out_ps, d.apply_mask ? mask : nullptr, d.coeffs_dev, d.nb, d.deg, d.npix,
+  return hsr_poly_apply(d.pseudo_dev, d.out_bs, d.out_ps, d.apply_mask ? mask : nullptr, coeffs, d.nb, d.deg, d.npix,
                         nullptr, d.clip, d.matched_dev, d.matched_bs, d.matched_ps, s);
 }
 
@@ -150,29 +157,14 @@ extern "C" int hsr_step_plan_create(const hsr_step_desc* desc, hsr_step_plan** o
   }
   p->d.k0 = p->k0;          // the plan owns its copy of the host tables
   p->d.klen = p->klen;
-  p->slots = 0;
-  p->pending = false;
-  p->ev_k1 = p->ev_fit = nullptr;
-  if (hipEventCreateWithFlags(&p->ev_k1, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&p->ev_fit, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    if (p->ev_k1) (void)hipEventDestroy(p->ev_k1);
-    delete p;
-    hsr::set_error("hsr_step_plan_create: hipEventCreate failed");
-    return HSR_ERR_HIP;
-  }
   *out = p;
   return HSR_OK;
 }
 
-extern "C" void hsr_step_plan_destroy(hsr_step_plan* p) {
-  if (!p) return;
-  (void)hipEventDestroy(p->ev_k1);
-  (void)hipEventDestroy(p->ev_fit);
-  delete p;
-}
+extern "C" void hsr_step_plan_destroy(hsr_step_plan* p) { delete p; }
 
 extern "C" int hsr_step_plan_slots(const hsr_step_plan* p) { return p ? p->slots : -1; }
+
 
 extern "C" int hsr_step_run(hsr_step_plan* p, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
                             hsr_stream_t stream) {
@@ -182,7 +174,7 @@ extern "C" int hsr_step_run(hsr_step_plan* p, const void* cube_dev, const float*
   if (rc != HSR_OK) return rc;
   rc = hsr_moments_reduce_solve(p->d.partials_dev, p->slots, p->d.nb, p->d.deg, p->d.min_count, p->d.moments_dev, p->d.coeffs_dev, s);
   if (rc != HSR_OK) return rc;
-  return run_apply(p, mask_dev, s);
+  return run_apply(p, p->d.coeffs_dev, mask_dev, s);
 }
 
 extern "C" int hsr_step_run_k1(hsr_step_plan* p, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
@@ -203,7 +195,7 @@ extern "C" int hsr_step_run_solve(hsr_step_plan* p, hsr_stream_t stream) {
 
 extern "C" int hsr_step_run_apply(hsr_step_plan* p, const uint8_t* mask_dev, hsr_stream_t stream) {
   HSR_REQUIRE(p, HSR_ERR_INVALID, "hsr_step_run_apply: NULL plan");
-  return run_apply(p, mask_dev, (hipStream_t)stream);
+  return run_apply(p, p->d.coeffs_dev, mask_dev, (hipStream_t)stream);
 }
 
 // ---- pipeline ------------------------------------------------------------------------------------------------
@@ -211,8 +203,9 @@ extern "C" int hsr_step_run_apply(hsr_step_plan* p, const uint8_t* mask_dev, hsr
 //     side stream     :  fit(0)        fit(1)        fit(2) ...          fit(i) runs under K1(i+1)
 // K3(i) waits for ev_fit(i) and precedes K1(i+2) in stream order, so two slots need no further events.  The event that
 // releases fit(i) is recorded behind K3(i-1), not between K1(i) and K3(i-1) (a record in between cost a 13 us bubble).
-static int pipeline_new(hsr_step_plan* const* sl, int nslots, hsr_stream_t side_stream, int32_t exchange, hsr_pipeline** out,
-                        const char* who) {
+// Argument checks first, then the HIP objects of the form: the device words of the fused forms, the events of the forms with
+// side-stream work (two slots, exchange).
+static int pipeline_new(hsr_step_plan* const* sl, int nslots, int kind, hsr_stream_t side_stream, hsr_pipeline** out, const char* who) {
   HSR_REQUIRE(out, HSR_ERR_INVALID, "%s: NULL argument", who);
   for (int i = 0; i < nslots; ++i) {
     HSR_REQUIRE(sl[i], HSR_ERR_INVALID, "%s: NULL plan", who);
@@ -221,44 +214,32 @@ static int pipeline_new(hsr_step_plan* const* sl, int nslots, hsr_stream_t side_
       // In one fused launch the pre-phase reads the coefficients of one slot, the tail writes the moments / coefficients and reads
       // the partials of another, K1 writes the partials of a third: aliased work buffers would race silently.
       const hsr_step_desc &a = sl[i]->d, &b = sl[k]->d;
-      HSR_REQUIRE(nslots == 2 || (a.partials_dev != b.partials_dev && a.moments_dev != b.moments_dev && a.coeffs_dev != b.coeffs_dev &&
-                                  a.pseudo_dev != b.pseudo_dev && a.matched_dev != b.matched_dev),
+      HSR_REQUIRE(kind == kTwoSlot || (a.partials_dev != b.partials_dev && a.moments_dev != b.moments_dev && a.coeffs_dev != b.coeffs_dev &&
+                                       a.pseudo_dev != b.pseudo_dev && a.matched_dev != b.matched_dev),
                   HSR_ERR_INVALID, "%s: plans %d and %d share a work buffer (partials / moments / coefficients / images must be distinct)", who, k, i);
     }
   }
   HSR_REQUIRE(side_stream != nullptr, HSR_ERR_INVALID, "%s: the side stream must be a real stream, not the default one", who);
   hsr_pipeline* pl = new (std::nothrow) hsr_pipeline();
   HSR_REQUIRE(pl, HSR_ERR_INVALID, "%s: out of host memory", who);
-  pl->slot.assign(sl, sl + nslots);
-  for (int i = 0; i < 4; ++i) pl->host_moments[i] = nullptr;
+  pl->slot.resize(nslots);
+  for (int k = 0; k < nslots; ++k) pl->slot[k].p = sl[k];
+  pl->kind = kind;
   pl->nslots = nslots;
-  pl->kind = nslots == 2 ? kTwoSlot : (nslots == 3 ? kFused : kExchange);      // (the create functions set the other kinds)
-  pl->group_T = 0;
-  pl->group_moments = pl->group_total = pl->group_coeffs = nullptr;
   pl->side = (hipStream_t)side_stream;
-  pl->n = 0;
-  pl->exchange = exchange ? 1 : 0;
-  pl->counter = nullptr;
-  pl->sync = nullptr;
-  pl->tickets = pl->published = 0;
-  pl->x = hsr_exchange{};
-  pl->host_error = 0;
-  pl->deferred = -1;
-  pl->deferred_solve = 0;
-  for (int k = 0; k < nslots; ++k) {
-    pl->slot[k]->pending = pl->slot[k]->fitted = pl->slot[k]->exchanged = false;
-    pl->slot[k]->seq = 0;
-  }
-  if (nslots >= 3) {              // not a launch-path call: the device words of the fused pipelines
-    if (hipMalloc(&pl->sync, 8 * sizeof(unsigned int)) != hipSuccess || hipMemset(pl->sync, 0, 8 * sizeof(unsigned int)) != hipSuccess ||
-        hipDeviceSynchronize() != hipSuccess) {
-      (void)hipGetLastError();
-      if (pl->sync) (void)hipFree(pl->sync);
-      delete pl;
-      hsr::set_error("%s: could not allocate the pipeline's device words", who);
-      return HSR_ERR_HIP;
-    }
-    pl->counter = pl->sync;
+  bool ok = true;
+  if (kind != kTwoSlot)           // not a launch-path call
+    ok = hipMalloc(&pl->sync, 8 * sizeof(unsigned int)) == hipSuccess && hipMemset(pl->sync, 0, 8 * sizeof(unsigned int)) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess;
+  if (kind == kTwoSlot || kind == kExchange)
+    for (pipe_slot& s : pl->slot)
+      ok = ok && hipEventCreateWithFlags(&s.ev_fit, hipEventDisableTiming) == hipSuccess &&
+           (kind != kTwoSlot || hipEventCreateWithFlags(&s.ev_k1, hipEventDisableTiming) == hipSuccess);
+  if (!ok) {
+    (void)hipGetLastError();
+    hsr_pipeline_destroy(pl);
+    hsr::set_error("%s: could not create the pipeline's device words or events", who);
+    return HSR_ERR_HIP;
   }
   *out = pl;
   return HSR_OK;
@@ -267,7 +248,9 @@ static int pipeline_new(hsr_step_plan* const* sl, int nslots, hsr_stream_t side_
 extern "C" int hsr_pipeline_create(hsr_step_plan* slot0, hsr_step_plan* slot1, hsr_stream_t side_stream, int32_t exchange,
                                    hsr_pipeline** out) {
   hsr_step_plan* sl[2] = {slot0, slot1};
-  return pipeline_new(sl, 2, side_stream, exchange, out, "hsr_pipeline_create");
+  int rc = pipeline_new(sl, 2, kTwoSlot, side_stream, out, "hsr_pipeline_create");
+  if (rc == HSR_OK) (*out)->exchange = exchange ? 1 : 0;
+  return rc;
 }
 
 // The fused launches need one tile geometry in every plan, 16-byte aligned pixel-major rows of 4 / 8 / 12 / 16 floats, and a K1
@@ -299,7 +282,7 @@ extern "C" int hsr_pipeline_create_fused(hsr_step_plan* slot0, hsr_step_plan* sl
   hsr_step_plan* ps[3] = {slot0, slot1, slot2};
   int rc = fused_geometry(ps, 3, "hsr_pipeline_create_fused");
   if (rc != HSR_OK) return rc;
-  return pipeline_new(ps, 3, side_stream, 0, out, "hsr_pipeline_create_fused");
+  return pipeline_new(ps, 3, kFused, side_stream, out, "hsr_pipeline_create_fused");
 }
 
 extern "C" int hsr_pipeline_create_exchange(hsr_step_plan* const* slots4, hsr_stream_t side_stream, const hsr_exchange* x,
@@ -319,11 +302,11 @@ extern "C" int hsr_pipeline_create_exchange(hsr_step_plan* const* slots4, hsr_st
   HSR_REQUIRE(slots4[0]->d.opts.reserved_cus >= 8, HSR_ERR_INVALID, "%s: the plans must leave at least 8 CUs free (hsr_srf_options.reserved_cus >= 8, one "
               "per XCD) for the side stream's kernels; got %d", who, slots4[0]->d.opts.reserved_cus);
   hsr_pipeline* pl = nullptr;
-  rc = pipeline_new(slots4, 4, side_stream, 1, &pl, who);
+  rc = pipeline_new(slots4, 4, kExchange, side_stream, &pl, who);
   if (rc != HSR_OK) return rc;
   pl->x = *x;
   if (x->host_sum) {
-    const size_t bytes = (size_t)pl->slot[0]->d.nb * hsr::moment_count(pl->slot[0]->d.deg) * sizeof(double);
+    const size_t bytes = (size_t)pl->slot[0].p->d.nb * hsr::moment_count(pl->slot[0].p->d.deg) * sizeof(double);
     for (int k = 0; k < 4; ++k) {
       if (hipHostMalloc(&pl->host_moments[k], bytes, hipHostMallocDefault) != hipSuccess) {
         (void)hipGetLastError();
@@ -347,9 +330,8 @@ extern "C" int hsr_pipeline_create_group(hsr_step_plan* const* slots, int32_t ns
   int rc = fused_geometry(slots, nslots, who);
   if (rc != HSR_OK) return rc;
   hsr_pipeline* pl = nullptr;
-  rc = pipeline_new(slots, nslots, side_stream, 0, &pl, who);
+  rc = pipeline_new(slots, nslots, kGroup, side_stream, &pl, who);
   if (rc != HSR_OK) return rc;
-  pl->kind = kGroup;
   pl->group_T = group_tiles;
   pl->group_moments = group_moments_dev;
   pl->group_total = group_total_dev;
@@ -361,26 +343,17 @@ extern "C" int hsr_pipeline_create_group(hsr_step_plan* const* slots, int32_t ns
 extern "C" void hsr_pipeline_destroy(hsr_pipeline* pl) {
   if (!pl) return;
   if (pl->kind == kExchange) (void)hipStreamSynchronize(pl->side);      // a host_sum callback may still point at this object
+  for (pipe_slot& s : pl->slot) {
+    if (s.ev_k1) (void)hipEventDestroy(s.ev_k1);
+    if (s.ev_fit) (void)hipEventDestroy(s.ev_fit);
+  }
   for (int k = 0; k < 4; ++k)
     if (pl->host_moments[k]) (void)hipHostFree(pl->host_moments[k]);
   if (pl->sync) (void)hipFree(pl->sync);
   delete pl;
 }
 
-static int finish_slot(hsr_pipeline* pl, hsr_step_plan* p, const uint8_t* mask, hipStream_t main) {
-  int rc = HSR_OK;
-  if (pl->kind == kFused) {                    // tail-fit pipeline: everything lives on the caller's stream
-    if (!p->fitted)
-      rc = hsr_moments_reduce_solve(p->d.partials_dev, p->slots, p->d.nb, p->d.deg, p->d.min_count, p->d.moments_dev, p->d.coeffs_dev, main);
-    p->fitted = true;
-  } else {
-    rc = hsr::check_hip(hipStreamWaitEvent(main, p->ev_fit, 0), "hsr_pipeline: wait for the fit");
-  }
-  if (rc != HSR_OK) return rc;
-  rc = run_apply(p, mask, main);
-  p->pending = false;
-  return rc;
-}
+static inline pipe_slot& slot_of(hsr_pipeline* pl, int64_t tile) { return pl->slot[tile % pl->nslots]; }
 
 // ---- four slots: the exchange issued from here ------------------------------------------------------------------------
 static void host_sum_trampoline(void* arg) {
@@ -388,24 +361,12 @@ static void host_sum_trampoline(void* arg) {
   if (j->pl->x.host_sum(j->pl->x.host_user, j->values, j->count) != 0) j->pl->host_error = 1;
 }
 
-// The slot reduction of a tile as a launch of its own on the caller's stream (tiles whose follower cannot carry it in its tail:
-// fewer workgroups than bands, or no follower at a drain), published like a tail reduction.
-static int reduce_and_publish(hsr_pipeline* pl, hsr_step_plan* p, hipStream_t main) {
-  int rc = hsr_moments_reduce(p->d.partials_dev, p->slots, p->d.nb, p->d.deg, p->d.moments_dev, main);
-  if (rc != HSR_OK) return rc;
-  hipLaunchKernelGGL(publish_add_kernel, dim3(1), dim3(64), 0, main, pl->sync + 1, (unsigned int)p->d.nb);
-  HSR_LAUNCH_CHECK("publish_add_kernel");
-  pl->published += (unsigned int)p->d.nb;
-  p->fitted = true;
-  return HSR_OK;
-}
-
 // solve + publish of the deferred slot, optionally going on as the gate of the next tile's collective
 static int launch_solve_publish(hsr_pipeline* pl, bool with_gate) {
-  hsr_step_plan* p = pl->slot[pl->deferred];
-  const hsr_step_desc& d = p->d;
+  const pipe_slot& s = pl->slot[pl->deferred];
+  const hsr_step_desc& d = s.p->d;
   hipLaunchKernelGGL(solve_publish_kernel, dim3(1), dim3(64), 0, pl->side, d.moments_dev, d.nb, d.deg, (long long)d.min_count, d.coeffs_dev,
-                     pl->deferred_solve, pl->sync + 4 + pl->deferred, p->seq, with_gate ? pl->sync + 1 : nullptr, pl->published, pl->sync + 2);
+                     pl->deferred_solve, pl->sync + 4 + pl->deferred, s.seq, with_gate ? pl->sync + 1 : nullptr, pl->published, pl->sync + 2);
   HSR_LAUNCH_CHECK("solve_publish_kernel");
   pl->deferred = -1;
   return HSR_OK;
@@ -414,8 +375,7 @@ static int launch_solve_publish(hsr_pipeline* pl, bool with_gate) {
 // gate -> collective -> solve + publish of the tile in slot k, on the side stream.  Called once per tile, in tile order, on every
 // rank: the collectives of all ranks line up.  The solve + publish itself is enqueued with the NEXT tile's gate (or by a drain).
 static int enqueue_exchange(hsr_pipeline* pl, int k) {
-  hsr_step_plan* p = pl->slot[k];
-  const hsr_step_desc& d = p->d;
+  const hsr_step_desc& d = pl->slot[k].p->d;
   const int64_t nmom = (int64_t)d.nb * hsr::moment_count(d.deg);
   int rc = HSR_OK;
   if (pl->deferred >= 0) {
@@ -449,95 +409,8 @@ static int enqueue_exchange(hsr_pipeline* pl, int k) {
   }
   pl->deferred = k;
   pl->deferred_solve = solve_here;
-  p->exchanged = true;
+  pl->slot[k].exchanged = true;
   return HSR_OK;
-}
-
-static int submit_exchange(hsr_pipeline* pl, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
-                           const uint8_t* prev_mask_dev, hipStream_t main, int32_t* finished_slot, void* k1_begin_event,
-                           void* k1_end_event) {
-  const int cur = (int)(pl->n % 4);
-  hsr_step_plan* p = pl->slot[cur];
-  const int ko = (int)((pl->n + 1) % 4), kl = (int)((pl->n + 3) % 4);
-  hsr_step_plan* old = pl->n >= 3 ? pl->slot[ko] : nullptr;        // tile n - 3: its K3 rides in this launch
-  hsr_step_plan* last = pl->n >= 1 ? pl->slot[kl] : nullptr;       // tile n - 1: its slot reduction rides in this launch's tail
-  int rc = HSR_OK;
-  hsr_apply_job job{};
-  job.sync_error_dev = pl->sync + 2;
-  const bool carry = old && old->pending;
-  if (carry) {
-    HSR_REQUIRE(old->exchanged, HSR_ERR_INVALID, "hsr_pipeline_submit: tile %lld has no exchange enqueued", (long long)(pl->n - 3));
-    job.x_dev = old->d.pseudo_dev;
-    job.out_dev = old->d.matched_dev;
-    job.coeffs_dev = old->d.coeffs_dev;
-    job.mask_dev = old->d.apply_mask ? prev_mask_dev : nullptr;
-    job.npix = old->d.npix;
-    job.clip = old->d.clip;
-    job.coeffs_ready_dev = pl->sync + 4 + ko;
-    job.coeffs_ready_value = old->seq;
-  }
-  const int grid = hsr_partial_slots(p->d.npix, &p->d.opts);
-  const bool reduce_last = last && last->pending && !last->fitted;
-  const bool ride = reduce_last && grid >= p->d.nb;                // one ticket per workgroup, one band per ticket
-  if (ride) {
-    job.fit_partials_dev = last->d.partials_dev;
-    job.fit_slots = last->slots;
-    job.fit_moments_dev = last->d.moments_dev;
-    job.fit_coeffs_dev = last->d.coeffs_dev;                       // not written in this mode
-    job.fit_min_count = last->d.min_count;
-    job.fit_counter_dev = pl->sync;
-    job.fit_ticket_base = pl->tickets;
-    job.fit_ready_dev = pl->sync + 1;
-  } else if (reduce_last) {
-    rc = reduce_and_publish(pl, last, main);
-    if (rc != HSR_OK) return rc;
-  }
-  if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-  if (rc != HSR_OK) return rc;
-  rc = run_k1(p, cube_dev, real_dev, mask_dev, main, (carry || ride) ? &job : nullptr);
-  if (rc != HSR_OK) return rc;
-  if (ride) {
-    HSR_REQUIRE(p->slots == grid, HSR_ERR_INVALID, "hsr_pipeline_submit: the launch used %d workgroups, %d expected", p->slots, grid);
-    pl->tickets += (unsigned int)p->slots;     // every workgroup of the launch drew one ticket
-    pl->published += (unsigned int)p->d.nb;
-    last->fitted = true;
-  }
-  if (k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
-  if (rc != HSR_OK) return rc;
-  if (reduce_last) {                           // its moments are (or will be, when this launch's tail runs) published: the exchange
-    rc = enqueue_exchange(pl, kl);
-    if (rc != HSR_OK) return rc;
-  }
-  if (carry) {
-    old->pending = false;
-    if (finished_slot) *finished_slot = ko;
-  }
-  p->pending = true;
-  p->fitted = p->exchanged = false;
-  p->seq = (unsigned int)(pl->n + 1);
-  pl->n += 1;
-  return HSR_OK;
-}
-
-// finish the tile in slot k outside a K1 launch (drain): reduction and exchange if they have not been enqueued yet, then K3 as its
-// own launch behind an event of the side stream
-static int finish_exchange_slot(hsr_pipeline* pl, int k, const uint8_t* mask, hipStream_t main) {
-  hsr_step_plan* p = pl->slot[k];
-  int rc = HSR_OK;
-  if (!p->fitted) rc = reduce_and_publish(pl, p, main);
-  if (rc == HSR_OK && !p->exchanged) rc = enqueue_exchange(pl, k);
-  if (rc == HSR_OK && pl->deferred >= 0) rc = launch_solve_publish(pl, false);     // (this tile's, or a later one's: at most one is deferred)
-  if (rc != HSR_OK) return rc;
-  // (an EVENT here, not a polling gate: this is a drain, a bubble costs nothing - and a wave spinning on the caller's stream would
-  // deadlock, until its time limit, against side-stream work queued behind it if the runtime serves both streams from one
-  // hardware queue.  Everything the side stream still holds in front of the record is released by launches that are already
-  // enqueued on the caller's stream.)
-  rc = hsr::check_hip(hipEventRecord(p->ev_fit, pl->side), "hsr_pipeline: record fit");
-  if (rc == HSR_OK) rc = hsr::check_hip(hipStreamWaitEvent(main, p->ev_fit, 0), "hsr_pipeline: wait for the fit");
-  if (rc != HSR_OK) return rc;
-  rc = run_apply(p, mask, main);
-  p->pending = false;
-  return rc;
 }
 
 // ---- T + 2 slots: ONE fit per group of T consecutive tiles (a mosaic held by one GPU) ----------------------------------
@@ -547,7 +420,7 @@ static int finish_exchange_slot(hsr_pipeline* pl, int k, const uint8_t* mask, hi
 // nothing but one kernel per tile on the caller's stream, no side stream, no events, no CUs kept free.  Buffers of two
 // consecutive groups never alias (parity).
 static inline size_t group_mom_doubles(const hsr_pipeline* pl) {
-  return (size_t)pl->slot[0]->d.nb * hsr::moment_count(pl->slot[0]->d.deg);
+  return (size_t)pl->slot[0].p->d.nb * hsr::moment_count(pl->slot[0].p->d.deg);
 }
 static inline double* group_entry(const hsr_pipeline* pl, int64_t tile) {      // moments of tile `tile` inside its group's array
   const int64_t g = tile / pl->group_T, i = tile % pl->group_T;
@@ -555,100 +428,199 @@ static inline double* group_entry(const hsr_pipeline* pl, int64_t tile) {      /
 }
 static inline double* group_total_of(const hsr_pipeline* pl, int64_t tile) { return pl->group_total + (size_t)((tile / pl->group_T) & 1) * group_mom_doubles(pl); }
 static inline double* group_coeffs_of(const hsr_pipeline* pl, int64_t tile) {
-  return pl->group_coeffs + (size_t)((tile / pl->group_T) & 1) * pl->slot[0]->d.nb * (pl->slot[0]->d.deg + 1);
+  return pl->group_coeffs + (size_t)((tile / pl->group_T) & 1) * pl->slot[0].p->d.nb * (pl->slot[0].p->d.deg + 1);
 }
 
-// slot reduction of tile `tile` (and, for a group's last tile, the group's fit) as launches of their own
-static int group_fit_standalone(hsr_pipeline* pl, int64_t tile, hipStream_t main) {
-  hsr_step_plan* p = pl->slot[tile % pl->nslots];
-  const hsr_step_desc& d = p->d;
-  int rc = hsr_moments_reduce(d.partials_dev, p->slots, d.nb, d.deg, group_entry(pl, tile), main);
-  if (rc == HSR_OK && tile % pl->group_T == pl->group_T - 1)
-    rc = hsr_moments_reduce_solve(group_entry(pl, tile - (pl->group_T - 1)), pl->group_T, d.nb, d.deg, d.min_count, group_total_of(pl, tile),
-                                  group_coeffs_of(pl, tile), main);
-  p->fitted = true;
+// ---- the three fused forms: one submit and one finish path -------------------------------------------------------------
+// Launch n = [K3 of tile n - (S - 1) as the pre-phase | K1+K2 of tile n | fit of tile n - 1 in the tail]: tile n - 2 (fused),
+// n - 3 (exchange), n - T - 1 (group).  What differs between the forms is in the helpers below, one switch each.
+
+// where the fit of a tile writes its moments, and the coefficients its K3 reads
+static inline double* moments_of(hsr_pipeline* pl, int64_t tile) { return pl->kind == kGroup ? group_entry(pl, tile) : slot_of(pl, tile).p->d.moments_dev; }
+static inline double* coeffs_of(hsr_pipeline* pl, int64_t tile) { return pl->kind == kGroup ? group_coeffs_of(pl, tile) : slot_of(pl, tile).p->d.coeffs_dev; }
+
+// K3 of `tile` as the pre-phase of a K1 launch
+static void job_apply(hsr_pipeline* pl, int64_t tile, const uint8_t* mask, hsr_apply_job* job) {
+  const pipe_slot& s = slot_of(pl, tile);
+  const hsr_step_desc& d = s.p->d;
+  job->x_dev = d.pseudo_dev;
+  job->out_dev = d.matched_dev;
+  job->coeffs_dev = coeffs_of(pl, tile);
+  job->mask_dev = d.apply_mask ? mask : nullptr;
+  job->npix = d.npix;
+  job->clip = d.clip;
+  if (pl->kind == kExchange) {               // the coefficients come from the side stream: wait for the slot's "ready" word
+    job->coeffs_ready_dev = pl->sync + 4 + tile % pl->nslots;
+    job->coeffs_ready_value = s.seq;
+  }
+}
+
+// the fit of `tile` in the tail of a K1 launch
+static void job_fit(hsr_pipeline* pl, int64_t tile, hsr_apply_job* job) {
+  const hsr_step_plan* p = slot_of(pl, tile).p;
+  job->fit_partials_dev = p->d.partials_dev;
+  job->fit_slots = p->slots;
+  job->fit_moments_dev = moments_of(pl, tile);
+  job->fit_coeffs_dev = coeffs_of(pl, tile);
+  job->fit_min_count = p->d.min_count;
+  job->fit_counter_dev = pl->sync;
+  job->fit_ticket_base = pl->tickets;
+  switch (pl->kind) {
+    case kExchange:                          // reduce only, and publish: the solve follows the collective on the side stream
+      job->fit_ready_dev = pl->sync + 1;
+      break;
+    case kGroup: {                           // the tile's entry of its group; behind the group's last tile the group's sum + solve
+      const int T = pl->group_T;
+      job->fit_group_tiles = T;
+      job->fit_group_index = (int32_t)(tile % T);
+      job->fit_group_moments_dev = group_entry(pl, tile - tile % T);
+      job->fit_group_total_dev = group_total_of(pl, tile);
+      break;
+    }
+  }
+}
+
+// the same fit as launches of its own on the caller's stream: for a tile whose follower cannot carry it, or at a drain
+static int fit_standalone(hsr_pipeline* pl, int64_t tile, hipStream_t main) {
+  pipe_slot& s = slot_of(pl, tile);
+  const hsr_step_desc& d = s.p->d;
+  int rc = HSR_OK;
+  switch (pl->kind) {
+    case kFused:
+      rc = hsr_moments_reduce_solve(d.partials_dev, s.p->slots, d.nb, d.deg, d.min_count, d.moments_dev, d.coeffs_dev, main);
+      break;
+    case kExchange:
+      rc = hsr_moments_reduce(d.partials_dev, s.p->slots, d.nb, d.deg, d.moments_dev, main);
+      if (rc != HSR_OK) return rc;
+      hipLaunchKernelGGL(publish_add_kernel, dim3(1), dim3(64), 0, main, pl->sync + 1, (unsigned int)d.nb);
+      HSR_LAUNCH_CHECK("publish_add_kernel");
+      pl->published += (unsigned int)d.nb;
+      break;
+    case kGroup: {
+      const int T = pl->group_T;
+      rc = hsr_moments_reduce(d.partials_dev, s.p->slots, d.nb, d.deg, group_entry(pl, tile), main);
+      if (rc == HSR_OK && tile % T == T - 1)
+        rc = hsr_moments_reduce_solve(group_entry(pl, tile - (T - 1)), T, d.nb, d.deg, d.min_count, group_total_of(pl, tile),
+                                      group_coeffs_of(pl, tile), main);
+      break;
+    }
+  }
+  if (rc == HSR_OK) s.fitted = true;
   return rc;
 }
 
-static int submit_group(hsr_pipeline* pl, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
+static int submit_fused(hsr_pipeline* pl, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
                         const uint8_t* prev_mask_dev, hipStream_t main, int32_t* finished_slot, void* k1_begin_event,
                         void* k1_end_event) {
-  const int S = pl->nslots, T = pl->group_T;
-  const int64_t n = pl->n;
-  hsr_step_plan* p = pl->slot[n % S];
-  hsr_step_plan* old = n >= T + 1 ? pl->slot[(n - (T + 1)) % S] : nullptr;      // tile n - (T + 1): its K3 rides in this launch
-  hsr_step_plan* last = n >= 1 ? pl->slot[(n - 1) % S] : nullptr;               // tile n - 1: its slot reduction rides in the tail
-  int rc = HSR_OK;
+  const int S = pl->nslots;
+  const int64_t n = pl->n, old = n - (S - 1), last = n - 1;
+  pipe_slot& cur = slot_of(pl, n);
+  const bool carry = old >= 0 && slot_of(pl, old).pending;                                  // its K3 rides in this launch
+  const bool fit_last = last >= 0 && slot_of(pl, last).pending && !slot_of(pl, last).fitted;
+  HSR_REQUIRE(!carry || pl->kind != kExchange || slot_of(pl, old).exchanged, HSR_ERR_INVALID,
+              "hsr_pipeline_submit: tile %lld has no exchange enqueued", (long long)old);
   hsr_apply_job job{};
-  const bool carry = old && old->pending;
-  if (carry) {
-    job.x_dev = old->d.pseudo_dev;
-    job.out_dev = old->d.matched_dev;
-    job.coeffs_dev = group_coeffs_of(pl, n - (T + 1));
-    job.mask_dev = old->d.apply_mask ? prev_mask_dev : nullptr;
-    job.npix = old->d.npix;
-    job.clip = old->d.clip;
-  }
-  const int grid = hsr_partial_slots(p->d.npix, &p->d.opts);
-  const bool fit_last = last && last->pending && !last->fitted;
-  const bool ride = fit_last && grid >= p->d.nb;
-  if (ride) {
-    job.fit_partials_dev = last->d.partials_dev;
-    job.fit_slots = last->slots;
-    job.fit_moments_dev = group_entry(pl, n - 1);
-    job.fit_coeffs_dev = group_coeffs_of(pl, n - 1);
-    job.fit_min_count = last->d.min_count;
-    job.fit_counter_dev = pl->counter;
-    job.fit_ticket_base = pl->tickets;
-    job.fit_group_tiles = T;
-    job.fit_group_index = (int32_t)((n - 1) % T);
-    job.fit_group_moments_dev = group_entry(pl, (n - 1) - (n - 1) % T);
-    job.fit_group_total_dev = group_total_of(pl, n - 1);
-  } else if (fit_last) {
-    rc = group_fit_standalone(pl, n - 1, main);
-    if (rc != HSR_OK) return rc;
-  }
-  if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-  if (rc != HSR_OK) return rc;
-  rc = run_k1(p, cube_dev, real_dev, mask_dev, main, (carry || ride) ? &job : nullptr);
+  if (pl->kind == kExchange) job.sync_error_dev = pl->sync + 2;
+  if (carry) job_apply(pl, old, prev_mask_dev, &job);
+  // Every workgroup of the launch draws ONE ticket and tickets 0 .. nb-1 fit one band each: a launch of fewer workgroups than bands
+  // - a tile of fewer than nb 64-pixel groups - cannot carry the fit, which then runs in front of it as launches of its own.  (Found
+  // by tools/dbg/stress_fused.py: a 2 x 158 tile with 7 bands kept two stale rows.)
+  const int grid = hsr_partial_slots(cur.p->d.npix, &cur.p->d.opts);
+  const bool ride = fit_last && grid >= cur.p->d.nb;
+  int rc = HSR_OK;
+  if (ride) job_fit(pl, last, &job);
+  else if (fit_last) rc = fit_standalone(pl, last, main);
+  if (rc == HSR_OK && k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
+  if (rc == HSR_OK) rc = run_k1(cur.p, cube_dev, real_dev, mask_dev, main, (carry || ride) ? &job : nullptr);
   if (rc != HSR_OK) return rc;
   if (ride) {
-    HSR_REQUIRE(p->slots == grid, HSR_ERR_INVALID, "hsr_pipeline_submit: the launch used %d workgroups, %d expected", p->slots, grid);
-    pl->tickets += (unsigned int)p->slots;
-    last->fitted = true;
+    // the ticket base advances by the workgroups the launch REALLY had (run_k1 reports them), and that must be the number the
+    // "can this launch carry the fit" test above was made with
+    HSR_REQUIRE(cur.p->slots == grid, HSR_ERR_INVALID, "hsr_pipeline_submit: the launch used %d workgroups, %d expected", cur.p->slots, grid);
+    pl->tickets += (unsigned int)cur.p->slots;
+    if (pl->kind == kExchange) pl->published += (unsigned int)cur.p->d.nb;
+    slot_of(pl, last).fitted = true;
   }
   if (k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
+  // exchange: the moments of tile n - 1 are (or will be, when this launch's tail runs) published - its collective
+  if (rc == HSR_OK && fit_last && pl->kind == kExchange) rc = enqueue_exchange(pl, (int)(last % S));
   if (rc != HSR_OK) return rc;
   if (carry) {
-    old->pending = false;
-    if (finished_slot) *finished_slot = (int)((n - (T + 1)) % S);
+    slot_of(pl, old).pending = false;
+    if (finished_slot) *finished_slot = (int)(old % S);
   }
-  p->pending = true;
-  p->fitted = false;
+  cur.pending = true;
+  cur.fitted = cur.exchanged = false;
+  cur.seq = (unsigned int)(n + 1);
   pl->n += 1;
   return HSR_OK;
 }
 
-// drain: tile i (the oldest unfinished one).  Whole groups only: a group whose last tile has not been submitted has no polynomial.
-static int finish_group_slot(hsr_pipeline* pl, int64_t i, const uint8_t* mask, hipStream_t main) {
-  const int T = pl->group_T;
-  HSR_REQUIRE(pl->n % T == 0, HSR_ERR_INVALID, "hsr_pipeline_flush: %lld tiles submitted, not a whole number of groups of %d - the last group "
-              "has no fit yet", (long long)pl->n, T);
+// drain: tile i (the oldest unfinished one) outside a K1 launch - its fit enqueued if it is not yet, then K3 as its own launch with
+// the tile's coefficients
+static int finish_fused(hsr_pipeline* pl, int64_t i, const uint8_t* mask, hipStream_t main) {
+  // A group's polynomial needs every reduction of the group: whole groups only, and the open reductions (only the newest tile's can
+  // be) go out first.
+  HSR_REQUIRE(pl->kind != kGroup || pl->n % pl->group_T == 0, HSR_ERR_INVALID,
+              "hsr_pipeline_flush: %lld tiles submitted, not a whole number of groups of %d - the last group has no fit yet", (long long)pl->n, pl->group_T);
   int rc = HSR_OK;
-  for (int64_t k = i; k < pl->n && rc == HSR_OK; ++k) {          // every reduction up to the end of the tile's group (only the last tile's can be open)
-    hsr_step_plan* q = pl->slot[k % pl->nslots];
-    if (q->pending && !q->fitted) rc = group_fit_standalone(pl, k, main);
+  for (int64_t k = i; k < (pl->kind == kGroup ? pl->n : i + 1) && rc == HSR_OK; ++k)
+    if (slot_of(pl, k).pending && !slot_of(pl, k).fitted) rc = fit_standalone(pl, k, main);
+  pipe_slot& s = slot_of(pl, i);
+  if (pl->kind == kExchange) {
+    if (rc == HSR_OK && !s.exchanged) rc = enqueue_exchange(pl, (int)(i % pl->nslots));
+    if (rc == HSR_OK && pl->deferred >= 0) rc = launch_solve_publish(pl, false);     // (this tile's, or a later one's: at most one is deferred)
+    // (an EVENT here, not a polling gate: this is a drain, a bubble costs nothing - and a wave spinning on the caller's stream would
+    // deadlock, until its time limit, against side-stream work queued behind it if the runtime serves both streams from one
+    // hardware queue.  Everything the side stream still holds in front of the record is released by launches that are already
+    // enqueued on the caller's stream.)
+    if (rc == HSR_OK) rc = hsr::check_hip(hipEventRecord(s.ev_fit, pl->side), "hsr_pipeline: record fit");
+    if (rc == HSR_OK) rc = hsr::check_hip(hipStreamWaitEvent(main, s.ev_fit, 0), "hsr_pipeline: wait for the fit");
   }
   if (rc != HSR_OK) return rc;
-  hsr_step_plan* p = pl->slot[i % pl->nslots];
-  const hsr_step_desc& d = p->d;
-  rc = hsr_poly_apply(d.pseudo_dev, d.out_bs, d.out_ps, d.apply_mask ? mask : nullptr, group_coeffs_of(pl, i), d.nb, d.deg, d.npix, nullptr, d.clip,
-                      d.matched_dev, d.matched_bs, d.matched_ps, main);
-  p->pending = false;
+  rc = run_apply(s.p, coeffs_of(pl, i), mask, main);
+  s.pending = false;
   return rc;
 }
 
-// Starts tile i in slot i % S and finishes tile i-1 (two slots), i-2 (fused) or i-3 (fused with exchange): its K3.
+// ---- two slots: the fit on the side stream, K3 as its own launch ---------------------------------------------------------
+static int finish_two_slot(pipe_slot& s, const uint8_t* mask, hipStream_t main) {
+  int rc = hsr::check_hip(hipStreamWaitEvent(main, s.ev_fit, 0), "hsr_pipeline: wait for the fit");
+  if (rc != HSR_OK) return rc;
+  rc = run_apply(s.p, s.p->d.coeffs_dev, mask, main);
+  s.pending = false;
+  return rc;
+}
+
+static int submit_two_slot(hsr_pipeline* pl, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
+                           const uint8_t* prev_mask_dev, hipStream_t main, int32_t* finished_slot, void* k1_begin_event,
+                           void* k1_end_event) {
+  const int cur = (int)(pl->n % 2);
+  pipe_slot &s = pl->slot[cur], &prev = pl->slot[cur ^ 1];
+  int rc = HSR_OK;
+  if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
+  if (rc == HSR_OK) rc = run_k1(s.p, cube_dev, real_dev, mask_dev, main);
+  if (rc == HSR_OK && k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
+  if (rc != HSR_OK) return rc;
+  if (prev.pending) {
+    rc = finish_two_slot(prev, prev_mask_dev, main);
+    if (rc != HSR_OK) return rc;
+    if (finished_slot) *finished_slot = cur ^ 1;
+  }
+  rc = hsr::check_hip(hipEventRecord(s.ev_k1, main), "hsr_pipeline: record K1");
+  if (rc == HSR_OK) rc = hsr::check_hip(hipStreamWaitEvent(pl->side, s.ev_k1, 0), "hsr_pipeline: side stream wait");
+  if (rc == HSR_OK && !pl->exchange) {
+    const hsr_step_desc& d = s.p->d;
+    rc = hsr_moments_reduce_solve(d.partials_dev, s.p->slots, d.nb, d.deg, d.min_count, d.moments_dev, d.coeffs_dev, pl->side);
+    if (rc == HSR_OK) rc = hsr::check_hip(hipEventRecord(s.ev_fit, pl->side), "hsr_pipeline: record fit");
+  }
+  if (rc != HSR_OK) return rc;
+  s.pending = true;
+  pl->n += 1;
+  return HSR_OK;
+}
+
+// Starts tile i in slot i % S and finishes tile i-1 (two slots), i-2 (fused), i-3 (fused with exchange) or i-T-1 (group): its K3.
 // *finished_slot = slot of the finished tile, or -1.  prev_mask_dev: the mask of the tile being finished (only read when the
 // plan applies the mask in K3).
 // Two slots, exchange = 0: the fit (slot reduction + solve) is enqueued on the side stream here.  With exchange = 1 the side stream
@@ -658,103 +630,18 @@ extern "C" int hsr_pipeline_submit(hsr_pipeline* pl, const void* cube_dev, const
                                    const uint8_t* prev_mask_dev, hsr_stream_t main_stream, int32_t* finished_slot,
                                    void* k1_begin_event, void* k1_end_event) {
   HSR_REQUIRE(pl && cube_dev && real_dev, HSR_ERR_INVALID, "hsr_pipeline_submit: NULL argument");
-  hipStream_t main = (hipStream_t)main_stream;
-  const int S = pl->nslots;
-  const int cur = (int)(pl->n % S);
-  hsr_step_plan* p = pl->slot[cur];
-  HSR_REQUIRE(!p->pending, HSR_ERR_INVALID, "hsr_pipeline_submit: slot %d still holds an unfinished tile", cur);
-  int rc = HSR_OK;
+  const int cur = (int)(pl->n % pl->nslots);
+  HSR_REQUIRE(!pl->slot[cur].pending, HSR_ERR_INVALID, "hsr_pipeline_submit: slot %d still holds an unfinished tile", cur);
   if (finished_slot) *finished_slot = -1;
-  if (pl->kind == kExchange) return submit_exchange(pl, cube_dev, real_dev, mask_dev, prev_mask_dev, main, finished_slot, k1_begin_event, k1_end_event);
-  if (pl->kind == kGroup) return submit_group(pl, cube_dev, real_dev, mask_dev, prev_mask_dev, main, finished_slot, k1_begin_event, k1_end_event);
-  if (pl->kind == kFused) {
-    // fused: this launch carries K3 of tile n - 2 (slot (n + 1) % 3); its fit has had all of K1(n - 1) to finish
-    hsr_step_plan* old = pl->n >= 2 ? pl->slot[(pl->n + 1) % 3] : nullptr;
-    hsr_apply_job job{};
-    const bool carry = old && old->pending;
-    if (carry) {
-      job.x_dev = old->d.pseudo_dev;
-      job.out_dev = old->d.matched_dev;
-      job.coeffs_dev = old->d.coeffs_dev;
-      job.mask_dev = old->d.apply_mask ? prev_mask_dev : nullptr;
-      job.npix = old->d.npix;
-      job.clip = old->d.clip;
-    }
-    hsr_step_plan* last = pl->n >= 1 ? pl->slot[(pl->n + 2) % 3] : nullptr;     // tile n - 1: its fit rides in this launch's tail
-    const int grid = hsr_partial_slots(p->d.npix, &p->d.opts);
-    // (every workgroup of the launch draws ONE ticket and tickets 0 .. nb-1 fit one band each: a launch of fewer workgroups
-    // than bands - a tile of fewer than nb 64-pixel groups - cannot carry the fit; that tile's fit runs as its own launch
-    // below, when its K3 comes up.  Found by tools/dbg/stress_fused.py: a 2 x 158 tile with 7 bands kept two stale rows.)
-    if (last && last->pending && !last->fitted && grid >= p->d.nb) {
-      job.fit_partials_dev = last->d.partials_dev;
-      job.fit_slots = last->slots;
-      job.fit_moments_dev = last->d.moments_dev;
-      job.fit_coeffs_dev = last->d.coeffs_dev;
-      job.fit_min_count = last->d.min_count;
-      job.fit_counter_dev = pl->counter;
-      job.fit_ticket_base = pl->tickets;
-    }
-    if (carry && !old->fitted) {                 // its fit did not ride in the previous launch (see above): a launch of its own
-      rc = hsr_moments_reduce_solve(old->d.partials_dev, old->slots, old->d.nb, old->d.deg, old->d.min_count, old->d.moments_dev,
-                                    old->d.coeffs_dev, main);
-      if (rc != HSR_OK) return rc;
-      old->fitted = true;
-    }
-    if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-    if (rc != HSR_OK) return rc;
-    rc = run_k1(p, cube_dev, real_dev, mask_dev, main, (carry || job.fit_partials_dev) ? &job : nullptr);
-    if (rc != HSR_OK) return rc;
-    if (job.fit_partials_dev) {
-      // the ticket base advances by the workgroups the launch REALLY had (run_k1 reports them), and that must be the number the
-      // "can this launch carry the fit" test above was made with
-      HSR_REQUIRE(p->slots == grid, HSR_ERR_INVALID, "hsr_pipeline_submit: the launch used %d workgroups, %d expected", p->slots, grid);
-      pl->tickets += (unsigned int)p->slots;
-      last->fitted = true;
-    }
-    if (k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
-    if (rc != HSR_OK) return rc;
-    if (carry) {
-      old->pending = false;
-      if (finished_slot) *finished_slot = (int)((pl->n + 1) % 3);
-    }
-    p->pending = true;                    // tail fits: nothing on the side stream, no events
-    p->fitted = false;
-    pl->n += 1;
-    return HSR_OK;
-  }
-  hsr_step_plan* prev = pl->slot[cur ^ 1];
-  if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-  if (rc != HSR_OK) return rc;
-  rc = run_k1(p, cube_dev, real_dev, mask_dev, main);
-  if (rc != HSR_OK) return rc;
-  if (k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
-  if (rc != HSR_OK) return rc;
-  if (prev->pending) {
-    rc = finish_slot(pl, prev, prev_mask_dev, main);
-    if (rc != HSR_OK) return rc;
-    if (finished_slot) *finished_slot = cur ^ 1;
-  }
-  rc = hsr::check_hip(hipEventRecord(p->ev_k1, main), "hsr_pipeline: record K1");
-  if (rc != HSR_OK) return rc;
-  rc = hsr::check_hip(hipStreamWaitEvent(pl->side, p->ev_k1, 0), "hsr_pipeline: side stream wait");
-  if (rc != HSR_OK) return rc;
-  if (!pl->exchange) {
-    rc = hsr_moments_reduce_solve(p->d.partials_dev, p->slots, p->d.nb, p->d.deg, p->d.min_count, p->d.moments_dev,
-                                  p->d.coeffs_dev, pl->side);
-    if (rc != HSR_OK) return rc;
-    rc = hsr::check_hip(hipEventRecord(p->ev_fit, pl->side), "hsr_pipeline: record fit");
-    if (rc != HSR_OK) return rc;
-  }
-  p->pending = true;
-  pl->n += 1;
-  return HSR_OK;
+  hipStream_t main = (hipStream_t)main_stream;
+  if (pl->kind == kTwoSlot) return submit_two_slot(pl, cube_dev, real_dev, mask_dev, prev_mask_dev, main, finished_slot, k1_begin_event, k1_end_event);
+  return submit_fused(pl, cube_dev, real_dev, mask_dev, prev_mask_dev, main, finished_slot, k1_begin_event, k1_end_event);
 }
 
 // two slots, exchange = 1: the caller has enqueued the fit of the slot submitted last on the side stream.
 extern "C" int hsr_pipeline_fit_done(hsr_pipeline* pl) {
   HSR_REQUIRE(pl && pl->n > 0 && pl->kind == kTwoSlot, HSR_ERR_INVALID, "hsr_pipeline_fit_done: nothing submitted, or not a two-slot pipeline");
-  hsr_step_plan* p = pl->slot[(pl->n - 1) % pl->nslots];
-  return hsr::check_hip(hipEventRecord(p->ev_fit, pl->side), "hsr_pipeline: record fit");
+  return hsr::check_hip(hipEventRecord(slot_of(pl, pl->n - 1).ev_fit, pl->side), "hsr_pipeline: record fit");
 }
 
 // K3 of the OLDEST tile left in the pipeline; *finished_slot = its slot or -1.
@@ -763,11 +650,10 @@ extern "C" int hsr_pipeline_flush(hsr_pipeline* pl, const uint8_t* mask_dev, hsr
   if (finished_slot) *finished_slot = -1;
   const int S = pl->nslots;
   for (int64_t i = pl->n >= S - 1 ? pl->n - (S - 1) : 0; i < pl->n; ++i) {
-    hsr_step_plan* p = pl->slot[i % S];
-    if (!p->pending) continue;
-    int rc = pl->kind == kExchange ? finish_exchange_slot(pl, (int)(i % S), mask_dev, (hipStream_t)main_stream)
-             : pl->kind == kGroup  ? finish_group_slot(pl, i, mask_dev, (hipStream_t)main_stream)
-                                   : finish_slot(pl, p, mask_dev, (hipStream_t)main_stream);
+    pipe_slot& s = slot_of(pl, i);
+    if (!s.pending) continue;
+    const int rc = pl->kind == kTwoSlot ? finish_two_slot(s, mask_dev, (hipStream_t)main_stream)
+                                        : finish_fused(pl, i, mask_dev, (hipStream_t)main_stream);
     if (rc == HSR_OK && finished_slot) *finished_slot = (int)(i % S);
     return rc;
   }

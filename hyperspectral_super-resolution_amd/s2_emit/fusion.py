@@ -434,6 +434,11 @@ class SpectralFusion:
         for kind, h in reversed(handles):                       # pipelines before the plans they point to
             (lib.hsr_pipeline_destroy if kind == "pipe" else lib.hsr_step_plan_destroy)(h)
 
+    def _drop_handles(self, handles):
+        """Destroy these handles now instead of at close()."""
+        self._native_handles = [e for e in self._native_handles if not any(e[1] is h for _, h in handles)]
+        self._destroy_handles(handles)
+
     # ---- the exchange of an exchange pipeline ----------------------------------------------------------------------------
     def comm(self):
         """The library's own RCCL communicator over this plan's group (built on first use; collective over the group)."""
@@ -888,8 +893,7 @@ class SpectralFusion:
             # return them first, in order (round 3 dropped them here: a mosaic with a ragged last tile lost one or two tiles)
             self._backlog = self.drain()               # (drain() hands over what the backlog already held, in front)
             old, self._pipe = self._pipe, None
-            self._native_handles = [e for e in self._native_handles if not any(e[1] is h for _, h in old["handles"])]
-            self._destroy_handles(old["handles"])
+            self._drop_handles(old["handles"])
         npix = cube.numel() // cube.shape[-1]
         real2, real_layout = self._real_image(real, npix)
         if not (real2.is_cuda and real2.dtype == torch.float32):
@@ -906,17 +910,20 @@ class SpectralFusion:
             placed = [eng.alloc_image(torch, nb, npix, self.layout, self.device) for _ in range(2)]
             if self.placement_trials > 1 and npix >= (1 << 16):
                 placed = self._place(npix, placed, probe, count=2)       # ONE search for both slots' images
-        # Three forms: two slots (fit on the side stream, K3 as its own launch); fused, three slots (one kernel per tile, fit in the
-        # tail: no exchange possible); fused with the exchange issued from C, four slots (hsr_pipeline_create_exchange).
+        # Four forms: two slots (fit on the side stream, K3 as its own launch); fused, three slots (one kernel per tile, fit in the
+        # tail: no exchange possible); fused with the exchange issued from C, four slots (hsr_pipeline_create_exchange); fused with
+        # one fit per group of T tiles, T + 2 slots (hsr_pipeline_create_group).
         # The C side decides whether a K1 launch of this geometry can carry the older tile's K3 (hsr_srf_fused_launch_supported, called
         # by the create functions); what it cannot see is the cube pointer - uint16 tiles need the 16-byte aligned loader.
         exchange = self._exchanges()
         if self.group_tiles > 1 and (exchange or not self.fuse_apply or self.layout != nat.PIXMAJOR):
             raise ValueError("group_tiles > 1 needs fuse_apply=True, the pixel-major layout and no exchange (multi-rank mosaics: fuse_mosaic)")
-        fused = (self.fuse_apply and self.layout == nat.PIXMAJOR and
-                 (cube.dtype == torch.float32 or (cube.data_ptr() % 16 == 0 and not self.u16_single_buffer)))
-        grouped = fused and not exchange and self.group_tiles > 1
-        nslots = (self.group_tiles + 2 if grouped else (4 if exchange else 3)) if fused else 2
+        if not (self.fuse_apply and self.layout == nat.PIXMAJOR and
+                (cube.dtype == torch.float32 or (cube.data_ptr() % 16 == 0 and not self.u16_single_buffer))):
+            form = "two"
+        else:
+            form = "group" if self.group_tiles > 1 else ("exchange" if exchange else "fused")
+        nslots = {"two": 2, "fused": 3, "exchange": 4, "group": self.group_tiles + 2}[form]
         while len(placed) < nslots:
             placed.append(eng.alloc_image(torch, nb, npix, self.layout, self.device))
         slots, outs, handles = [], [], []
@@ -928,53 +935,44 @@ class SpectralFusion:
             handles.append(("plan", h))
             slots.append(dict(plan=h, ws=ws, keep=keep, mask=None))
             outs.append(FusionOutput(self.names, placed[k], ws.moments, ws.coeffs, matched, self.layout))
-        if self.side_stream is not None:
-            side = self.side_stream
-        elif fused and not exchange:                   # the three-slot pipeline has no side-stream work: nothing to choose
-            side = torch.cuda.Stream(device=self.device)
-        elif fused:
-            # gate -> collective -> solve run under K1 on this stream: chosen by MEASUREMENT like the two-slot pipeline's (some of a
-            # process's high-priority streams are served by a hardware queue on which side work next to the persistent K1 costs
-            # ~100 us per step: r04 shard curve, 338 us per 1024-row step on the 5th such stream of the process against 229)
-            side = self._pick_side_stream(slots, cube, real2, mask)
-        else:
-            side = self._pick_side_stream(slots, cube, real2, mask)
+        # The fused and group pipelines have no side-stream work: nothing to choose.  The exchange pipeline runs gate -> collective ->
+        # solve under K1 on it: chosen by MEASUREMENT like the two-slot pipeline's (some of a process's high-priority streams are
+        # served by a hardware queue on which side work next to the persistent K1 costs ~100 us per step: r04 shard curve, 338 us per
+        # 1024-row step on the 5th such stream of the process against 229).
+        side = (self.side_stream if self.side_stream is not None else
+                torch.cuda.Stream(device=self.device) if form in ("fused", "group") else
+                self._pick_side_stream(slots, cube, real2, mask))
         ph = C.c_void_p()
-        transport = None
-        gbuf = None
-        if grouped:
+        plans = [sl["plan"] for sl in slots]
+        transport = gbuf = None
+        if form == "group":
             T, M = self.group_tiles, 3 * self.deg + 2
             gbuf = (torch.zeros((2, T, nb, M), dtype=torch.float64, device=self.device), torch.zeros((2, nb, M), dtype=torch.float64, device=self.device),
                     torch.zeros((2, nb, self.deg + 1), dtype=torch.float64, device=self.device))
-            arr = (C.c_void_p * nslots)(*[sl["plan"] for sl in slots])
-            rc = lib.hsr_pipeline_create_group(arr, nslots, T, gbuf[0].data_ptr(), gbuf[1].data_ptr(), gbuf[2].data_ptr(),
-                                               C.c_void_p(side.cuda_stream), C.byref(ph))
-        elif fused and exchange:
-            x, transport = self._exchange_desc()
-            arr = (C.c_void_p * 4)(*[sl["plan"] for sl in slots])
-            rc = lib.hsr_pipeline_create_exchange(arr, C.c_void_p(side.cuda_stream), C.byref(x), C.byref(ph))
-        elif fused:
-            rc = lib.hsr_pipeline_create_fused(slots[0]["plan"], slots[1]["plan"], slots[2]["plan"], C.c_void_p(side.cuda_stream),
-                                               0, C.byref(ph))
-        if grouped and rc != nat.HSR_OK:
-            nat.check(rc, "hsr_pipeline_create_group")      # a group fit has no two-slot form to fall back to
-        if fused and rc != nat.HSR_OK:                 # geometry the fused launch does not cover: the two-slot pipeline
-            fused, transport = False, None
-            self.fused_fallback = nat.load().hsr_last_error().decode("utf-8", "replace")
-            for kind, h in reversed(handles[2:]):
-                lib.hsr_step_plan_destroy(h)
-            self._native_handles = [e for e in self._native_handles if not any(e[1] is h for _, h in handles[2:])]
-            slots, outs, handles = slots[:2], outs[:2], handles[:2]
-            if self.side_stream is None:
-                side = self._pick_side_stream(slots, cube, real2, mask)
-        if not fused:
+            # (a group fit has no two-slot form to fall back to)
+            nat.check(lib.hsr_pipeline_create_group((C.c_void_p * nslots)(*plans), nslots, T, gbuf[0].data_ptr(), gbuf[1].data_ptr(),
+                                                    gbuf[2].data_ptr(), C.c_void_p(side.cuda_stream), C.byref(ph)), "hsr_pipeline_create_group")
+        elif form != "two":
+            if form == "exchange":
+                x, transport = self._exchange_desc()
+                rc = lib.hsr_pipeline_create_exchange((C.c_void_p * 4)(*plans), C.c_void_p(side.cuda_stream), C.byref(x), C.byref(ph))
+            else:
+                rc = lib.hsr_pipeline_create_fused(*plans, C.c_void_p(side.cuda_stream), 0, C.byref(ph))
+            if rc != nat.HSR_OK:                       # geometry the fused launch does not cover: the two-slot pipeline
+                form, transport = "two", None
+                self.fused_fallback = lib.hsr_last_error().decode("utf-8", "replace")
+                self._drop_handles(handles[2:])
+                slots, outs, handles = slots[:2], outs[:2], handles[:2]
+                if self.side_stream is None:
+                    side = self._pick_side_stream(slots, cube, real2, mask)
+        if form == "two":
             nat.check(lib.hsr_pipeline_create(slots[0]["plan"], slots[1]["plan"], C.c_void_p(side.cuda_stream), 1 if exchange else 0,
                                               C.byref(ph)), "hsr_pipeline_create")
         self._native_handles.append(("pipe", ph))
         handles.append(("pipe", ph))
         self._pipe = dict(key=key, npix=npix, h=ph, slots=slots, outs=outs, side=side, side_handle=C.c_void_p(side.cuda_stream),
-                          exchange=exchange, n=0, fin=C.c_int32(-1), fused=fused, S=len(slots), inflight=[], handles=handles,
-                          c_exchange=bool(fused and exchange), transport=transport, group=gbuf, done=0)
+                          exchange=exchange, n=0, fin=C.c_int32(-1), fused=form != "two", S=len(slots), inflight=[], handles=handles,
+                          c_exchange=form == "exchange", transport=transport, group=gbuf, done=0)
         return self._pipe
 
     @staticmethod

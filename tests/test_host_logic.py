@@ -194,6 +194,92 @@ def test_fused_launch_predicate_and_exchange_validation_host_side():
     assert lib.hsr_pipeline_status(None, None, ctypes.byref(code)) == 1
 
 
+def test_step_plan_and_pipeline_creation_checks_host_side():
+    """hsr_step_plan_create makes no HIP call, and the pipeline create functions check every argument before their first one:
+    plans over fake device pointers (none is dereferenced) and the pipelines over them are refused with their messages."""
+    lib = nat.load()
+    w, good = onp.synthetic_wavelengths()
+    t12 = eng.build_srf_table(w, onp.synthetic_srf(), good)
+    nb = t12.nb
+    k0 = (ctypes.c_int32 * nb)(*[int(v) for v in t12.k0])
+    kl = (ctypes.c_int32 * nb)(*[int(v) for v in t12.klen])
+    fake = iter(range(0x7f0000000000, 0x7f0100000000, 1 << 20))          # distinct, 16-byte aligned, never dereferenced
+
+    def desc(reserved_cus=0, **kw):
+        d = nat.StepDesc()
+        d.cube_dtype, d.B, d.npix, d.nb, d.deg, d.min_count = 0, 285, 64 * 64, nb, 3, 5
+        d.k0, d.klen = ctypes.cast(k0, ctypes.POINTER(ctypes.c_int32)), ctypes.cast(kl, ctypes.POINTER(ctypes.c_int32))
+        d.out_bs, d.out_ps, d.matched_bs, d.matched_ps, d.real_bs, d.real_ps = 1, 12, 1, 12, 1, 12
+        d.opts = nat.SrfOptions(0, reserved_cus, 0, 0)
+        for f in ("wn_dev", "pseudo_dev", "partials_dev", "moments_dev", "coeffs_dev", "matched_dev"):
+            setattr(d, f, next(fake))
+        for f, v in kw.items():
+            setattr(d, f, v)
+        return d
+
+    made = []
+
+    def plan(d):
+        h = ctypes.c_void_p()
+        assert lib.hsr_step_plan_create(ctypes.byref(d), ctypes.byref(h)) == 0, lib.hsr_last_error()
+        made.append(h)
+        return h
+
+    def refused(rc, code, msg):
+        assert rc == code and msg in lib.hsr_last_error(), (rc, lib.hsr_last_error())
+
+    h = ctypes.c_void_p()
+    refused(lib.hsr_step_plan_create(None, ctypes.byref(h)), 1, b"NULL argument")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(nb=0)), ctypes.byref(h)), 1, b"nb=0 outside")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(k0=None)), ctypes.byref(h)), 1, b"NULL band tables")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(deg=5)), ctypes.byref(h)), 1, b"deg=5 outside")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(cube_dtype=1)), ctypes.byref(h)), 1, b"cube_dtype 1")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(coeffs_dev=None)), ctypes.byref(h)), 1, b"NULL device pointer")
+    refused(lib.hsr_step_plan_create(ctypes.byref(desc(npix=0)), ctypes.byref(h)), 1, b"npix < 1")
+    try:
+        ds = [desc() for _ in range(4)]
+        p = [plan(d) for d in ds]
+        assert lib.hsr_step_plan_slots(p[0]) == 0 and lib.hsr_step_plan_slots(None) == -1
+        side = ctypes.c_void_p(0x1000)                 # a stream handle is only compared with NULL before the first HIP call
+        for field in ("partials_dev", "moments_dev", "coeffs_dev", "pseudo_dev", "matched_dev"):
+            shared = plan(desc(**{field: getattr(ds[1], field)}))
+            refused(lib.hsr_pipeline_create_fused(p[0], p[1], shared, side, 0, ctypes.byref(h)), 1, b"plans 1 and 2 share a work buffer")
+            four = (ctypes.c_void_p * 4)(p[0], p[1], p[2], shared)
+            refused(lib.hsr_pipeline_create_group(four, 4, 2, side, side, side, side, ctypes.byref(h)), 1, b"plans 1 and 3 share a work buffer")
+        refused(lib.hsr_pipeline_create_fused(p[0], p[1], p[1], side, 0, ctypes.byref(h)), 1, b"distinct plans needed")
+        refused(lib.hsr_pipeline_create_fused(p[0], None, p[2], side, 0, ctypes.byref(h)), 1, b"NULL plan")
+        refused(lib.hsr_pipeline_create_fused(p[0], p[1], p[2], side, 1, ctypes.byref(h)), 2, b"no exchange in the three-slot form")
+        refused(lib.hsr_pipeline_create_fused(p[0], p[1], p[2], None, 0, ctypes.byref(h)), 1, b"side stream must be a real stream")
+        refused(lib.hsr_pipeline_create_fused(p[0], p[1], p[2], side, 0, None), 1, b"NULL argument")
+        # geometry: every plan like the first, 16-byte aligned pixel-major rows of 4 / 8 / 12 / 16 floats
+        for kw in (dict(npix=64 * 63), dict(B=284), dict(deg=2), dict(out_ps=16, matched_ps=16), dict(pseudo_dev=next(fake) + 4),
+                   dict(matched_ps=16), dict(out_bs=2), dict(cube_dtype=2), dict(reserved_cus=8)):
+            odd = plan(desc(**kw))
+            refused(lib.hsr_pipeline_create_fused(p[0], p[1], odd, side, 0, ctypes.byref(h)), 2, b"the same geometry")
+            four = (ctypes.c_void_p * 4)(p[0], p[1], p[2], odd)
+            refused(lib.hsr_pipeline_create_group(four, 4, 2, side, side, side, side, ctypes.byref(h)), 2, b"the same geometry")
+        # group sizes: group_tiles + 2 plans, 2 .. 64 tiles
+        four = (ctypes.c_void_p * 4)(*p)
+        for nslots, tiles in ((4, 1), (3, 1), (2, 0), (4, 3), (5, 2), (67, 65)):
+            refused(lib.hsr_pipeline_create_group(four, nslots, tiles, side, side, side, side, ctypes.byref(h)), 1, b"groups of 2 .. 64 tiles")
+        refused(lib.hsr_pipeline_create_group(four, 4, 2, side, None, side, side, ctypes.byref(h)), 1, b"NULL argument")
+        refused(lib.hsr_pipeline_create_group(four, 4, 2, side, side, side, None, ctypes.byref(h)), 1, b"side stream must be a real stream")
+        # exchange: CUs kept free for the side stream, then the same plan checks as the other fused forms
+        x = nat.Exchange()
+        x.mode, x.host_sum = nat.HSR_SYNC_ALLREDUCE, nat.HOST_SUM_FN(lambda user, values, count: 0)
+        refused(lib.hsr_pipeline_create_exchange(four, side, ctypes.byref(x), ctypes.byref(h)), 1, b"at least 8 CUs free")
+        ds8 = [desc(reserved_cus=8) for _ in range(3)]
+        p8 = [plan(d) for d in ds8] + [plan(desc(reserved_cus=8, coeffs_dev=ds8[0].coeffs_dev))]
+        refused(lib.hsr_pipeline_create_exchange((ctypes.c_void_p * 4)(*p8), side, ctypes.byref(x), ctypes.byref(h)), 1,
+                b"plans 0 and 3 share a work buffer")
+        refused(lib.hsr_pipeline_create_exchange((ctypes.c_void_p * 4)(*p8[:3], p8[0]), side, ctypes.byref(x), ctypes.byref(h)), 1,
+                b"distinct plans needed")
+        assert not h.value                             # nothing was created
+    finally:
+        for m in made:
+            lib.hsr_step_plan_destroy(m)
+
+
 def test_polyfeat_table_matches_sklearn_order():
     lib = nat.load()
     assert lib.hsr_polyfeat_count(10, 3) == 285 and lib.hsr_polyfeat_count(10, 2) == 65
