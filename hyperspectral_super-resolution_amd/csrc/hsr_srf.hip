@@ -141,6 +141,7 @@ __device__ __forceinline__ unsigned long long phase_stamp() {
 #define HSR_STAMP(var)
 #endif
 
+constexpr int kGroupPixels = 64;                    // pixels per LDS group (lane = pixel), the only geometry
 constexpr int kGroups = 8;                          // band groups per workgroup (band = group + 8 * slot)
 constexpr int kBandSlots = HSR_MAX_BANDS / kGroups;  // 2 bands per thread
 constexpr int kTapChunk = 16;                       // taps per unrolled dot-product chunk
@@ -157,14 +158,12 @@ constexpr int kScanBatchF32 = HSR_F32_SCAN_BATCH;   // ... in the float32 sweep
 //  groups kept the band parameters in VGPRs; P = 64: 0.2133 ms on the same box.)
 // The geometry comes with every call (hsr_srf_options); the library keeps no tuning state.
 struct SrfTuning {
-  int tile_pixels;    // 64
   int reserved_cus;   // CUs left without a persistent K1 workgroup (side-stream kernels of the previous tile's fit)
   bool u16_ring;      // uint16 cubes: double-buffered kernel where it fits
   bool u16_fast;      // uint16 cubes: fast arithmetic (decode scale folded into the weights, packed fma)
 };
 
 static int srf_tuning(const hsr_srf_options* o, SrfTuning* t, const char* who) {
-  t->tile_pixels = 64;
   t->reserved_cus = 0;
   t->u16_ring = true;
   t->u16_fast = false;
@@ -175,7 +174,6 @@ static int srf_tuning(const hsr_srf_options* o, SrfTuning* t, const char* who) {
   HSR_REQUIRE(o->reserved_cus >= 0 && o->reserved_cus <= 128, HSR_ERR_INVALID, "%s: options.reserved_cus=%d outside [0,128]",
               who, o->reserved_cus);
   HSR_REQUIRE((o->flags & ~HSR_SRF_U16_FAST) == 0, HSR_ERR_INVALID, "%s: options.flags has unknown bits (0x%x)", who, o->flags);
-  if (o->tile_pixels) t->tile_pixels = o->tile_pixels;
   t->reserved_cus = o->reserved_cus;
   t->u16_ring = o->u16_single_buffer == 0;
   t->u16_fast = (o->flags & HSR_SRF_U16_FAST) != 0;
@@ -183,10 +181,10 @@ static int srf_tuning(const hsr_srf_options* o, SrfTuning* t, const char* who) {
 }
 
 // Partial slots of a tile of npix pixels: min(pixel groups, resident workgroups).
-static int srf_slots(int64_t npix, int P, int reserved_cus) {
-  int64_t groups = (npix + P - 1) / P;
+static int srf_slots(int64_t npix, int reserved_cus) {
+  int64_t groups = (npix + kGroupPixels - 1) / kGroupPixels;
   if (groups < 1) groups = 1;
-  const int64_t cap = (int64_t)(256 - reserved_cus) * (P == 64 ? 2 : 4);  // CUs x resident workgroups
+  const int64_t cap = (int64_t)(256 - reserved_cus) * 2;  // CUs x resident workgroups
   // Up to 64 groups: a slot per group.  65 .. 512 groups (tiles up to ~180 x 180, whose stand-alone step is launch-bound
   // anyway): four groups per slot, at least 64 slots - so that a batch of small tiles does not flush and re-read one
   // 1.3 KB partial per 64-pixel group (a 100 x 100 tile: 64 slots of 2-3 groups instead of 157 of one; batched K1+K2 of
@@ -1578,149 +1576,131 @@ __global__ __launch_bounds__(512, 4) void srf_u16_ring_kernel(const SrfArgs a) {
     if (a.lazy_partials) lazy_fit<DEG, T>(a, smem, t);   // the previous tile's fit as tail work (fused pipeline)
 }
 
-template <typename K>
-static void ensure_dynamic_lds(K kern, size_t lds, size_t* configured) {
-  if (lds > *configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    *configured = lds;
-  }
+// ---- K1 launches: one table of kernel instances, one selection, one launcher ----------------------------------------
+// Every K1 kernel instance, per degree: exactly the ones a launch can select (tools/pmc_summary.py and tools/make_profiles.py
+// match on their names).  Entry kSrfKernels[deg].k[variant]; the comment of each variant says what the offset adds.
+typedef void (*SrfKernel)(SrfArgs);
+enum SrfVariant {
+  kF32Global = 0,             // srf_kernel<D, false, false, 64, false, false>: weights read from global memory
+  kF32 = 1,                   // + 2 FAST + OUTV: srf_kernel<D, FAST, true, 64, OUTV, false>
+  kF32Apply = 5,              // + FAST: srf_kernel<D, FAST, true, 64, true, false, true>      (D > 0)
+  kF32Batch = 7,              // + FAST: srf_kernel<D, FAST, true, 64, true, true>
+  kU16 = 9,                   // + 2 FAST + OUTV: srf_u16_kernel<D, FAST, OUTV, false>
+  kU16Batch = 13,             // + FAST: srf_u16_kernel<D, FAST, true, true>
+  kRing = 15,                 // + OUTV + FASTU (FASTU only with OUTV): srf_u16_ring_kernel<D, OUTV, false, FASTU>
+  kRingApply = 18,            // + FASTU: srf_u16_ring_kernel<D, true, false, FASTU, true>      (D > 0)
+  kRingBatch = 20,            // + FASTU: srf_u16_ring_kernel<D, true, true, FASTU>
+  kSrfVariants = 22
+};
+struct SrfKernelRow {
+  SrfKernel k[kSrfVariants];
+};
+template <int D, bool FAST>
+constexpr SrfKernel srf_apply_kernel() {
+  if constexpr (D > 0) return srf_kernel<D, FAST, true, 64, true, false, true>;
+  return nullptr;
 }
-
-template <int DEG, bool OUTV, bool BATCH, bool FASTU, bool APPLY = false>
-static int launch_srf_u16_ring(const SrfArgs& a, int grid, hipStream_t stream) {
-  const size_t lds = (size_t)2 * 64 * a.B * 2 + 128 * sizeof(uint32_t) + (size_t)a.wtaps * 4 + (OUTV ? (size_t)64 * stage_row(a.nb, (int)a.out_ps) * 4 : 0);
-  auto kern = srf_u16_ring_kernel<DEG, OUTV, BATCH, FASTU, APPLY>;
-#ifdef HSR_PHASE_STAMPS
-  const_cast<SrfArgs&>(a).stamps = g_stamp_buffer;
-#endif
-  static thread_local size_t configured = 0;
-  ensure_dynamic_lds(kern, lds, &configured);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a);
-  HSR_LAUNCH_CHECK("srf_u16_ring_kernel");
-  return HSR_OK;
+template <int D, bool FASTU>
+constexpr SrfKernel srf_ring_apply_kernel() {
+  if constexpr (D > 0) return srf_u16_ring_kernel<D, true, false, FASTU, true>;
+  return nullptr;
 }
-
-template <int DEG, bool FAST, bool OUTV, bool BATCH>
-static int launch_srf_u16(const SrfArgs& a, int grid, hipStream_t stream) {
-  const size_t lds = (size_t)64 * a.B * 2 + (64 + (BATCH ? 16 : 0)) * sizeof(uint32_t) + (size_t)a.wtaps * 4 +
-                     (OUTV ? (size_t)64 * stage_row(a.nb, (int)a.out_ps) * 4 : 0) + (DEG > 0 ? target_stage_bytes(a.nb) : 0);
-  auto kern = srf_u16_kernel<DEG, FAST, OUTV, BATCH>;
-  static thread_local size_t configured = 0;
-  ensure_dynamic_lds(kern, lds, &configured);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, a);
-  HSR_LAUNCH_CHECK("srf_u16_kernel");
-  return HSR_OK;
+template <int D>
+constexpr SrfKernelRow srf_kernel_row() {
+  return {{srf_kernel<D, false, false, 64, false, false>,
+           srf_kernel<D, false, true, 64, false, false>, srf_kernel<D, false, true, 64, true, false>,
+           srf_kernel<D, true, true, 64, false, false>, srf_kernel<D, true, true, 64, true, false>,
+           srf_apply_kernel<D, false>(), srf_apply_kernel<D, true>(),
+           srf_kernel<D, false, true, 64, true, true>, srf_kernel<D, true, true, 64, true, true>,
+           srf_u16_kernel<D, false, false, false>, srf_u16_kernel<D, false, true, false>,
+           srf_u16_kernel<D, true, false, false>, srf_u16_kernel<D, true, true, false>,
+           srf_u16_kernel<D, false, true, true>, srf_u16_kernel<D, true, true, true>,
+           srf_u16_ring_kernel<D, false, false, false>, srf_u16_ring_kernel<D, true, false, false>,
+           srf_u16_ring_kernel<D, true, false, true>,
+           srf_ring_apply_kernel<D, false>(), srf_ring_apply_kernel<D, true>(),
+           srf_u16_ring_kernel<D, true, true, false>, srf_u16_ring_kernel<D, true, true, true>}};
 }
+static const SrfKernelRow kSrfKernels[HSR_MAX_DEG + 1] = {srf_kernel_row<0>(), srf_kernel_row<1>(), srf_kernel_row<2>(),
+                                                          srf_kernel_row<3>(), srf_kernel_row<4>()};
+static_assert(HSR_MAX_DEG == 4, "one kernel row per degree");
 
-static bool out_rows_vectorised(const SrfArgs& a, const float* out) {
-  return a.out_bs == 1 && (a.out_ps & 3) == 0 && a.out_ps <= HSR_MAX_BANDS && (((uintptr_t)out) & 15) == 0;
-}
+// A selected K1 launch: kernel kSrfKernels[deg].k[variant], grid x 512 threads, lds bytes of dynamic LDS.
+struct SrfLaunch {
+  int deg, variant, grid;
+  size_t lds;
+  const char* what;   // "<kernel> launch", for the error text
+};
 
-// two group buffers must fit twice per CU next to the weights and the output slab: B <= ~300 spectral samples
-static bool u16_ring_fits(const SrfArgs& a, bool outv) {
-  const size_t ring_lds = (size_t)2 * 64 * a.B * 2 + 512 + (size_t)a.wtaps * 4 + (outv ? (size_t)64 * stage_row(a.nb, (int)a.out_ps) * 4 : 0);
-  return ring_lds <= 80 * 1024;
-}
-
-template <int DEG>
-static int dispatch_u16_deg(const SrfArgs& a, bool fast, bool ring, int grid, hipStream_t s) {
-  const bool outv = out_rows_vectorised(a, a.one.pseudo_dev);
-  if (a.apply_x != nullptr || a.lazy_partials != nullptr) {   // the fused pipeline's launch: only the ring kernel carries it
-    if constexpr (DEG > 0) {
-      if (!(fast && ring && outv && a.wtaps > 0 && u16_ring_fits(a, true) && 2 * 64 * a.B * 2 >= 12 * 1024)) {
-        set_error("hsr_srf_integrate_moments_u16_apply: this launch cannot carry an apply job (needs the ring kernel: 16-byte aligned "
-                  "cube, weights in LDS, pixel-major rows, 48 <= B <= ~300)");
-        return HSR_ERR_UNSUPPORTED;
-      }
-      return a.u16_fast ? launch_srf_u16_ring<DEG, true, false, true, true>(a, grid, s)
-                        : launch_srf_u16_ring<DEG, true, false, false, true>(a, grid, s);
-    }
-  }
-  if (fast && ring && u16_ring_fits(a, outv)) {
-    if (outv && a.u16_fast && a.wtaps > 0) return launch_srf_u16_ring<DEG, true, false, true>(a, grid, s);
-    return outv ? launch_srf_u16_ring<DEG, true, false, false>(a, grid, s) : launch_srf_u16_ring<DEG, false, false, false>(a, grid, s);
-  }
-  if (outv) return fast ? launch_srf_u16<DEG, true, true, false>(a, grid, s) : launch_srf_u16<DEG, false, true, false>(a, grid, s);
-  return fast ? launch_srf_u16<DEG, true, false, false>(a, grid, s) : launch_srf_u16<DEG, false, false, false>(a, grid, s);
-}
-
-static int dispatch_u16(const SrfArgs& a, int deg, bool fast, bool ring, int grid, hipStream_t s) {
-  switch (deg) {
-    case 0: return dispatch_u16_deg<0>(a, fast, ring, grid, s);
-    case 1: return dispatch_u16_deg<1>(a, fast, ring, grid, s);
-    case 2: return dispatch_u16_deg<2>(a, fast, ring, grid, s);
-    case 3: return dispatch_u16_deg<3>(a, fast, ring, grid, s);
-    case 4: return dispatch_u16_deg<4>(a, fast, ring, grid, s);
-  }
-  set_error("hsr_srf_integrate_moments_u16: deg=%d outside [1,%d]", deg, HSR_MAX_DEG);
-  return HSR_ERR_UNSUPPORTED;
-}
-
-template <int DEG, bool FAST, bool WLDS, int P, bool OUTV, bool BATCH, bool APPLY = false>
-static int launch_srf(const SrfArgs& a, int grid, hipStream_t stream) {
-  const size_t lds = (size_t)P * a.ldsB * 4 + (64 + (BATCH ? 16 : 0)) * sizeof(uint32_t) + (WLDS ? (size_t)a.wtaps * 4 : 0) +
-                     (OUTV ? (size_t)P * stage_row(a.nb, (int)a.out_ps) * 4 : 0) + (DEG > 0 ? target_stage_bytes(a.nb) : 0);
-  auto kern = srf_kernel<DEG, FAST, WLDS, P, OUTV, BATCH, APPLY>;
-  static thread_local size_t configured = 0;
-  ensure_dynamic_lds(kern, lds, &configured);
-#ifdef HSR_PHASE_STAMPS
-  const_cast<SrfArgs&>(a).stamps = g_stamp_buffer;
-  const_cast<SrfArgs&>(a).stamps2 = g_stamp_buffer2;
-  const_cast<SrfArgs&>(a).stamps3 = g_stamp_buffer3;
-#endif
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(8 * P), lds, stream, a);
-  HSR_LAUNCH_CHECK("srf_kernel");
-  return HSR_OK;
-}
-
-template <int DEG, int P>
-static int dispatch_fast(const SrfArgs& a, bool fast, int grid, hipStream_t s) {
-  // pixel-major output with a 16-byte friendly row: stage the slab in LDS and flush it vectorised
-  const bool outv = out_rows_vectorised(a, a.one.pseudo_dev);
-  if (a.wtaps == 0) return launch_srf<DEG, false, false, 64, false, false>(a, grid, s);  // rare fallback: one generic kernel
-  if (a.apply_x != nullptr || a.lazy_partials != nullptr) {   // srf_common has checked that this launch can carry it (outv, weights in LDS, DEG > 0)
-    if constexpr (DEG > 0)
-      return fast ? launch_srf<DEG, true, true, P, true, false, true>(a, grid, s) : launch_srf<DEG, false, true, P, true, false, true>(a, grid, s);
-  }
-  if (outv) return fast ? launch_srf<DEG, true, true, P, true, false>(a, grid, s) : launch_srf<DEG, false, true, P, true, false>(a, grid, s);
-  return fast ? launch_srf<DEG, true, true, P, false, false>(a, grid, s) : launch_srf<DEG, false, true, P, false, false>(a, grid, s);
-}
-
-template <int P>
-static int dispatch_deg(const SrfArgs& a, int deg, bool fast, int grid, hipStream_t s) {
-  switch (deg) {
-    case 0: return dispatch_fast<0, P>(a, fast, grid, s);
-    case 1: return dispatch_fast<1, P>(a, fast, grid, s);
-    case 2: return dispatch_fast<2, P>(a, fast, grid, s);
-    case 3: return dispatch_fast<3, P>(a, fast, grid, s);
-    case 4: return dispatch_fast<4, P>(a, fast, grid, s);
-  }
-  set_error("hsr_srf_integrate_moments: deg=%d outside [1,%d]", deg, HSR_MAX_DEG);
-  return HSR_ERR_UNSUPPORTED;
-}
-
-// batch launches: pixel-major rows staged in LDS, weights in LDS, 64-pixel groups
-template <int DEG>
-static int dispatch_batch_deg(const SrfArgs& a, bool fast, bool ring, int grid, hipStream_t s) {
+// The K1 launch of validated arguments (srf_prepare_bands has run; batch: a.units / a.nunits).  The only place that knows
+// which kernel a launch runs and how much LDS each kernel family takes: srf_common, the batched entry and
+// hsr_srf_fused_launch_supported all ask it.  aligned: the cube (in a batch every tile's cube) is 16-byte aligned.
+// A launch that carries an apply job or a tail fit (job) needs the weights in LDS; a uint16 one also needs the ring kernel.
+static int srf_select(const SrfArgs& a, int deg, const SrfTuning& tn, bool aligned, bool batch, const char* who, SrfLaunch* L) {
+  HSR_REQUIRE(deg >= 0 && deg <= HSR_MAX_DEG, HSR_ERR_UNSUPPORTED, "%s: deg=%d outside [0,%d]", who, deg, HSR_MAX_DEG);
+  const bool job = !batch && (a.apply_x != nullptr || a.lazy_partials != nullptr);
+  HSR_REQUIRE(!job || deg >= 1, HSR_ERR_UNSUPPORTED, "%s: a launch of degree 0 cannot carry an apply job", who);
+  HSR_REQUIRE(a.wtaps > 0 || !(job || batch), HSR_ERR_UNSUPPORTED,
+              "%s: the weight taps of the %d bands (B=%d) do not fit the %d floats of LDS reserved for them; a batch or a launch "
+              "that carries an apply job needs them there", who, a.nb, a.B, kWeightCap);
+  // pixel-major output with a 16-byte friendly row: the kernel stages the slab in LDS and flushes it vectorised
+  const bool outv = batch || (a.out_bs == 1 && (a.out_ps & 3) == 0 && a.out_ps <= HSR_MAX_BANDS && ((uintptr_t)a.one.pseudo_dev & 15) == 0);
+  const size_t slab = (size_t)kGroupPixels * stage_row(a.nb, (int)a.out_ps) * 4;   // the staged rows (OUTV kernels)
+  const size_t weights = (size_t)a.wtaps * 4;
+  // single-buffer kernels: the group, flags [64] (+ the next unit's record [16] in a batch), weights, rows, fit targets
+  const size_t single = (64 + (batch ? 16 : 0)) * sizeof(uint32_t) + weights + (deg > 0 ? target_stage_bytes(a.nb) : 0);
+  L->deg = deg;
+  const int64_t cap = (int64_t)(256 - tn.reserved_cus) * 2;   // CUs x resident workgroups
+  L->grid = (int)(a.nunits < cap ? a.nunits : cap);
   if (a.u16) {
-    if (fast && ring && u16_ring_fits(a, true))
-      return a.u16_fast ? launch_srf_u16_ring<DEG, true, true, true>(a, grid, s) : launch_srf_u16_ring<DEG, true, true, false>(a, grid, s);
-    return fast ? launch_srf_u16<DEG, true, true, true>(a, grid, s) : launch_srf_u16<DEG, false, true, true>(a, grid, s);
+    // the ring kernel: two group buffers, flags [2][64], weights, rows; twice per CU: B <= ~300 spectral samples
+    const size_t ring_lds = (size_t)2 * kGroupPixels * a.B * 2 + 128 * sizeof(uint32_t) + weights + (outv ? slab : 0);
+    const bool ring = aligned && tn.u16_ring && ring_lds <= 80 * 1024;
+    HSR_REQUIRE(!job || (ring && outv && 2 * kGroupPixels * a.B * 2 >= 12 * 1024), HSR_ERR_UNSUPPORTED,
+                "%s: this launch cannot carry an apply job: uint16 tiles ride only in the double-buffered kernel (16-byte aligned cube, "
+                "u16_single_buffer = 0, pixel-major rows, 48 <= B, two %d-byte group buffers + %d taps + the %lld-float rows within "
+                "80 KB of LDS)", who, kGroupPixels * a.B * 2, a.wtaps, (long long)a.out_ps);
+    const int fastu = a.u16_fast ? 1 : 0;
+    if (ring) {
+      L->variant = job ? kRingApply + fastu : batch ? kRingBatch + fastu : kRing + (outv ? 1 + (fastu && a.wtaps > 0) : 0);
+      L->lds = ring_lds;
+      L->what = "srf_u16_ring_kernel launch";
+    } else {
+      L->variant = batch ? kU16Batch + aligned : kU16 + 2 * aligned + outv;
+      L->lds = (size_t)kGroupPixels * a.B * 2 + single + (outv ? slab : 0);
+      L->what = "srf_u16_kernel launch";
+    }
+    return HSR_OK;
   }
-  return fast ? launch_srf<DEG, true, true, 64, true, true>(a, grid, s) : launch_srf<DEG, false, true, 64, true, true>(a, grid, s);
+  const bool fast = aligned && (a.B & 1);   // odd B (ldsB == B): a group lands in LDS as one slab of 16-byte DMA
+  const bool staged = a.wtaps > 0 && (outv || job);   // the kernel's OUTV
+  if (a.wtaps == 0) L->variant = kF32Global;   // rare fallback: one generic kernel
+  else if (batch) L->variant = kF32Batch + fast;
+  else if (job) L->variant = kF32Apply + fast;
+  else L->variant = kF32 + 2 * fast + outv;
+  L->lds = (size_t)kGroupPixels * a.ldsB * 4 + single + (staged ? slab : 0);
+  L->what = "srf_kernel launch";
+  HSR_REQUIRE(!job || L->lds <= 160 * 1024, HSR_ERR_UNSUPPORTED,
+              "%s: a 64-pixel group of B=%d samples needs %zu bytes of LDS (160 KB per workgroup)", who, a.B, L->lds);
+  return HSR_OK;
 }
 
-static int dispatch_batch(const SrfArgs& a, int deg, bool fast, bool ring, int grid, hipStream_t s) {
-  switch (deg) {
-    case 0: return dispatch_batch_deg<0>(a, fast, ring, grid, s);
-    case 1: return dispatch_batch_deg<1>(a, fast, ring, grid, s);
-    case 2: return dispatch_batch_deg<2>(a, fast, ring, grid, s);
-    case 3: return dispatch_batch_deg<3>(a, fast, ring, grid, s);
-    case 4: return dispatch_batch_deg<4>(a, fast, ring, grid, s);
+// Launches what srf_select chose.  A kernel's dynamic-LDS limit is raised when its launches grow (one cache per kernel).
+static int srf_launch(SrfArgs& a, const SrfLaunch& L, hipStream_t stream) {
+  const SrfKernel kern = kSrfKernels[L.deg].k[L.variant];
+  static thread_local size_t configured[HSR_MAX_DEG + 1][kSrfVariants] = {};
+  size_t& c = configured[L.deg][L.variant];
+  if (L.lds > c) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
+    (void)hipGetLastError();
+    c = L.lds;
   }
-  set_error("hsr_srf_integrate_moments_batched: deg=%d outside [0,%d]", deg, HSR_MAX_DEG);
-  return HSR_ERR_UNSUPPORTED;
+#ifdef HSR_PHASE_STAMPS
+  a.stamps = g_stamp_buffer;
+  a.stamps2 = g_stamp_buffer2;
+  a.stamps3 = g_stamp_buffer3;
+#endif
+  hipLaunchKernelGGL(kern, dim3(L.grid), dim3(512), L.lds, stream, a);
+  return check_hip(hipGetLastError(), L.what);
 }
 
 // Band table of a launch: validated supports, LDS weight segments, band -> (group, slot) assignment.
@@ -1788,7 +1768,7 @@ static int srf_prepare_bands(SrfArgs& a, const int32_t* k0, const int32_t* klen)
 }
 
 static int srf_common(SrfArgs& a, const int32_t* k0, const int32_t* klen, int32_t deg, const hsr_srf_options* opts,
-                      hipStream_t stream) {
+                      hipStream_t stream, const char* who) {
   SrfTuning tn;
   int rc = srf_tuning(opts, &tn, "hsr_srf_integrate");
   if (rc != HSR_OK) return rc;
@@ -1802,19 +1782,15 @@ static int srf_common(SrfArgs& a, const int32_t* k0, const int32_t* klen, int32_
   HSR_REQUIRE(((uintptr_t)a.one.cube_dev & (a.u16 ? 1 : 3)) == 0, HSR_ERR_INVALID, "hsr_srf_integrate: cube not %d-byte aligned",
               a.u16 ? 2 : 4);
   if (a.one.npix == 0) return HSR_OK;
-  HSR_REQUIRE((a.apply_x == nullptr && a.lazy_partials == nullptr) || a.wtaps > 0, HSR_ERR_UNSUPPORTED,
-              "hsr_srf_integrate_moments_apply: the weight table does not fit LDS, this launch cannot carry an apply job");
   a.u16_fast = a.u16 && tn.u16_fast;
-  int P = a.u16 ? 64 : tn.tile_pixels;
-  if (a.wtaps == 0) P = 64;  // the generic fallback kernel exists for 64-pixel groups only
-  a.one.ngroups = (int32_t)((a.one.npix + P - 1) / P);
-  a.one.slots = srf_slots(a.one.npix, P, tn.reserved_cus);
+  a.one.ngroups = (int32_t)((a.one.npix + kGroupPixels - 1) / kGroupPixels);
+  a.one.slots = srf_slots(a.one.npix, tn.reserved_cus);
   a.one.slot = 0;
   a.nunits = a.one.slots;
-  const bool aligned = (((uintptr_t)a.one.cube_dev) & 15) == 0;
-  if (a.u16) return dispatch_u16(a, deg, aligned, tn.u16_ring, a.one.slots, stream);
-  const bool fast = (a.B & 1) && aligned;
-  return dispatch_deg<64>(a, deg, fast, a.one.slots, stream);
+  SrfLaunch L;
+  rc = srf_select(a, deg, tn, (((uintptr_t)a.one.cube_dev) & 15) == 0, false, who, &L);
+  if (rc != HSR_OK) return rc;
+  return srf_launch(a, L, stream);
 }
 
 }  // namespace hsr
@@ -1822,13 +1798,13 @@ static int srf_common(SrfArgs& a, const int32_t* k0, const int32_t* klen, int32_
 extern "C" int hsr_partial_slots(int64_t npix, const hsr_srf_options* opts) {
   hsr::SrfTuning tn;
   if (hsr::srf_tuning(opts, &tn, "hsr_partial_slots") != HSR_OK) return -1;
-  return hsr::srf_slots(npix, tn.tile_pixels, tn.reserved_cus);
+  return hsr::srf_slots(npix, tn.reserved_cus);
 }
 
-// Can a K1 launch of this geometry carry an apply job / a tail fit (hsr_srf_integrate_moments[_u16]_apply)?  The conditions of
-// dispatch_fast / dispatch_u16_deg and srf_common in one place, without a launch, so that hsr_pipeline_create_fused /
-// _exchange fail at creation - where the caller can still fall back to the two-slot pipeline - instead of at the first
-// carrying launch, with tiles in flight.  (What it cannot see is the cube pointer: uint16 cubes must be 16-byte aligned.)
+// Can a K1 launch of this geometry carry an apply job / a tail fit (hsr_srf_integrate_moments[_u16]_apply)?  Asks srf_select
+// with a placeholder job, without a launch, so that hsr_pipeline_create_fused / _exchange / _group fail at creation - where the
+// caller can still fall back to the two-slot pipeline - instead of at the first carrying launch, with tiles in flight.  (What it
+// cannot see is the cube pointer: it assumes a 16-byte aligned cube, which uint16 tiles need.)
 extern "C" int hsr_srf_fused_launch_supported(int32_t cube_dtype, int32_t B, int32_t nb, const int32_t* k0, const int32_t* klen,
                                               int64_t out_ps, int32_t deg, const hsr_srf_options* opts) {
   const char* who = "hsr_srf_fused_launch_supported";
@@ -1839,26 +1815,20 @@ extern "C" int hsr_srf_fused_launch_supported(int32_t cube_dtype, int32_t B, int
   hsr::SrfTuning tn;
   int rc = hsr::srf_tuning(opts, &tn, who);
   if (rc != HSR_OK) return rc;
+  alignas(16) static float placeholder[4];   // never touched: srf_prepare_bands and srf_select only test the pointers
   hsr::SrfArgs a{};
-  static const float dummy = 0.0f;
-  a.wn = &dummy;                   // srf_prepare_bands only tests it
+  a.wn = placeholder;
   a.B = B;
   a.nb = nb;
+  a.u16 = cube_dtype == 2;
   a.out_bs = 1;
   a.out_ps = out_ps;
+  a.one.pseudo_dev = placeholder;   // 16-byte aligned rows
+  a.apply_x = placeholder;
   rc = hsr::srf_prepare_bands(a, k0, klen);
   if (rc != HSR_OK) return rc;
-  HSR_REQUIRE(a.wtaps > 0, HSR_ERR_UNSUPPORTED, "%s: the weight taps of the %d bands do not fit the %d floats of LDS reserved for them",
-              who, nb, hsr::kWeightCap);
-  if (cube_dtype == 2) {
-    HSR_REQUIRE(tn.u16_ring && hsr::u16_ring_fits(a, true) && 2 * 64 * B * 2 >= 12 * 1024, HSR_ERR_UNSUPPORTED,
-                "%s: uint16 tiles ride only in the double-buffered kernel (u16_single_buffer = 0, 48 <= B, two %d-byte group buffers + "
-                "%d taps + the %lld-float rows within 80 KB of LDS)", who, 64 * B * 2, a.wtaps, (long long)out_ps);
-  } else {
-    const size_t lds = (size_t)64 * a.ldsB * 4 + 64 * sizeof(uint32_t) + (size_t)a.wtaps * 4 + (size_t)64 * hsr::stage_row(nb, (int)out_ps) * 4 + hsr::target_stage_bytes(nb);
-    HSR_REQUIRE(lds <= 160 * 1024, HSR_ERR_UNSUPPORTED, "%s: a 64-pixel group of B=%d samples needs %zu bytes of LDS (160 KB per workgroup)", who, B, lds);
-  }
-  return HSR_OK;
+  hsr::SrfLaunch L;
+  return hsr::srf_select(a, deg, tn, true, false, who, &L);
 }
 
 extern "C" int hsr_srf_integrate(const float* cube_dev, int64_t npix, int32_t B, const float* wn_dev,
@@ -1873,7 +1843,7 @@ extern "C" int hsr_srf_integrate(const float* cube_dev, int64_t npix, int32_t B,
   a.nb = nb;
   a.out_bs = out_bs;
   a.out_ps = out_ps;
-  return hsr::srf_common(a, k0, klen, 0, opts, (hipStream_t)stream);
+  return hsr::srf_common(a, k0, klen, 0, opts, (hipStream_t)stream, "hsr_srf_integrate");
 }
 
 // K1+K2 entry shared by the float32 / uint16 and the plain / fused-fit forms.
@@ -1965,7 +1935,7 @@ static int srf_moments_entry(const char* who, const void* cube_dev, bool u16, fl
     }
     a.sync_error = job->sync_error_dev;
   }
-  int rc = hsr::srf_common(a, k0, klen, deg, opts, (hipStream_t)stream);
+  int rc = hsr::srf_common(a, k0, klen, deg, opts, (hipStream_t)stream, who);
   if (rc == HSR_OK && slots_out) *slots_out = a.one.slots;
   return rc;
 }
@@ -2021,7 +1991,7 @@ extern "C" int hsr_srf_integrate_u16(const uint16_t* cube_dev, int64_t npix, int
   a.nb = nb;
   a.out_bs = out_bs;
   a.out_ps = out_ps;
-  return hsr::srf_common(a, k0, klen, 0, opts, (hipStream_t)stream);
+  return hsr::srf_common(a, k0, klen, 0, opts, (hipStream_t)stream, "hsr_srf_integrate_u16");
 }
 
 extern "C" int hsr_srf_integrate_moments_u16(const uint16_t* cube_dev, int64_t npix, int32_t B, float scale,
@@ -2085,8 +2055,8 @@ extern "C" int hsr_batch_plan(hsr_batch_tile* tiles, int32_t ntiles, int32_t nb,
     HSR_REQUIRE(deg == 0 || tl.real_dev, HSR_ERR_INVALID, "hsr_batch_plan: tile %d has no real-S2 target (deg > 0)", t);
     HSR_REQUIRE((((uintptr_t)tl.pseudo_dev) & 15) == 0 && (tl.matched_dev == nullptr || (((uintptr_t)tl.matched_dev) & 15) == 0),
                 HSR_ERR_INVALID, "hsr_batch_plan: tile %d: image rows must be 16-byte aligned", t);
-    tl.ngroups = (int32_t)((tl.npix + 63) / 64);
-    tl.slots = hsr::srf_slots(tl.npix, 64, tn.reserved_cus);     // batches always use 64-pixel groups
+    tl.ngroups = (int32_t)((tl.npix + hsr::kGroupPixels - 1) / hsr::kGroupPixels);
+    tl.slots = hsr::srf_slots(tl.npix, tn.reserved_cus);
     tl.slot0 = slot0;
     slot0 += tl.slots;
     pixels += tl.npix;
@@ -2171,10 +2141,8 @@ extern "C" int hsr_srf_integrate_moments_batched(const hsr_batch_unit* units_dev
   a.min_y = min_y;
   rc = hsr::srf_prepare_bands(a, k0, klen);
   if (rc != HSR_OK) return rc;
-  HSR_REQUIRE(a.wtaps > 0, HSR_ERR_UNSUPPORTED,
-              "hsr_srf_integrate_moments_batched: the SRF supports do not fit the LDS weight area (B=%d)", B);
-  const int64_t cap = (int64_t)(256 - tn.reserved_cus) * 2;
-  const int grid = (int)(info->nunits < cap ? info->nunits : cap);
-  const bool fast = info->aligned16 && (a.u16 || (B & 1));
-  return hsr::dispatch_batch(a, deg, fast, tn.u16_ring, grid, (hipStream_t)stream);
+  hsr::SrfLaunch L;
+  rc = hsr::srf_select(a, deg, tn, info->aligned16 != 0, true, "hsr_srf_integrate_moments_batched", &L);
+  if (rc != HSR_OK) return rc;
+  return hsr::srf_launch(a, L, (hipStream_t)stream);
 }
