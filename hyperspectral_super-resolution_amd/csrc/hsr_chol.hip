@@ -815,21 +815,11 @@ extern "C" int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double*
   HSR_REQUIRE(lda >= n && nrhs >= 1 && ldb >= nrhs, HSR_ERR_INVALID, "hsr_chol_solve_f64: bad leading dimension");
   hipStream_t s = (hipStream_t)stream;
   const size_t lds_f = ((size_t)kCb + (size_t)(n - kCb)) * kCs * sizeof(double);
-  static thread_local size_t configured = 0;
-  if (lds_f > configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_f);
-    (void)hipGetLastError();
-    configured = lds_f;
-  }
-  static const bool no_res = getenv("HSR_CHOL_NO_RES") != nullptr;     // A/B switch of tools/chol_stamps
-  if (n <= kResMaxN && !no_res) {
+  static thread_local size_t configured = 0, configured_r = 0, configured_s = 0;
+  raise_lds_limit(reinterpret_cast<const void*>(chol_factor_kernel), lds_f, configured);
+  if (n <= kResMaxN) {
     const size_t lds_r = (size_t)(2 * n - kCb) * kDs * sizeof(double);   // two (D | P) buffers of n and n - 32 rows of 34 doubles
-    static thread_local size_t configured_r = 0;
-    if (lds_r > configured_r) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_factor_res_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-      (void)hipGetLastError();
-      configured_r = lds_r;
-    }
+    raise_lds_limit(reinterpret_cast<const void*>(chol_factor_res_kernel), lds_r, configured_r);
     hipLaunchKernelGGL(chol_factor_res_kernel, dim3(1), dim3(kResThreads), lds_r, s, a_dev, lda, n, info_dev, work_dev CHOL_STAMP_ARG);
   } else {
     hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), lds_f, s, a_dev, lda, n, info_dev, work_dev CHOL_STAMP_ARG);
@@ -837,12 +827,7 @@ extern "C" int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double*
   size_t lds_s = ((size_t)n + kCb) * kYs * sizeof(double);
   const int dinv_in_lds = lds_s + (size_t)n * kCs * sizeof(double) <= 160 * 1024 ? 1 : 0;
   if (dinv_in_lds) lds_s += (size_t)n * kCs * sizeof(double);
-  static thread_local size_t configured_s = 0;
-  if (lds_s > configured_s) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
-    (void)hipGetLastError();
-    configured_s = lds_s;
-  }
+  raise_lds_limit(reinterpret_cast<const void*>(chol_solve_kernel), lds_s, configured_s);
   hipLaunchKernelGGL(chol_solve_kernel, dim3((nrhs + kSw - 1) / kSw), dim3(1024), lds_s, s, a_dev, lda, n, work_dev, b_dev, ldb, nrhs, dinv_in_lds CHOL_STAMP_ARG);
   HSR_LAUNCH_CHECK("chol kernels");
   return HSR_OK;

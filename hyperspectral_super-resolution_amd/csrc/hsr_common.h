@@ -31,6 +31,15 @@ inline int check_hip(hipError_t e, const char* what) {
     if (rc_ != HSR_OK) return rc_;                               \
   } while (0)
 
+// Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
+// records, and clears the error a refused request leaves: the launch itself then reports it.
+inline void raise_lds_limit(const void* kernel, size_t bytes, size_t& configured) {
+  if (bytes <= configured) return;
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  (void)hipGetLastError();
+  configured = bytes;
+}
+
 constexpr int kWave = 64;
 
 // Number of moments for a degree.

@@ -373,15 +373,13 @@ __global__ __launch_bounds__(256) void apply_planar_kernel(const ApplyArgs a) {
 // cs + ch * n: lanes of a wave sit on Q channel groups whose rows collide in the banks - SQ_LDS_BANK_CONFLICT was
 // half of SQ_LDS_IDX_ACTIVE (profiles/r01_rocprof_summary.md) and the kernel ran at 4.3 TB/s.
 // BATCH: blockIdx.y = tile of a batch (hsr_poly_apply_batched), every tile with its own coefficients.
+// kK3U: independent 16-byte loads in flight per thread.  A/B on one box at 1024 x 1024 x 12 (tools/dbg/k3_time.py):
+// U = 4: 25.0 us, 8: 22.1, 12: 22.7, 16: 19.0 (768 workgroups = 3 per CU in one round), 20: 21.7, 24: 24.0, 32: 23.2
+constexpr int kK3U = 16;
 template <int Q, int N, bool BATCH>
 __global__ __launch_bounds__(256) void apply_rows_kernel(const ApplyArgs a, const hsr_batch_tile* __restrict__ tiles,
                                                          int use_mask) {
-#ifndef HSR_K3_U
-#define HSR_K3_U 16
-#endif
-  // independent 16-byte loads in flight per thread.  A/B on one box at 1024 x 1024 x 12 (tools/dbg/k3_time.py):
-  // U = 4: 25.0 us, 8: 22.1, 12: 22.7, 16: 19.0 (768 workgroups = 3 per CU in one round), 20: 21.7, 24: 24.0, 32: 23.2
-  constexpr int U = HSR_K3_U;
+  constexpr int U = kK3U;
   const bool has_poly = a.coeffs != nullptr;
   const bool st = a.lohi != nullptr;
   const float* x = a.x;
@@ -722,7 +720,7 @@ extern "C" int hsr_poly_apply(const float* x_dev, int64_t x_bs, int64_t x_ps, co
       // image, so a larger grid simply means fewer loads per thread: aim for 3 workgroups per CU (768) and 1 .. U loads.
       const int64_t nv4 = npix * q;
       int64_t per_thread = (nv4 + 768 * 256 - 1) / (768 * 256);
-      per_thread = per_thread < 1 ? 1 : (per_thread > HSR_K3_U ? HSR_K3_U : per_thread);
+      per_thread = per_thread < 1 ? 1 : (per_thread > kK3U ? kK3U : per_thread);
       int64_t gb = (nv4 + 256 * per_thread - 1) / (256 * per_thread);
       if (gb > 8190) gb = 2046;
       gb = (gb + 2) / 3 * 3;
@@ -794,7 +792,7 @@ extern "C" int hsr_poly_apply_batched(const hsr_batch_tile* tiles_dev, int32_t n
   const int64_t q = row >> 2;
   HSR_REQUIRE(max_npix >= 1 && max_npix * q < ((int64_t)1 << 31), HSR_ERR_UNSUPPORTED, "hsr_poly_apply_batched: max_npix=%lld", (long long)max_npix);
   ApplyArgs a{nullptr, 1, row, nullptr, coeffs_dev, nullptr, nb, deg, clip, 0, nullptr, 1, row};
-  int64_t gb = (max_npix * q + 256 * HSR_K3_U - 1) / (256 * HSR_K3_U);
+  int64_t gb = (max_npix * q + 256 * kK3U - 1) / (256 * kK3U);
   if (gb > 2046) gb = 2046;
   gb = (gb + 2) / 3 * 3;
   int rc = launch_apply_rows<true>(a, tiles_dev, use_mask, (int)q, deg, dim3((unsigned)gb, (unsigned)ntiles), (hipStream_t)stream);

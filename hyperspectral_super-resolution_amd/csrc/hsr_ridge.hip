@@ -215,24 +215,15 @@ __global__ __launch_bounds__(256) void gram_f64_kernel(const double* __restrict_
 //    instructions (4 240 -> 3 750 shader cycles per batch of 3 x 18 MFMAs = 3 456).
 //  * the diagonal blocks of the symmetric part are a third kind (gram_diag_block below): upper tiles only.
 //  What is left: the shader clock runs at 2.10 GHz under this kernel (s_memtime against s_memrealtime), not 2.4.
-#ifndef HSR_GRAM_BUFS
-#define HSR_GRAM_BUFS 4
-#endif
-#ifndef HSR_GRAM_GROUPS
-#define HSR_GRAM_GROUPS 3
-#endif
-#ifndef HSR_GRAM_WGS
-#define HSR_GRAM_WGS 1
-#endif
 constexpr int kGpCols = 96;          // panel width = 6 MFMA tiles
 constexpr int kGpNarrow = 32;        // widest last strip that becomes a narrow block
 constexpr int kGpRows = 8;           // rows per batch = 2 k-steps
-constexpr int kGpBufs = HSR_GRAM_BUFS;   // panel ring: batch b lives in slot b % kGpBufs, the DMA runs kGpBufs - 1 batches ahead
+constexpr int kGpBufs = 4;           // panel ring: batch b lives in slot b % kGpBufs, the DMA runs kGpBufs - 1 batches ahead
 constexpr int kGpAhead = kGpBufs - 1;
 constexpr int kGpStride = 208;       // doubles per LDS row = [A 96 | B 96 | 16 spare]: 1664 B = 128 B mod 256 B -> kk rows 0/1 and 2/3 on disjoint banks
 constexpr int kGpDmaPerWave = 2 * kGpRows / 4;   // panel rows each wave moves per batch (waves 0, 1: A; waves 2, 3: B)
-constexpr int kGramGroups = HSR_GRAM_GROUPS;     // 4-wave groups per workgroup
-constexpr int kGramWgs = HSR_GRAM_WGS;           // workgroups per CU
+constexpr int kGramGroups = 3;                   // 4-wave groups per workgroup
+constexpr int kGramWgs = 1;                      // workgroups per CU
 constexpr int kGramSlots = 256 * kGramWgs;       // resident workgroups of this kernel on the chip
 constexpr int kGramThreads = 256 * kGramGroups;
 constexpr int kGpRingDoubles = kGpBufs * kGpRows * kGpStride;       // one group's panel ring (4 slots: 53 248 B; three groups: 159 744 B)
@@ -639,7 +630,7 @@ __device__ __forceinline__ void gram_diag_block(const GramCore a, double* pan_ba
 // Workgroup id -> (block, chunk): consecutive ids are the blocks of one chunk of rows, and the eight XCDs take
 // contiguous runs of ids (hardware deals workgroup w to XCD w % 8), so that the workgroups that read the same rows
 // of A sit behind the same L2.
-__global__ __launch_bounds__(kGramThreads, HSR_GRAM_WGS) void gram_f64_lds_kernel(const GramLdsArgs args) {
+__global__ __launch_bounds__(kGramThreads, kGramWgs) void gram_f64_lds_kernel(const GramLdsArgs args) {
   extern __shared__ __attribute__((aligned(16))) double pan[];   // kGramLdsDoubles
   const GramCore a = args.c;
   const int id = (int)(blockIdx.x % 8) * a.per_xcd + (int)(blockIdx.x / 8);
@@ -823,12 +814,14 @@ __global__ __launch_bounds__(kPredThreads) void predict_kernel(const PredArgs a)
 // predict, specialised for the notebook's shape (10 inputs, degree 3 -> 285 monomials): MFMA-bound
 // ------------------------------------------------------------------------------------------------
 // The generic kernel above stages a 64 x 286 feature tile in LDS (73 KB -> one workgroup per CU) and fetches
-// W from global memory per MFMA: 10-12 % of the f32 matrix peak.  Here every lane keeps the 10 standardised
-// inputs of its pixel in registers and the monomials are generated by fully unrolled code from a
-// compile-time table (2-5 VALU ops per MFMA, hidden under the 64-cycle v_mfma_f32_32x32x2_f32), W lives in
-// LDS (whole when it fits, otherwise double-buffered 32-row chunks), and a workgroup covers 128 pixels with
-// all four waves busy.  Targets sit on the M axis so each accumulator register is 32 consecutive pixels of
-// one target: coalesced band-major stores.
+// W from global memory per MFMA: 10-12 % of the f32 matrix peak.  In the kernels below every lane keeps the 10
+// standardised inputs of its pixel in registers, the monomials are generated by fully unrolled code from
+// compile-time tables, and W is staged in LDS once per workgroup for the whole launch:
+//   T <= 16            predict103_x16_kernel       (16-target tiles, v_mfma_f32_16x16x4_f32)
+//   17 <= T <= 32      predict103_slice_kernel<1>  (one 32-target slice)
+//   33 <= T <= 512     predict103_slice_kernel<2 / 3>  (slices of 64 or 96 targets, blockIdx.y)
+// Larger T take the generic kernel.  Targets sit on the M axis so each accumulator register holds consecutive
+// pixels of one target: coalesced band-major stores.
 struct Tab103 {
   uint8_t v[286][3];
 };
@@ -851,41 +844,6 @@ constexpr Tab103 make_tab103() {
   return t;
 }
 constexpr Tab103 kTab103 = make_tab103();
-constexpr int kSteps103 = 143;      // 286 / 2
-constexpr int kChunkRows = 32;      // W rows per LDS chunk (16 MFMA steps)
-
-template <int S0, int S1, int TT>
-__device__ __forceinline__ void mfma_steps103(const float (&z)[11], int kh, const float* __restrict__ wl, int ldwl,
-                                              int row0, int j, f32x16 (&acc)[TT]) {
-  // Hand-pipelined: the W operands of step s+1 are read from LDS before the MFMAs of step s, and a
-  // scheduling barrier per step stops hipcc from hoisting all 286 monomial products ahead of the MFMA
-  // chain (which cost 230-256 VGPRs and spills).  Per step: 2-4 v_mul + 1 v_cndmask + TT ds_read_b32 under
-  // TT x 64 cycles of MFMA.
-  float wc[TT], wn[TT];
-  {
-    const float* wr = wl + (2 * S0 + kh - row0) * ldwl + j;   // A[i = target][k] = W[k][target]
-#pragma unroll
-    for (int q = 0; q < TT; ++q) wc[q] = wr[q * 32];
-  }
-#pragma unroll
-  for (int s = S0; s < S1; ++s) {
-    const float p0 = z[kTab103.v[2 * s][0]] * z[kTab103.v[2 * s][1]] * z[kTab103.v[2 * s][2]];
-    const float p1 = z[kTab103.v[2 * s + 1][0]] * z[kTab103.v[2 * s + 1][1]] * z[kTab103.v[2 * s + 1][2]];
-    const float bv = kh ? p1 : p0;                            // B[k = 2s + kh][pixel j]
-    if (s + 1 < S1) {
-      const float* wr = wl + (2 * (s + 1) + kh - row0) * ldwl + j;
-#pragma unroll
-      for (int q = 0; q < TT; ++q) wn[q] = wr[q * 32];
-    }
-#pragma unroll
-    for (int q = 0; q < TT; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wc[q], bv, acc[q], 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < TT; ++q) wc[q] = wn[q];
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-
 // (r04, measured and dropped: two accumulator tiles per wave for T <= 32 - even / odd steps, added at the end - so that a wave always
 // has an independent MFMA to issue: 0.2039 vs 0.2054 ms per Mpixel.  The chain's latency is not what idles the matrix pipe.)
 // the 10 inputs of one pixel.  Pixel-major rows (x_cs == 1, the (N, 10) arrays of predict()) with an even pitch and an 8-byte
@@ -902,115 +860,6 @@ __device__ __forceinline__ void pred_load10(const PredArgs& a, int64_t pc, float
   } else {
 #pragma unroll
     for (int c = 0; c < 10; ++c) x[c] = a.x[pc * a.x_ps + c * a.x_cs];
-  }
-}
-
-// workgroups per CU: a wave of the T <= 32 kernel carries ONE accumulator chain (143 dependent MFMAs per tile) and a 16-value
-// sigmoid epilogue; with four waves per SIMD instead of two the matrix pipe has something to run while a wave is in its
-// epilogue or waits for its next operand (r03: 0.214 -> 0.199 ms per Mpixel, 111 VGPRs, W resident in 36.6 KB of LDS)
-#ifndef HSR_PRED_OCC1
-#define HSR_PRED_OCC1 4
-#endif
-#ifndef HSR_PRED_OCC2
-#define HSR_PRED_OCC2 2
-#endif
-constexpr int pred103_occupancy(int tt) { return tt == 1 ? HSR_PRED_OCC1 : tt == 2 ? HSR_PRED_OCC2 : 2; }
-template <int TT, bool WHOLE>
-__global__ __launch_bounds__(256, pred103_occupancy(TT)) void predict103_kernel(const PredArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* wl = reinterpret_cast<float*>(smem);
-  constexpr int Tp = TT * 32;                       // padded target count held by every wave
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int j = lane & 31, kh = lane >> 5;
-  if (WHOLE) {                                      // W (286 x Tp) resident for the whole launch
-    for (int i = t; i < 286 * Tp; i += 256) {
-      const int r = i / Tp, c = i % Tp;
-      wl[i] = c < a.T ? a.W[(size_t)r * a.ldw + c] : 0.0f;
-    }
-    __syncthreads();
-  }
-  float bv[TT][16];                                 // bias of this lane's targets: tile-invariant
-#pragma unroll
-  for (int q = 0; q < TT; ++q)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int trg = q * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      bv[q][r] = trg < a.T ? a.bias[trg] : 0.0f;
-    }
-  // the 10 inputs of the NEXT tile are loaded while this tile's MFMA chain runs (a fresh load at the top of every tile left
-  // the matrix pipe idle for one HBM latency per tile: ~2 us of a 9-27 us tile)
-  float xn[10];
-  auto load_inputs = [&](int64_t tile_) {
-    const int64_t p_ = tile_ * 128 + wave * 32 + j;
-    const int64_t pc_ = p_ < a.npix ? p_ : a.npix - 1;
-    pred_load10(a, pc_, xn);
-  };
-  if ((int64_t)blockIdx.x * 128 < a.npix) load_inputs(blockIdx.x);
-  for (int64_t tile = blockIdx.x; tile * 128 < a.npix; tile += gridDim.x) {
-    const int64_t p = tile * 128 + wave * 32 + j;
-    float z[11];
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < 10; ++c) {
-      const float xr = xn[c];
-      bad = bad || pred_bad_input(xr, a.use_nodata, a.nodata);
-      z[c] = (xr - a.mean[c]) * a.inv[c];
-    }
-    bad = bad && a.nan_bad != 0;
-    z[10] = 1.0f;
-    if ((tile + gridDim.x) * 128 < a.npix) load_inputs(tile + gridDim.x);
-    f32x16 acc[TT];
-#pragma unroll
-    for (int q = 0; q < TT; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[q][r] = bv[q][r];
-    if (WHOLE) {
-      mfma_steps103<0, kSteps103, TT>(z, kh, wl, Tp, 0, j, acc);
-    } else {
-      // 9 chunks of 32 W rows (the last has 30), double-buffered: chunk c+1 is copied while chunk c is used
-      auto stage = [&](int c, int buf) {
-        float* dst = wl + buf * kChunkRows * Tp;
-        const int rows = c == 8 ? 286 - 8 * kChunkRows : kChunkRows;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll 2
-        for (int i = t; i < rows * Tp; i += 256) {
-          const int r = i / Tp, col = i % Tp;
-          dst[i] = col < a.T ? a.W[(size_t)(c * kChunkRows + r) * a.ldw + col] : 0.0f;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      stage(0, 0);
-      __syncthreads();
-#define HSR_CHUNK(C)                                                                                   \
-  do {                                                                                                 \
-    if (C < 8) stage(C + 1, (C + 1) & 1);                                                              \
-    mfma_steps103<C * 16, (C == 8 ? kSteps103 : C * 16 + 16), TT>(z, kh, wl + (C & 1) * kChunkRows * Tp, Tp, \
-                                                                  C * kChunkRows, j, acc);               \
-    __syncthreads();                                                                                   \
-  } while (0)
-      HSR_CHUNK(0); HSR_CHUNK(1); HSR_CHUNK(2); HSR_CHUNK(3); HSR_CHUNK(4);
-      HSR_CHUNK(5); HSR_CHUNK(6); HSR_CHUNK(7); HSR_CHUNK(8);
-#undef HSR_CHUNK
-    }
-    if (p < a.npix) {
-      // keep the epilogue's addressing inside the tile loop: hoisted out of it (LICM) the 64-bit offsets of
-      // all 16*TT accumulator rows cost up to 288 VGPRs and spilled the accumulators
-      int64_t ostride = a.out_stride;
-      int tmax = a.T;
-      asm volatile("" : "+s"(ostride), "+s"(tmax));
-      float* orow = a.out + (size_t)(4 * kh) * ostride + p;
-#pragma unroll
-      for (int q = 0; q < TT; ++q) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int tu = q * 32 + (r & 3) + 8 * (r >> 2);      // wave-uniform part of the target index
-          const int trg = tu + 4 * kh;
-          float v = predict_activation(acc[q][r], a.act);
-          if (bad) v = __uint_as_float(0x7fc00000u);
-          if (trg < tmax) orow[(size_t)tu * ostride] = v;
-        }
-      }
-    }
   }
 }
 
@@ -1094,16 +943,16 @@ __device__ __forceinline__ void mfma_steps_orb2(const float (&Z)[11], int kh, co
   }
 }
 
-// Many targets (T > 96, e.g. EMIT's 285 bands): the chunked path above re-stages the whole 329 KB of W through LDS for
-// every 128-pixel tile, with nine barriers per tile, and sat at 39 % of the f32-MFMA peak against 50 % for T <= 32 where
-// W is resident.  W does not fit one LDS, but a SLICE of 96 targets does (286 x 96 x 4 = 110 KB): blockIdx.y picks the
+// Many targets (T > 96, e.g. EMIT's 285 bands): the chunked kernel of rounds 1-2 re-staged the whole 329 KB of W through
+// LDS for every 128-pixel tile, with nine barriers per tile, and sat at 39 % of the f32-MFMA peak against 50 % for T <= 32
+// where W was resident.  W does not fit one LDS, but a SLICE of 96 targets does (286 x 96 x 4 = 110 KB): blockIdx.y picks the
 // slice, the slice is staged once per workgroup and stays for the whole launch, and the workgroup (12 waves = 3 per
 // SIMD, each wave its own 32 pixels) walks the pixel tiles with no staging and no barrier in the loop.  The monomials
 // of a pixel are recomputed once per slice (2-4 v_mul per MFMA step of 3 x 64 cycles: free) and its 10 inputs re-read
 // (40 B per slice: nothing).  3 accumulator tiles per wave instead of 9.
 // r03: (a) 8 -> 12 waves on the one 96-target slice a CU holds (3 per SIMD, 168 VGPRs, no spill; 16 waves = 128 VGPRs spill):
 // 1.675 -> 1.603 ms at T = 285 on one box; (b) the kernel is a template on the slice width, and it also serves 33 <= T <= 96 with
-// ONE slice: the chunked predict103_kernel<2 / 3, false> (nine barriers and a re-staged W per 128-pixel tile) took 0.83-0.87 ms
+// ONE slice: the chunked kernel (nine barriers and a re-staged W per 128-pixel tile) took 0.83-0.87 ms
 // per Mpixel for 65-96 targets, the 96-wide slice kernel 0.51-0.52 ms; (c) slices are as narrow as the target count allows
 // (T = 97: two slices of 64 instead of two of 96).  64-target slices run 16 waves (4 per SIMD) on their 73 KB of W.
 // Wave priorities of the slice and 16-target kernels (r04, after they paid in the uint16 K1): level of a wave during its MFMA chain /
@@ -1111,45 +960,10 @@ __device__ __forceinline__ void mfma_steps_orb2(const float (&Z)[11], int kh, co
 // (profiles/r04_k4_ridge.md): none 0.129 / 0.203 / 0.528 / 1.523; REST 1 (shipped): 0.123 / 0.198 / 0.520 / 1.491; REST 3: the same;
 // CHAIN 3 or 1: no change; STAGGER (the four waves of a SIMD at four different levels during the chain, so that they drift apart and
 // one wave's epilogue meets another's chain - either guess of the wave -> SIMD mapping): T = 32 unchanged at 0.200-0.205.
-#ifndef HSR_PRED_PRIO_CHAIN
-#define HSR_PRED_PRIO_CHAIN 0
-#endif
-#ifndef HSR_PRED_PRIO_REST
-#define HSR_PRED_PRIO_REST 1
-#endif
-#ifndef HSR_PRED_PRIO_STAGGER     // 1: chain level = (wave >> 2) & 3, 2: wave & 3 - the waves of a SIMD at DIFFERENT levels drift apart
-#define HSR_PRED_PRIO_STAGGER 0
-#endif
-__device__ __forceinline__ void pred_chain_prio(int wave) {
-  if (HSR_PRED_PRIO_STAGGER == 0) {
-    if (HSR_PRED_PRIO_CHAIN != HSR_PRED_PRIO_REST) __builtin_amdgcn_s_setprio(HSR_PRED_PRIO_CHAIN);
-    return;
-  }
-  const int k = __builtin_amdgcn_readfirstlane(HSR_PRED_PRIO_STAGGER == 1 ? (wave >> 2) & 3 : wave & 3);
-  if (k == 3) __builtin_amdgcn_s_setprio(3);
-  else if (k == 2) __builtin_amdgcn_s_setprio(2);
-  else if (k == 1) __builtin_amdgcn_s_setprio(1);
-  else __builtin_amdgcn_s_setprio(0);
-}
-__device__ __forceinline__ void pred_rest_prio() {
-  if (HSR_PRED_PRIO_STAGGER != 0 || HSR_PRED_PRIO_CHAIN != HSR_PRED_PRIO_REST) __builtin_amdgcn_s_setprio(HSR_PRED_PRIO_REST);
-}
-#ifndef HSR_SLICE_WAVES
-#define HSR_SLICE_WAVES 12
-#endif
-#ifndef HSR_SLICE2_WAVES
-#define HSR_SLICE2_WAVES 16
-#endif
-#ifndef HSR_SLICE1_WAVES
-#define HSR_SLICE1_WAVES 16
-#endif
-#ifndef HSR_SLICE1_WGS
-#define HSR_SLICE1_WGS 1
-#endif
-constexpr int slice_waves(int tt) { return tt == 3 ? HSR_SLICE_WAVES : (tt == 1 ? HSR_SLICE1_WAVES : HSR_SLICE2_WAVES); }
-constexpr int slice_wgs(int tt) { return tt == 1 ? HSR_SLICE1_WGS : 1; }       // workgroups per CU
+// Shipped: level 1 from the start of the tile loop, 0 during each MFMA chain, back to 1 after it.
+constexpr int slice_waves(int tt) { return tt == 3 ? 12 : 16; }      // one workgroup per CU
 template <int TT>
-__global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) * slice_wgs(TT) + 3) / 4) void predict103_slice_kernel(const PredArgs a, const int16_t* __restrict__ src_rows) {
+__global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) + 3) / 4) void predict103_slice_kernel(const PredArgs a, const int16_t* __restrict__ src_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* wl = reinterpret_cast<float*>(smem);       // [2 * kStepsOrb2][Tp]: W's rows in orbit order (kOrb2)
   constexpr int Tp = TT * 32;
@@ -1179,7 +993,7 @@ __global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) * slice_wgs(
     pred_load10(a, pc_, xn);
   };
   if ((int64_t)blockIdx.x * kSlicePix < a.npix) load_inputs(blockIdx.x);
-  if (HSR_PRED_PRIO_REST != 0) __builtin_amdgcn_s_setprio(HSR_PRED_PRIO_REST);
+  __builtin_amdgcn_s_setprio(1);
   for (int64_t tile = blockIdx.x; tile * kSlicePix < a.npix; tile += gridDim.x) {
     const int64_t p = tile * kSlicePix + wave * 32 + j;
     float z[11];
@@ -1204,13 +1018,15 @@ __global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) * slice_wgs(
     for (int q = 0; q < TT; ++q)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[q][r] = bv[q][r];
-    pred_chain_prio(wave);
+    __builtin_amdgcn_s_setprio(0);
     mfma_steps_orb2<TT>(z, kh, wl, Tp, j, acc);
-    pred_rest_prio();
+    __builtin_amdgcn_s_setprio(1);
     if (p < a.npix) {
+      // keep the epilogue's addressing inside the tile loop: hoisted out of it (LICM) the 64-bit offsets of
+      // all 16*TT accumulator rows cost up to 288 VGPRs and spilled the accumulators
       int64_t ostride = a.out_stride;
       int tmax = a.T;
-      asm volatile("" : "+s"(ostride), "+s"(tmax));        // keep the addressing inside the loop (see predict103_kernel)
+      asm volatile("" : "+s"(ostride), "+s"(tmax));
       float* orow = a.out + (size_t)(t0 + 4 * kh) * ostride + p;
 #pragma unroll
       for (int q = 0; q < TT; ++q) {
@@ -1243,13 +1059,7 @@ __global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) * slice_wgs(
 //   D[i][j]: lane (j, g) holds targets 4 g + r, r = 0 .. 3, of pixel j: 64-byte store segments per target.
 // One 16-wave workgroup per CU, W staged once.  (Three such tiles for 33 <= T <= 48 were measured too: 82 x 6 MFMAs of 32 cycles are
 // no better than the 64-target slice's 143 x 2 of 64; those T keep the slice kernel.)
-#ifndef HSR_X16_WAVES
-#define HSR_X16_WAVES 12
-#endif
-#ifndef HSR_X16_WGS
-#define HSR_X16_WGS 2
-#endif
-constexpr int kX16Waves = HSR_X16_WAVES, kX16Wgs = HSR_X16_WGS;     // 2 x 12 waves per CU = 6 per SIMD at <= 80 VGPRs (r04: 16 x 1: 0.132 ms per Mpixel)
+constexpr int kX16Waves = 12, kX16Wgs = 2;     // 2 x 12 waves per CU = 6 per SIMD at <= 80 VGPRs (r04: 16 x 1: 0.132 ms per Mpixel)
 __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel(const PredArgs a, const int16_t* __restrict__ src_rows) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* wl = reinterpret_cast<float*>(smem);          // [4 * kStepsOrb][16]
@@ -1274,7 +1084,7 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
     }
   };
   if ((int64_t)blockIdx.x * kPix < a.npix) load_inputs(blockIdx.x);
-  if (HSR_PRED_PRIO_REST != 0) __builtin_amdgcn_s_setprio(HSR_PRED_PRIO_REST);
+  __builtin_amdgcn_s_setprio(1);
   for (int64_t tile = blockIdx.x; tile * kPix < a.npix; tile += gridDim.x) {
     float Z[2][11];                                    // this lane group's permuted copy of the standardised inputs
     bool bad[2] = {false, false};
@@ -1305,7 +1115,7 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
       for (int r = 0; r < 4; ++r) acc[h][r] = bias[r];
     const float* wr = wl + g * 16 + i;
     float wc = wr[0], wn = 0.0f;
-    pred_chain_prio(wave);
+    __builtin_amdgcn_s_setprio(0);
 #pragma unroll
     for (int s = 0; s < kStepsOrb; ++s) {
       const float b0 = Z[0][kOrb103.rep[s][0]] * Z[0][kOrb103.rep[s][1]] * Z[0][kOrb103.rep[s][2]];
@@ -1316,10 +1126,10 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
       wc = wn;
       __builtin_amdgcn_sched_barrier(0);
     }
-    pred_rest_prio();
+    __builtin_amdgcn_s_setprio(1);
     int64_t ostride = a.out_stride;
     int tmax = a.T;
-    asm volatile("" : "+s"(ostride), "+s"(tmax));      // keep the addressing inside the loop (see predict103_kernel)
+    asm volatile("" : "+s"(ostride), "+s"(tmax));      // keep the addressing inside the loop (see predict103_slice_kernel)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int64_t p = tile * kPix + wave * 32 + h * 16 + i;
@@ -1336,74 +1146,66 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
   }
 }
 
-static void launch_predict103_x16(const PredArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)4 * kStepsOrb * 16 * 4;
-  constexpr int pix = 32 * kX16Waves;
-  int64_t tiles = (a.npix + pix - 1) / pix;
-  const int gx = (int)(tiles < 256 * kX16Wgs ? tiles : 256 * kX16Wgs);
-  hipLaunchKernelGGL(predict103_x16_kernel, dim3(gx), dim3(64 * kX16Waves), lds, s, a, g_orb_rows_dev);
-}
-
-template <int TT>
-static void launch_predict103_slices(const PredArgs& a, int slices, hipStream_t s) {
-  const size_t lds = (size_t)2 * kStepsOrb2 * TT * 32 * 4;
-  static thread_local bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(predict103_slice_kernel<TT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    configured = true;
-  }
-  constexpr int pix = 32 * slice_waves(TT);
-  int64_t tiles = (a.npix + pix - 1) / pix;
-  int gx = 256 * slice_wgs(TT) / slices;       // one workgroup per CU in all (73 / 110 KB of LDS each; T <= 32: slice_wgs)
-  if (gx < 1) gx = 1;
-  if (tiles < gx) gx = (int)tiles;
-  hipLaunchKernelGGL(predict103_slice_kernel<TT>, dim3(gx, slices), dim3(64 * slice_waves(TT)), lds, s, a, g_orb_rows_dev + 4 * kStepsOrb);
-}
-
-template <int TT, bool WHOLE>
-static void launch_predict103(const PredArgs& a, hipStream_t s) {
-  const size_t lds = WHOLE ? (size_t)286 * TT * 32 * 4 : (size_t)2 * kChunkRows * TT * 32 * 4;
-  static thread_local bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(predict103_kernel<TT, WHOLE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();
-    configured = true;
-  }
-  int64_t tiles = (a.npix + 127) / 128;
-  const int resident = 256 * pred103_occupancy(TT);
-  const int grid = (int)(tiles < resident ? tiles : resident);
-  hipLaunchKernelGGL((predict103_kernel<TT, WHOLE>), dim3(grid), dim3(256), lds, s, a);
-}
-
-// returns false when the shape is not covered (caller falls back to the generic kernel)
-static bool try_predict103(const PredArgs& a, hipStream_t s) {
-  if (a.n_in != 10 || a.nfeat != 285 || g_orb_rows_dev == nullptr) return false;
+// Picks the predict kernel, its grid and its LDS for the shape in PredArgs, and launches it.  10 inputs at degree 3 with the orbit
+// rows on the device and T <= 512 take the MFMA kernels above; every other shape takes the generic predict_kernel.
+typedef void (*PredOrbKernel)(PredArgs, const int16_t*);
+typedef void (*PredGenericKernel)(PredArgs);
+static int launch_predict(const PredArgs& a, int degree, hipStream_t s) {
+  static thread_local size_t configured[7] = {};     // per kernel: x16, slice<1 / 2 / 3>, predict_kernel<1 / 2 / 4>
+  PredOrbKernel orb = nullptr;
+  PredGenericKernel generic = nullptr;
+  const void* kern;
+  const char* what;
+  int slot, gx, slices = 1, threads;
+  size_t lds;
+  const int16_t* rows = nullptr;
   const int tt = a.ttiles;
-#ifndef HSR_PRED_NO_X16
-  if (a.T <= 16) {                                        // 16-target tiles (v_mfma_f32_16x16x4_f32)
-    launch_predict103_x16(a, s);
-    return true;
+  if (degree == 3 && a.n_in == 10 && a.nfeat == 285 && g_orb_rows_dev != nullptr && tt <= 16) {
+    int waves, wgs_per_cu = 1;
+    if (a.T <= 16) {                                    // 16-target tiles (v_mfma_f32_16x16x4_f32)
+      orb = predict103_x16_kernel;
+      what = "predict103_x16_kernel launch";
+      slot = 0;
+      waves = kX16Waves;
+      wgs_per_cu = kX16Wgs;
+      lds = (size_t)4 * kStepsOrb * 16 * 4;
+      rows = g_orb_rows_dev;                            // kOrb103.src
+    } else {
+      // T <= 32: one 16-wave workgroup per CU, W (36.6 KB) staged once per CU (0.209 -> 0.199 ms);
+      // T <= 512: slices of 64 or 96 targets, as few and as narrow as T allows
+      slices = (tt + 2) / 3;
+      const int per = (tt + slices - 1) / slices;       // 32-target tiles per slice: 1 only for tt == 1
+      orb = per == 1 ? predict103_slice_kernel<1> : (per <= 2 ? predict103_slice_kernel<2> : predict103_slice_kernel<3>);
+      what = "predict103_slice_kernel launch";
+      slot = per;
+      waves = slice_waves(per);
+      lds = (size_t)2 * kStepsOrb2 * per * 32 * 4;
+      rows = g_orb_rows_dev + 4 * kStepsOrb;            // kOrb2.src
+    }
+    const int pix = 32 * waves;
+    const int64_t tiles = (a.npix + pix - 1) / pix;
+    gx = 256 * wgs_per_cu / slices;                     // one workgroup per CU in all (73 / 110 KB of LDS each), two for x16
+    if (gx < 1) gx = 1;
+    if (tiles < gx) gx = (int)tiles;
+    threads = 64 * waves;
+    kern = reinterpret_cast<const void*>(orb);
+  } else {
+    lds = ((size_t)kPredPix * (a.kpad + 1) + (size_t)kPredPix * (a.n_in + 1) + kPredPix) * sizeof(float);
+    HSR_REQUIRE(lds <= 150 * 1024, HSR_ERR_UNSUPPORTED, "hsr_polyfeat_predict: %zu bytes of LDS needed", lds);
+    const int64_t tiles = (a.npix + kPredPix - 1) / kPredPix;
+    gx = (int)(tiles < 512 ? tiles : 512);
+    threads = kPredThreads;
+    const int per_wave = (tt + 1) / 2;                  // target tiles a wave pair must cover
+    const int variant = per_wave <= 1 ? 0 : (per_wave <= 2 ? 1 : 2);
+    generic = variant == 0 ? predict_kernel<1> : (variant == 1 ? predict_kernel<2> : predict_kernel<4>);
+    what = "predict_kernel launch";
+    slot = 4 + variant;
+    kern = reinterpret_cast<const void*>(generic);
   }
-#endif
-#ifdef HSR_PRED_CHUNKED
-  if (tt == 1) launch_predict103<1, true>(a, s);          // diagnostic builds: four 4-wave workgroups per CU, each with its own copy of W
-#else
-  if (tt == 1) launch_predict103_slices<1>(a, 1, s);      // T <= 32: one 16-wave workgroup per CU, W (36.6 KB) staged once per CU (0.209 -> 0.199 ms)
-#endif
-#ifdef HSR_PRED_CHUNKED
-  else if (tt == 2) launch_predict103<2, false>(a, s);    // diagnostic builds: the chunked kernels of rounds 1-2
-  else if (tt == 3) launch_predict103<3, false>(a, s);
-#endif
-  else if (tt <= 16) {                                    // T <= 512: slices of 64 or 96 targets, as few and as narrow as T allows
-    const int slices = (tt + 2) / 3;
-    const int per = (tt + slices - 1) / slices;           // 32-target tiles per slice: 2 or 3 (1 only for tt == 1)
-    if (per <= 2) launch_predict103_slices<2>(a, slices, s);
-    else launch_predict103_slices<3>(a, slices, s);
-  }
-  else return false;
-  return true;
+  raise_lds_limit(kern, lds, configured[slot]);
+  if (orb) hipLaunchKernelGGL(orb, dim3(gx, slices), dim3(threads), lds, s, a, rows);
+  else hipLaunchKernelGGL(generic, dim3(gx), dim3(threads), lds, s, a);
+  return check_hip(hipGetLastError(), what);
 }
 
 static int ensure_table(int n_in, int degree) {
@@ -1856,32 +1658,5 @@ extern "C" int hsr_polyfeat_predict_cube(const float* x_dev, int64_t x_ps, int64
   a.nodata = nodata;
   a.out = out_dev;
   a.out_stride = out_stride;
-  if (degree == 3 && try_predict103(a, (hipStream_t)stream)) {
-    HSR_LAUNCH_CHECK("predict103_kernel");
-    return HSR_OK;
-  }
-  const size_t lds = ((size_t)kPredPix * (a.kpad + 1) + (size_t)kPredPix * (n_in + 1) + kPredPix) * sizeof(float);
-  HSR_REQUIRE(lds <= 150 * 1024, HSR_ERR_UNSUPPORTED, "hsr_polyfeat_predict: %zu bytes of LDS needed", lds);
-  int64_t tiles = (npix + kPredPix - 1) / kPredPix;
-  const int grid = (int)(tiles < 512 ? tiles : 512);
-  hipStream_t s = (hipStream_t)stream;
-  static thread_local size_t configured[3] = {0, 0, 0};
-  const int per_wave = (a.ttiles + 1) / 2;     // target tiles a wave pair must cover
-  const int variant = per_wave <= 1 ? 0 : (per_wave <= 2 ? 1 : 2);
-#define HSR_PRED_LAUNCH(TT, slot)                                                                                   \
-  do {                                                                                                              \
-    if (lds > configured[slot]) {                                                                                   \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(predict_kernel<TT>),                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                              \
-      (void)hipGetLastError();                                                                                      \
-      configured[slot] = lds;                                                                                       \
-    }                                                                                                               \
-    hipLaunchKernelGGL(predict_kernel<TT>, dim3(grid), dim3(kPredThreads), lds, s, a);                              \
-  } while (0)
-  if (variant == 0) HSR_PRED_LAUNCH(1, 0);
-  else if (variant == 1) HSR_PRED_LAUNCH(2, 1);
-  else HSR_PRED_LAUNCH(4, 2);
-#undef HSR_PRED_LAUNCH
-  HSR_LAUNCH_CHECK("predict_kernel");
-  return HSR_OK;
+  return launch_predict(a, degree, (hipStream_t)stream);
 }

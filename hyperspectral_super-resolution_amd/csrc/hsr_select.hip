@@ -29,21 +29,11 @@ struct SelArgs {
 // r03: 1024-thread workgroups (were 256 / 512).  Every workgroup ends by adding its LDS histogram to the global one with
 // integer atomics - in pass 2 a few thousand non-zero bins each, all workgroups on the same addresses; the same number of
 // resident waves in a quarter / half of the workgroups: 404 -> 367 us (three 6144 x 6144 planes), 86 -> 60 us (1024 x 1024).
-#ifndef HSR_SEL_THREADS
-#define HSR_SEL_THREADS 1024
-#endif
-#ifndef HSR_ROWS_THREADS
-#define HSR_ROWS_THREADS 1024
-#endif
-constexpr int kSelThreads = HSR_SEL_THREADS;      // workgroup of select_hist_kernel
-constexpr int kRowsThreads = HSR_ROWS_THREADS;    // workgroup of select_hist_rows4_kernel
+constexpr int kSelThreads = 1024;      // workgroup of select_hist_kernel
+constexpr int kRowsThreads = 1024;     // workgroup of select_hist_rows4_kernel
 // resident waves stay the same whatever the workgroup size: the caps below count workgroups of 256 / 512 threads
-#ifndef HSR_SEL_PLANE_WGS
-#define HSR_SEL_PLANE_WGS (1024 * 256 / HSR_SEL_THREADS)
-#endif
-#ifndef HSR_SEL_ROWS4_WGS
-#define HSR_SEL_ROWS4_WGS (1024 * 512 / HSR_ROWS_THREADS)
-#endif
+constexpr int kSelPlaneWgs = 1024 * 256 / kSelThreads;
+constexpr int kSelRows4Wgs = 1024 * 512 / kRowsThreads;
 
 // VEC: band-major planes whose rows start 16-byte aligned (and a 4-byte aligned mask): 4 samples + 4 mask bytes
 // per load, two loads in flight per thread.  The first version walked the plane sample by sample behind a
@@ -212,10 +202,7 @@ __device__ __forceinline__ void hist_pass_rows4(const SelArgs& a, int bid, int n
                       : (PASS == 2 ? a.hist2 + (size_t)c * kQ * kBins2 : a.hist3 + (size_t)c * kQ * kBins3);
   }
   const float4* rows = reinterpret_cast<const float4*>(a.x);
-#ifndef HSR_ROWS_U
-#define HSR_ROWS_U 4
-#endif
-  constexpr int U = HSR_ROWS_U;
+  constexpr int U = 4;
   const int64_t stride = (int64_t)nblk * kRowsThreads;
   const int64_t first = (int64_t)bid * kRowsThreads + (threadIdx.x & ~63);
   auto sweep = [&](auto has_mask) {
@@ -298,17 +285,12 @@ static void launch_rows4(const SelArgs& a, hipStream_t s) {
   constexpr int NB = PASS == 1 ? kBins1 : (PASS == 2 ? kBins2 * kLdsQ : kBins3 * kLdsQ);
   const size_t lds = (size_t)a.nb * NB * sizeof(uint32_t);
   static thread_local size_t configured = 0;
-  if (lds > configured) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(select_hist_rows4_kernel<PASS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    (void)hipGetLastError();
-    configured = lds;
-  }
+  raise_lds_limit(reinterpret_cast<const void*>(select_hist_rows4_kernel<PASS>), lds, configured);
   // (r04: above a megapixel a workgroup takes two iterations - half the workgroups, half the flush atomics onto the same global words:
   // 1448 x 1448 rows 99 -> 83 us, planes 71 -> 58; four or eight iterations, and two below a megapixel, were slower)
   const int64_t per_wg = (int64_t)kRowsThreads * 4 * (a.npix > (1 << 20) ? 2 : 1);
   int64_t gx = (a.npix + per_wg - 1) / per_wg;
-  if (gx > HSR_SEL_ROWS4_WGS) gx = HSR_SEL_ROWS4_WGS;
+  if (gx > kSelRows4Wgs) gx = kSelRows4Wgs;
   hipLaunchKernelGGL(select_hist_rows4_kernel<PASS>, dim3((unsigned)gx), dim3(kRowsThreads), lds, s, a);
 }
 
@@ -647,7 +629,7 @@ static dim3 select_grid(int64_t npix, int nb, int pass = 1) {
   // megapixel on: 1024 x 1024 45.5 -> 43.6 us, 1448 x 1448 53.8 -> 51.3 (a quarter, or half below a megapixel: no better)
   const int64_t per_wg = (int64_t)kSelThreads * 8 * (npix > (1 << 20) ? 2 : 1) * (pass == 2 && npix >= (1 << 20) ? 2 : 1);
   int64_t gx = (npix + per_wg - 1) / per_wg;
-  if (gx > HSR_SEL_PLANE_WGS) gx = HSR_SEL_PLANE_WGS;
+  if (gx > kSelPlaneWgs) gx = kSelPlaneWgs;
   return dim3((unsigned)gx, nb);
 }
 

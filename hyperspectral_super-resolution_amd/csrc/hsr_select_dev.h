@@ -70,10 +70,7 @@ __device__ __forceinline__ void dedupe_prefixes(uint32_t (&pre)[kQ]) {
 // (96 KB for the three channels of the band-last kernel: one workgroup per CU) and was the slowest pass for lack of waves in
 // flight, not for its atomics.
 constexpr int kLdsQ = 2;
-#ifndef HSR_SEL_COPIES
-#define HSR_SEL_COPIES 4
-#endif
-constexpr int kPass1Copies = HSR_SEL_COPIES;   // pass-1 histogram copies of select_hist_kernel (planes)
+constexpr int kPass1Copies = 4;   // pass-1 histogram copies of select_hist_kernel (planes)
 // r04: the prefixes are wave-uniform, so which of them exist is a SCALAR question: a sample is compared with query 0's prefix, with
 // the second distinct one only if there is one and with a third / fourth only if there are (`more`) - the four compare-and-branch
 // groups per sample of r03 (three of them against parked prefixes that nothing matches) were most of what pass 2 cost over its bytes.

@@ -146,10 +146,7 @@ constexpr int kGroups = 8;                          // band groups per workgroup
 constexpr int kBandSlots = HSR_MAX_BANDS / kGroups;  // 2 bands per thread
 constexpr int kTapChunk = 16;                       // taps per unrolled dot-product chunk
 constexpr int kScanBatch = 5;                       // ds_read_b128 in flight per thread in the uint16 sweep
-#ifndef HSR_F32_SCAN_BATCH
-#define HSR_F32_SCAN_BATCH 5
-#endif
-constexpr int kScanBatchF32 = HSR_F32_SCAN_BATCH;   // ... in the float32 sweep
+constexpr int kScanBatchF32 = 5;                    // ... in the float32 sweep
 
 // Group geometry: P = 64 pixels per LDS group, 512 threads (8 waves), lane = pixel, wave = band group; 2 workgroups
 // per CU: 16 waves (4 per SIMD, <= 128 VGPRs) and ~146 KB of LDS groups per CU.
@@ -709,11 +706,6 @@ __global__ __launch_bounds__(8 * P, 4) void srf_kernel(const SrfArgs a) {
       }
     }
   };
-
-#ifdef HSR_CONSTANTS_FIRST      // diagnostic variant (tools/dbg/build_variants.sh): round 2's order, for A/B runs
-  stage_constants();
-  constants_staged = true;
-#endif
 
 #ifdef HSR_PHASE_STAMPS
   unsigned long long stamp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1688,12 +1680,7 @@ static int srf_select(const SrfArgs& a, int deg, const SrfTuning& tn, bool align
 static int srf_launch(SrfArgs& a, const SrfLaunch& L, hipStream_t stream) {
   const SrfKernel kern = kSrfKernels[L.deg].k[L.variant];
   static thread_local size_t configured[HSR_MAX_DEG + 1][kSrfVariants] = {};
-  size_t& c = configured[L.deg][L.variant];
-  if (L.lds > c) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
-    (void)hipGetLastError();
-    c = L.lds;
-  }
+  raise_lds_limit(reinterpret_cast<const void*>(kern), L.lds, configured[L.deg][L.variant]);
 #ifdef HSR_PHASE_STAMPS
   a.stamps = g_stamp_buffer;
   a.stamps2 = g_stamp_buffer2;

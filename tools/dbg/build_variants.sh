@@ -1,6 +1,7 @@
 #!/bin/bash
-# diagnostic variants of the library (never shipped): tools/dbg/libhsr_<name>.so, selected with HSR_LIBRARY=...
-#   tools/dbg/build_variants.sh "name:-DMACRO=1[:source]" ...      (source defaults to hsr_srf; e.g. hsr_ridge)
+# instrumentation variants of the library (never shipped): tools/dbg/libhsr_<name>.so, selected with HSR_LIBRARY=...
+#   tools/dbg/build_variants.sh "name:-DHSR_PHASE_STAMPS[:source]" ...   (source defaults to hsr_srf)
+#   tools/dbg/build_variants.sh "gstamp:-DHSR_GRAM_STAMPS:hsr_ridge"      (the Gram timeline of tools/gram_stamps.py)
 set -e
 cd "$(dirname "$0")/../../hyperspectral_super-resolution_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-function"
