@@ -901,6 +901,12 @@ __global__ __launch_bounds__(8 * P, 4) void srf_kernel(const SrfArgs a) {
         }
       }
     }
+    // The generic kernel (weights from global memory) is selected whatever the output layout, so it also gets the 16-byte aligned
+    // padded rows the OUTV kernels own as whole rows (hsr.h): their pad columns are written as zeros here, by the first wave.
+    if constexpr (!WLDS)
+      if (grp == 0 && pvalid && a.out_bs == 1 && ops > a.nb && (ops & 3) == 0 && ops <= HSR_MAX_BANDS &&
+          (reinterpret_cast<uintptr_t>(cu.pseudo_dev) & 15) == 0)
+        for (int c = a.nb; c < ops; ++c) st_stream(cu.pseudo_dev + (pix0 + pl) * ops + c, 0.0f);
 #pragma unroll
     for (int j = 0; j < kBandSlots; ++j) {
       if (bval[j]) {
@@ -1644,8 +1650,9 @@ static int srf_select(const SrfArgs& a, int deg, const SrfTuning& tn, bool align
   const int64_t cap = (int64_t)(256 - tn.reserved_cus) * 2;   // CUs x resident workgroups
   L->grid = (int)(a.nunits < cap ? a.nunits : cap);
   if (a.u16) {
-    // the ring kernel: two group buffers, flags [2][64], weights, rows; twice per CU: B <= ~300 spectral samples
-    const size_t ring_lds = (size_t)2 * kGroupPixels * a.B * 2 + 128 * sizeof(uint32_t) + weights + (outv ? slab : 0);
+    // the ring kernel: two group buffers, flags [2][64] (+ the next units' records [2][16] in a batch), weights, rows; twice per
+    // CU: B <= ~300 spectral samples
+    const size_t ring_lds = (size_t)2 * kGroupPixels * a.B * 2 + (128 + (batch ? 32 : 0)) * sizeof(uint32_t) + weights + (outv ? slab : 0);
     const bool ring = aligned && tn.u16_ring && ring_lds <= 80 * 1024;
     HSR_REQUIRE(!job || (ring && outv && 2 * kGroupPixels * a.B * 2 >= 12 * 1024), HSR_ERR_UNSUPPORTED,
                 "%s: this launch cannot carry an apply job: uint16 tiles ride only in the double-buffered kernel (16-byte aligned cube, "
@@ -1676,6 +1683,13 @@ static int srf_select(const SrfArgs& a, int deg, const SrfTuning& tn, bool align
   return HSR_OK;
 }
 
+// The last successful K1 launch of this thread (hsr_srf_last_launch): deg < 0 = none since the last read.
+struct SrfLastLaunch {
+  int deg = -1, variant = -1;
+  size_t lds = 0;
+};
+static thread_local SrfLastLaunch g_srf_last;
+
 // Launches what srf_select chose.  A kernel's dynamic-LDS limit is raised when its launches grow (one cache per kernel).
 static int srf_launch(SrfArgs& a, const SrfLaunch& L, hipStream_t stream) {
   const SrfKernel kern = kSrfKernels[L.deg].k[L.variant];
@@ -1687,7 +1701,9 @@ static int srf_launch(SrfArgs& a, const SrfLaunch& L, hipStream_t stream) {
   a.stamps3 = g_stamp_buffer3;
 #endif
   hipLaunchKernelGGL(kern, dim3(L.grid), dim3(512), L.lds, stream, a);
-  return check_hip(hipGetLastError(), L.what);
+  const int rc = check_hip(hipGetLastError(), L.what);
+  if (rc == HSR_OK) g_srf_last = {L.deg, L.variant, L.lds};
+  return rc;
 }
 
 // Band table of a launch: validated supports, LDS weight segments, band -> (group, slot) assignment.
@@ -1781,6 +1797,24 @@ static int srf_common(SrfArgs& a, const int32_t* k0, const int32_t* klen, int32_
 }
 
 }  // namespace hsr
+
+extern "C" int hsr_srf_last_launch(int32_t* deg, int32_t* variant, int64_t* lds_bytes) {
+  const hsr::SrfLastLaunch r = hsr::g_srf_last;
+  hsr::g_srf_last = hsr::SrfLastLaunch{};
+  if (deg) *deg = r.deg;
+  if (variant) *variant = r.variant;
+  if (lds_bytes) *lds_bytes = r.deg >= 0 ? (int64_t)r.lds : -1;
+  return r.deg >= 0 ? 1 : 0;
+}
+
+extern "C" int hsr_srf_kernel_instance(int32_t deg, int32_t variant) {
+  if (deg < 0 || deg > HSR_MAX_DEG || variant < 0 || variant >= hsr::kSrfVariants) {
+    hsr::set_error("hsr_srf_kernel_instance: (deg=%d, variant=%d) outside the table [0,%d] x [0,%d)", deg, variant, HSR_MAX_DEG,
+                   (int)hsr::kSrfVariants);
+    return -1;
+  }
+  return hsr::kSrfKernels[deg].k[variant] != nullptr ? 1 : 0;
+}
 
 extern "C" int hsr_partial_slots(int64_t npix, const hsr_srf_options* opts) {
   hsr::SrfTuning tn;

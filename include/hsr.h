@@ -671,6 +671,15 @@ int hsr_pipeline_status(hsr_pipeline* pipeline, hsr_stream_t main_stream, uint32
  * mode 2: as 0 with 36 KiB slabs - the uint16 kernel's group - still 2 workgroups per CU (73 KB per CU in flight);
  * mode 3: 36 KiB slabs, 4 workgroups per CU (146 KB per CU in flight: what a deeper ring would reach). */
 int hsr_probe_read(const void* buf_dev, int64_t bytes, int32_t mode, float* sink_dev, hsr_stream_t stream);
+/* Which K1 kernel instance ran.  Host only; these two add no record and change no entry point, so HSR_ABI_VERSION stays.
+ * Every K1 launch (the hsr_srf_* entry points, the batch, the step executor and the pipelines) records its instance
+ * (deg, variant) of the library's K1 kernel table and its dynamic LDS bytes, per thread.  hsr_srf_last_launch returns 1 and
+ * that record of the calling thread's last successful K1 launch, then clears it; 0 (and -1 in every output) if there was no
+ * K1 launch since the last read.  NULL outputs are skipped.
+ * hsr_srf_kernel_instance: 1 if the table holds a kernel at (deg, variant), 0 for an empty entry, -1 outside the table
+ * (deg in [0, HSR_MAX_DEG], variant in [0, 22)).  The variant numbering is the enum SrfVariant of csrc/hsr_srf.hip. */
+int hsr_srf_last_launch(int32_t* deg, int32_t* variant, int64_t* lds_bytes);
+int hsr_srf_kernel_instance(int32_t deg, int32_t variant);
 
 #ifdef __cplusplus
 }

@@ -194,6 +194,25 @@ def test_fused_launch_predicate_and_exchange_validation_host_side():
     assert lib.hsr_pipeline_status(None, None, ctypes.byref(code)) == 1
 
 
+def test_k1_instance_table_and_launch_record_host_side():
+    """The K1 diagnostics need no device: the table query reports the 106 instances (5 degrees x 22 variants, minus the four
+    degree-0 apply slots) and refuses entries outside the table; the launch record starts empty, a call refused before its
+    launch leaves it empty, and a read clears it."""
+    lib = nat.load()
+    present = {(d, v) for d in range(nat.HSR_MAX_DEG + 1) for v in range(22) if lib.hsr_srf_kernel_instance(d, v) == 1}
+    empty = {(d, v) for d in range(nat.HSR_MAX_DEG + 1) for v in range(22) if lib.hsr_srf_kernel_instance(d, v) == 0}
+    assert len(present) == 106 and empty == {(0, 5), (0, 6), (0, 18), (0, 19)}
+    for d, v in ((-1, 0), (5, 0), (0, -1), (0, 22), (4, 1 << 20)):
+        assert lib.hsr_srf_kernel_instance(d, v) == -1 and b"hsr_srf_kernel_instance" in lib.hsr_last_error()
+    deg, var, lds = ctypes.c_int32(7), ctypes.c_int32(7), ctypes.c_int64(7)
+    lib.hsr_srf_last_launch(None, None, None)                    # whatever an earlier test left
+    assert lib.hsr_srf_last_launch(ctypes.byref(deg), ctypes.byref(var), ctypes.byref(lds)) == 0
+    assert (deg.value, var.value, lds.value) == (-1, -1, -1)
+    k = (ctypes.c_int32 * 1)(0)
+    rc = lib.hsr_srf_integrate(ctypes.c_void_p(16), 10, 9999, ctypes.c_void_p(16), k, k, 1, ctypes.c_void_p(16), 10, 1, None, None)
+    assert rc == 2 and lib.hsr_srf_last_launch(ctypes.byref(deg), ctypes.byref(var), ctypes.byref(lds)) == 0
+
+
 def test_step_plan_and_pipeline_creation_checks_host_side():
     """hsr_step_plan_create makes no HIP call, and the pipeline create functions check every argument before their first one:
     plans over fake device pointers (none is dereferenced) and the pipelines over them are refused with their messages."""
