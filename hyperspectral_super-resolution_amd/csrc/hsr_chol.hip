@@ -78,8 +78,11 @@ __device__ __forceinline__ double quad_sum(double v) {
 // memory up front so that their latency hides under the matrix instructions; the diagonal block multiplies by a
 // Newton-refined reciprocal instead of dividing.
 __global__ __launch_bounds__(1024) void chol_factor_kernel(double* __restrict__ A, int64_t lda, int n, int* info,
-                                                           double* __restrict__ dinv /* [n/32][32][32]: inverses of the diagonal blocks of L */
-                                                           CHOL_STAMP_PARAM) {
+                                                           double* __restrict__ dinv /* [n/32][32][32]: inverses of the diagonal blocks of L */,
+                                                           int64_t pair_a, int64_t pair_w CHOL_STAMP_PARAM) {
+  A += blockIdx.y * pair_a;          // system of a batched launch (0 otherwise): one workgroup per system
+  dinv += blockIdx.y * pair_w;
+  info += blockIdx.y;
   extern __shared__ __attribute__((aligned(16))) double chol_lds[];
   double (*D)[kCs] = reinterpret_cast<double (*)[kCs]>(chol_lds);                      // diagonal block
   double (*P)[kCs] = reinterpret_cast<double (*)[kCs]>(chol_lds + kCb * kCs);           // panel below, (n - 32) rows
@@ -426,7 +429,11 @@ constexpr int kResMaxN = 288;
 constexpr int kResTiles = 20;     // ceil(136 / 7): wave 0 owns none
 
 __global__ __launch_bounds__(kResThreads) void chol_factor_res_kernel(double* __restrict__ A, int64_t lda, int n, int* info,
-                                                                      double* __restrict__ dinv CHOL_STAMP_PARAM) {
+                                                                      double* __restrict__ dinv, int64_t pair_a,
+                                                                      int64_t pair_w CHOL_STAMP_PARAM) {
+  A += blockIdx.y * pair_a;          // system of a batched launch (0 otherwise): one workgroup per system
+  dinv += blockIdx.y * pair_w;
+  info += blockIdx.y;
   extern __shared__ __attribute__((aligned(16))) double chol_lds[];
   // two (D | P) buffers, block columns alternate: buffer 0 has n rows, buffer 1 n - 32 (the columns only get shorter)
   typedef double (*Rows)[kDs];
@@ -679,7 +686,11 @@ constexpr int kSw = 16;        // right-hand sides per slab
 constexpr int kYs = kSw + 1;   // LDS row stride of the slab
 __global__ __launch_bounds__(1024) void chol_solve_kernel(const double* __restrict__ L, int64_t lda, int n,
                                                           const double* __restrict__ dinv, double* __restrict__ B,
-                                                          int64_t ldb, int T, int dinv_in_lds CHOL_STAMP_PARAM) {
+                                                          int64_t ldb, int T, int dinv_in_lds, int64_t pair_a, int64_t pair_w,
+                                                          int64_t pair_b CHOL_STAMP_PARAM) {
+  L += blockIdx.y * pair_a;          // system of a batched launch (0 otherwise)
+  dinv += blockIdx.y * pair_w;
+  B += blockIdx.y * pair_b;
   extern __shared__ __attribute__((aligned(16))) double solve_lds[];
 #ifdef HSR_CHOL_STAMPS
 #define SOLVE_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x == 0 && stamps) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); stamps[200 + (k)] = t_; } } while (0)
@@ -806,6 +817,34 @@ __global__ __launch_bounds__(1024) void chol_solve_kernel(const double* __restri
 
 extern "C" size_t hsr_chol_work_bytes(int32_t n) { return n >= 32 ? (size_t)n * hsr::kCb * sizeof(double) : 0; }
 
+// Factor + solve of `npairs` systems of one shape: the systems are the grid's y extent (one factorisation workgroup each, then
+// the solve's right-hand-side slabs), with element strides between their matrices, workspaces and right-hand sides.
+static int chol_launch(double* a_dev, int64_t lda, int32_t n, int64_t pair_a, double* b_dev, int64_t ldb, int32_t nrhs,
+                       int64_t pair_b, double* work_dev, int32_t* info_dev, int32_t npairs, hipStream_t s) {
+  using namespace hsr;
+  const int64_t pair_w = (int64_t)n * kCb;
+  const size_t lds_f = ((size_t)kCb + (size_t)(n - kCb)) * kCs * sizeof(double);
+  static thread_local size_t configured = 0, configured_r = 0, configured_s = 0;
+  raise_lds_limit(reinterpret_cast<const void*>(chol_factor_kernel), lds_f, configured);
+  if (n <= kResMaxN) {
+    const size_t lds_r = (size_t)(2 * n - kCb) * kDs * sizeof(double);   // two (D | P) buffers of n and n - 32 rows of 34 doubles
+    raise_lds_limit(reinterpret_cast<const void*>(chol_factor_res_kernel), lds_r, configured_r);
+    hipLaunchKernelGGL(chol_factor_res_kernel, dim3(1, (unsigned)npairs), dim3(kResThreads), lds_r, s, a_dev, lda, n, info_dev, work_dev,
+                       pair_a, pair_w CHOL_STAMP_ARG);
+  } else {
+    hipLaunchKernelGGL(chol_factor_kernel, dim3(1, (unsigned)npairs), dim3(1024), lds_f, s, a_dev, lda, n, info_dev, work_dev, pair_a,
+                       pair_w CHOL_STAMP_ARG);
+  }
+  size_t lds_s = ((size_t)n + kCb) * kYs * sizeof(double);
+  const int dinv_in_lds = lds_s + (size_t)n * kCs * sizeof(double) <= 160 * 1024 ? 1 : 0;
+  if (dinv_in_lds) lds_s += (size_t)n * kCs * sizeof(double);
+  raise_lds_limit(reinterpret_cast<const void*>(chol_solve_kernel), lds_s, configured_s);
+  hipLaunchKernelGGL(chol_solve_kernel, dim3((nrhs + kSw - 1) / kSw, (unsigned)npairs), dim3(1024), lds_s, s, a_dev, lda, n, work_dev,
+                     b_dev, ldb, nrhs, dinv_in_lds, pair_a, pair_w, pair_b CHOL_STAMP_ARG);
+  HSR_LAUNCH_CHECK("chol kernels");
+  return HSR_OK;
+}
+
 extern "C" int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double* b_dev, int64_t ldb, int32_t nrhs,
                                   double* work_dev, int32_t* info_dev, hsr_stream_t stream) {
   using namespace hsr;
@@ -813,22 +852,19 @@ extern "C" int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double*
   HSR_REQUIRE(n >= kCb && n <= 512 && n % kCb == 0, HSR_ERR_UNSUPPORTED,
               "hsr_chol_solve_f64: n=%d must be a multiple of 32 in [32, 512] (pad with an identity block)", n);
   HSR_REQUIRE(lda >= n && nrhs >= 1 && ldb >= nrhs, HSR_ERR_INVALID, "hsr_chol_solve_f64: bad leading dimension");
-  hipStream_t s = (hipStream_t)stream;
-  const size_t lds_f = ((size_t)kCb + (size_t)(n - kCb)) * kCs * sizeof(double);
-  static thread_local size_t configured = 0, configured_r = 0, configured_s = 0;
-  raise_lds_limit(reinterpret_cast<const void*>(chol_factor_kernel), lds_f, configured);
-  if (n <= kResMaxN) {
-    const size_t lds_r = (size_t)(2 * n - kCb) * kDs * sizeof(double);   // two (D | P) buffers of n and n - 32 rows of 34 doubles
-    raise_lds_limit(reinterpret_cast<const void*>(chol_factor_res_kernel), lds_r, configured_r);
-    hipLaunchKernelGGL(chol_factor_res_kernel, dim3(1), dim3(kResThreads), lds_r, s, a_dev, lda, n, info_dev, work_dev CHOL_STAMP_ARG);
-  } else {
-    hipLaunchKernelGGL(chol_factor_kernel, dim3(1), dim3(1024), lds_f, s, a_dev, lda, n, info_dev, work_dev CHOL_STAMP_ARG);
-  }
-  size_t lds_s = ((size_t)n + kCb) * kYs * sizeof(double);
-  const int dinv_in_lds = lds_s + (size_t)n * kCs * sizeof(double) <= 160 * 1024 ? 1 : 0;
-  if (dinv_in_lds) lds_s += (size_t)n * kCs * sizeof(double);
-  raise_lds_limit(reinterpret_cast<const void*>(chol_solve_kernel), lds_s, configured_s);
-  hipLaunchKernelGGL(chol_solve_kernel, dim3((nrhs + kSw - 1) / kSw), dim3(1024), lds_s, s, a_dev, lda, n, work_dev, b_dev, ldb, nrhs, dinv_in_lds CHOL_STAMP_ARG);
-  HSR_LAUNCH_CHECK("chol kernels");
-  return HSR_OK;
+  return chol_launch(a_dev, lda, n, 0, b_dev, ldb, nrhs, 0, work_dev, info_dev, 1, (hipStream_t)stream);
+}
+
+extern "C" int hsr_chol_solve_f64_batched(double* a_dev, int64_t lda, int32_t n, int64_t pair_a, double* b_dev, int64_t ldb,
+                                          int32_t nrhs, int64_t pair_b, double* work_dev, int32_t* info_dev, int32_t npairs,
+                                          hsr_stream_t stream) {
+  using namespace hsr;
+  HSR_REQUIRE(a_dev && b_dev && work_dev && info_dev, HSR_ERR_INVALID, "hsr_chol_solve_f64_batched: NULL pointer");
+  HSR_REQUIRE(n >= kCb && n <= 512 && n % kCb == 0, HSR_ERR_UNSUPPORTED,
+              "hsr_chol_solve_f64_batched: n=%d must be a multiple of 32 in [32, 512] (pad with an identity block)", n);
+  HSR_REQUIRE(lda >= n && nrhs >= 1 && ldb >= nrhs && npairs >= 1 && npairs <= 65535, HSR_ERR_INVALID,
+              "hsr_chol_solve_f64_batched: bad leading dimension or pair count");
+  HSR_REQUIRE(npairs == 1 || (pair_a >= (int64_t)n * lda && pair_b >= (int64_t)n * ldb), HSR_ERR_INVALID,
+              "hsr_chol_solve_f64_batched: pair strides overlap");
+  return chol_launch(a_dev, lda, n, pair_a, b_dev, ldb, nrhs, pair_b, work_dev, info_dev, npairs, (hipStream_t)stream);
 }

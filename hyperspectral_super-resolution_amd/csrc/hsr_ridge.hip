@@ -79,6 +79,67 @@ __global__ __launch_bounds__(256) void expand_f64_kernel(const float* __restrict
   }
 }
 
+// Masked, batched form for tile pairs (hsr_pair_expand_f64): the inputs of a pair are band-major planes (x: n_in planes, y: T
+// planes of npix), the row of pixel r is [1 | monomials | 0 pad | logit(y) | 0 pad] when mask[r] is set, and ALL zero (the
+// constant column included) otherwise - so that the Gram over all npix rows is the Gram over the training pixels, with G[0][0]
+// their count.  The monomials are expand_f64_kernel's (same z, same product order); logit(clip(y, eps, 1 - eps)) in float64 from
+// the float32 reflectance.  blockIdx.y is the pair.
+struct PairExpandArgs {
+  const float* x;
+  const double* mean;
+  const double* scale;
+  const float* y;
+  const uint8_t* mask;
+  double* Q;
+  int64_t pair_x, pair_ms, pair_y, pair_m, pair_q;
+  int64_t npix, ldq;
+  int32_t n_in, nfeat, T, na;
+  double eps;
+  const uint8_t* table;
+};
+
+__global__ __launch_bounds__(256) void pair_expand_f64_kernel(const PairExpandArgs a) {
+  __shared__ double z[32][kMaxIn + 1];
+  __shared__ int ok[32];
+  const int64_t pr = blockIdx.y;
+  const float* x = a.x + pr * a.pair_x;
+  const double* mean = a.mean + pr * a.pair_ms;
+  const double* scale = a.scale + pr * a.pair_ms;
+  const float* y = a.y + pr * a.pair_y;
+  const uint8_t* mask = a.mask + pr * a.pair_m;
+  double* Q = a.Q + pr * a.pair_q;
+  const int64_t n = a.npix;
+  const int n_in = a.n_in;
+  const int64_t r0 = (int64_t)blockIdx.x * 32;
+  for (int i = threadIdx.x; i < 32 * (n_in + 1); i += 256) {
+    const int r = i / (n_in + 1), c = i % (n_in + 1);
+    double v = 1.0;
+    if (c < n_in && r0 + r < n) v = ((double)x[c * n + r0 + r] - mean[c]) / scale[c];
+    z[r][c] = v;
+  }
+  if (threadIdx.x < 32) ok[threadIdx.x] = r0 + threadIdx.x < n && mask[r0 + threadIdx.x] != 0;
+  __syncthreads();
+  const int ncols = (int)a.ldq;
+  for (int i = threadIdx.x; i < 32 * ncols; i += 256) {
+    const int r = i / ncols, c = i % ncols;
+    if (r0 + r >= n) continue;
+    double v = 0.0;
+    if (ok[r]) {
+      if (c == 0) {
+        v = 1.0;
+      } else if (c <= a.nfeat) {
+        const uint8_t* t = a.table + (size_t)(c - 1) * 4;
+        v = z[r][t[0]] * z[r][t[1]] * z[r][t[2]];
+      } else if (c >= a.na && c < a.na + a.T) {
+        double u = (double)y[(int64_t)(c - a.na) * n + r0 + r];
+        u = u < a.eps ? a.eps : (u > 1.0 - a.eps ? 1.0 - a.eps : u);
+        v = log(u / (1.0 - u));
+      }
+    }
+    Q[(r0 + r) * a.ldq + c] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // gram: C (na x nb) = A^T B over n rows, float64 MFMA 16x16x4, one wave per 16x16 tile and row chunk
 // ------------------------------------------------------------------------------------------------
@@ -245,6 +306,7 @@ struct GramCore {                     // scalars only: handed to the block routi
   int32_t narrow_col, narrow_width;  // first column and width of the narrow strip of B
   int32_t total, per_xcd;            // workgroups with work; ceil(total / 8)
   double* partials;                  // [chunk][tile][256]
+  int64_t pair_a, pair_p;            // batched form: element strides of A (== B) and of the partials between pairs (blockIdx.y)
 #ifdef HSR_GRAM_STAMPS
   unsigned long long* stamps;        // [workgroup][8] s_memrealtime at the phase boundaries (diagnostic builds only)
 #endif
@@ -632,7 +694,10 @@ __device__ __forceinline__ void gram_diag_block(const GramCore a, double* pan_ba
 // of A sit behind the same L2.
 __global__ __launch_bounds__(kGramThreads, kGramWgs) void gram_f64_lds_kernel(const GramLdsArgs args) {
   extern __shared__ __attribute__((aligned(16))) double pan[];   // kGramLdsDoubles
-  const GramCore a = args.c;
+  GramCore a = args.c;
+  a.A += blockIdx.y * a.pair_a;                   // pair of a batched launch (0 otherwise); the grid's x extent is a multiple
+  a.B += blockIdx.y * a.pair_a;                   // of 8, so the XCD of workgroup (x, y) is x % 8 as in a single launch
+  a.partials += blockIdx.y * a.pair_p;
   const int id = (int)(blockIdx.x % 8) * a.per_xcd + (int)(blockIdx.x / 8);
   if (id >= a.total) return;
   const int wide_ids = a.nwide * a.chunks_wide;
@@ -663,8 +728,11 @@ __global__ __launch_bounds__(kGramThreads, kGramWgs) void gram_f64_lds_kernel(co
 // have `chunks_narrow` chunks, tiles of diagonal blocks (edge `blk` tiles) `chunks_diag` when that is > 0.
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* __restrict__ partials, int ntiles, int chunks,
                                                           int tiles_j, int sym, int blk, int narrow_tj,
-                                                          int chunks_narrow, int chunks_diag, double* __restrict__ C, int64_t ldc) {
+                                                          int chunks_narrow, int chunks_diag, double* __restrict__ C, int64_t ldc,
+                                                          int64_t pair_p, int64_t pair_c) {
   const int tile = blockIdx.x, e = threadIdx.x;
+  partials += blockIdx.y * pair_p;                 // pair of a batched launch (0 otherwise)
+  C += blockIdx.y * pair_c;
   const int ti = tile / tiles_j, tj = tile % tiles_j;
   const bool mirror = sym && tj < ti;
   const int si = mirror ? tj : ti, sj = mirror ? ti : tj;           // the tile that was computed
@@ -707,7 +775,21 @@ struct PredArgs {
   float nodata;
   float* out;                  // (T, out_stride)
   int64_t out_stride;
+  int64_t pair_x, pair_mi, pair_w, pair_b, pair_out;   // batched form: element strides between the pairs (blockIdx.z)
 };
+
+// The operands of this workgroup's pair: a batched launch has one pair per grid z index and every workgroup stays on its pair,
+// so W is staged once per workgroup as in a single launch (z = 0, strides 0).
+__device__ __forceinline__ PredArgs pred_pair(PredArgs a) {
+  const int64_t z = blockIdx.z;
+  a.x += z * a.pair_x;
+  a.mean += z * a.pair_mi;
+  a.inv += z * a.pair_mi;
+  a.W += z * a.pair_w;
+  a.bias += z * a.pair_b;
+  a.out += z * a.pair_out;
+  return a;
+}
 
 // predict_cube_logit's rule for unusable pixels (Spectral_matching.ipynb raw lines 197-203): any input non-finite, or
 // close to the nodata value in torch.isclose's sense (|x - nd| <= 1e-8 + 1e-5 |nd|, equal infinities close, NaN never).
@@ -735,7 +817,8 @@ constexpr int kPredPix = 64;      // pixels per workgroup tile
 constexpr int kPredThreads = 256;
 
 template <int TT>   // number of 32-wide target tiles held by a wave (accumulators: TT * 16 VGPRs)
-__global__ __launch_bounds__(kPredThreads) void predict_kernel(const PredArgs a) {
+__global__ __launch_bounds__(kPredThreads) void predict_kernel(const PredArgs args) {
+  const PredArgs a = pred_pair(args);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int ldphi = a.kpad + 1;                      // odd row stride -> conflict-free column walks
   float* phi = reinterpret_cast<float*>(smem);       // [64][ldphi]
@@ -963,7 +1046,8 @@ __device__ __forceinline__ void mfma_steps_orb2(const float (&Z)[11], int kh, co
 // Shipped: level 1 from the start of the tile loop, 0 during each MFMA chain, back to 1 after it.
 constexpr int slice_waves(int tt) { return tt == 3 ? 12 : 16; }      // one workgroup per CU
 template <int TT>
-__global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) + 3) / 4) void predict103_slice_kernel(const PredArgs a, const int16_t* __restrict__ src_rows) {
+__global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) + 3) / 4) void predict103_slice_kernel(const PredArgs args, const int16_t* __restrict__ src_rows) {
+  const PredArgs a = pred_pair(args);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* wl = reinterpret_cast<float*>(smem);       // [2 * kStepsOrb2][Tp]: W's rows in orbit order (kOrb2)
   constexpr int Tp = TT * 32;
@@ -1060,7 +1144,8 @@ __global__ __launch_bounds__(64 * slice_waves(TT), (slice_waves(TT) + 3) / 4) vo
 // One 16-wave workgroup per CU, W staged once.  (Three such tiles for 33 <= T <= 48 were measured too: 82 x 6 MFMAs of 32 cycles are
 // no better than the 64-target slice's 143 x 2 of 64; those T keep the slice kernel.)
 constexpr int kX16Waves = 12, kX16Wgs = 2;     // 2 x 12 waves per CU = 6 per SIMD at <= 80 VGPRs (r04: 16 x 1: 0.132 ms per Mpixel)
-__global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel(const PredArgs a, const int16_t* __restrict__ src_rows) {
+__global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel(const PredArgs args, const int16_t* __restrict__ src_rows) {
+  const PredArgs a = pred_pair(args);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* wl = reinterpret_cast<float*>(smem);          // [4 * kStepsOrb][16]
   constexpr int kPix = 32 * kX16Waves;                 // pixels per workgroup tile: 32 per wave
@@ -1150,7 +1235,7 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
 // rows on the device and T <= 512 take the MFMA kernels above; every other shape takes the generic predict_kernel.
 typedef void (*PredOrbKernel)(PredArgs, const int16_t*);
 typedef void (*PredGenericKernel)(PredArgs);
-static int launch_predict(const PredArgs& a, int degree, hipStream_t s) {
+static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npairs = 1) {
   static thread_local size_t configured[7] = {};     // per kernel: x16, slice<1 / 2 / 3>, predict_kernel<1 / 2 / 4>
   PredOrbKernel orb = nullptr;
   PredGenericKernel generic = nullptr;
@@ -1202,9 +1287,12 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s) {
     slot = 4 + variant;
     kern = reinterpret_cast<const void*>(generic);
   }
+  // a batch shares the chip's workgroups among its pairs: fewer per pair, each walking more of its pair's tiles with W staged once
+  // (which workgroup computes a tile does not change its bits)
+  if (npairs > 1) gx = (gx + npairs - 1) / npairs;
   raise_lds_limit(kern, lds, configured[slot]);
-  if (orb) hipLaunchKernelGGL(orb, dim3(gx, slices), dim3(threads), lds, s, a, rows);
-  else hipLaunchKernelGGL(generic, dim3(gx), dim3(threads), lds, s, a);
+  if (orb) hipLaunchKernelGGL(orb, dim3(gx, slices, npairs), dim3(threads), lds, s, a, rows);
+  else hipLaunchKernelGGL(generic, dim3(gx, 1, npairs), dim3(threads), lds, s, a);
   return check_hip(hipGetLastError(), what);
 }
 
@@ -1278,6 +1366,25 @@ extern "C" int hsr_polyfeat_expand_f64(const float* x_dev, int64_t x_rs, int64_t
   hipLaunchKernelGGL(expand_f64_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, x_rs,
                      x_cs, mean_dev, scale_dev, n, n_in, g_table_nfeat, g_table_dev, p_dev, ldp, ncols);
   HSR_LAUNCH_CHECK("expand_f64_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const double* mean_dev, const double* scale_dev,
+                                   int64_t pair_ms, const float* y_dev, int64_t pair_y, const uint8_t* mask_dev, int64_t pair_m,
+                                   int64_t npix, int32_t n_in, int32_t degree, int32_t T, double eps, double* q_dev, int64_t ldq,
+                                   int64_t pair_q, int32_t na, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(x_dev && mean_dev && scale_dev && y_dev && mask_dev && q_dev && npix > 0 && T >= 1 && npairs >= 1 &&
+              npairs <= 65535, HSR_ERR_INVALID, "hsr_pair_expand_f64: bad argument");
+  HSR_REQUIRE(g_table_nin == n_in && g_table_deg == degree && g_table_dev, HSR_ERR_INVALID,
+              "hsr_pair_expand_f64: call hsr_polyfeat_prepare(%d, %d) first", n_in, degree);
+  HSR_REQUIRE(na >= g_table_nfeat + 1 && ldq >= (int64_t)na + T && ldq <= 4096, HSR_ERR_INVALID,
+              "hsr_pair_expand_f64: na=%d ldq=%lld T=%d (need na >= %d, ldq >= na + T)", na, (long long)ldq, T, g_table_nfeat + 1);
+  HSR_REQUIRE(npairs == 1 || pair_q >= npix * ldq, HSR_ERR_INVALID, "hsr_pair_expand_f64: pair stride of Q overlaps");
+  PairExpandArgs a{x_dev, mean_dev, scale_dev, y_dev, mask_dev, q_dev, pair_x, pair_ms, pair_y, pair_m, pair_q, npix, ldq,
+                   n_in, g_table_nfeat, T, na, eps, g_table_dev};
+  hipLaunchKernelGGL(pair_expand_f64_kernel, dim3((unsigned)((npix + 31) / 32), (unsigned)npairs), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  HSR_LAUNCH_CHECK("pair_expand_f64_kernel");
   return HSR_OK;
 }
 
@@ -1364,6 +1471,43 @@ extern "C" size_t hsr_gram_work_bytes(int32_t na, int32_t nb, int64_t n) {
   return (size_t)chunks * (na / 16) * (nb / 16) * 256 * sizeof(double);
 }
 
+// The LDS-panel Gram of `npairs` problems of one shape (A == B for the batched form): the pairs are the grid's y extent, with
+// per-pair element strides of A, of the partials and of C.  False when the panels cannot be loaded by DMA or the plan does not fit.
+static bool launch_gram_lds(const double* a_dev, int64_t lda, int32_t na, const double* b_dev, int64_t ldb, int32_t nb, int64_t n,
+                            int sym, double* work_dev, double* c_dev, int64_t ldc, int64_t pair_a, int64_t pair_p,
+                            int64_t pair_c, int32_t npairs, hipStream_t s) {
+  const bool dma_ok = (lda % 2 == 0) && (ldb % 2 == 0) && (((uintptr_t)a_dev | (uintptr_t)b_dev) & 15) == 0 &&
+                      (npairs == 1 || pair_a % 2 == 0);
+  GramLdsArgs g{};
+  if (!dma_ok || !gram_lds_plan(na, nb, sym, n, &g)) return false;
+  g.c.A = a_dev;
+  g.c.B = b_dev;
+  g.c.lda = lda;
+  g.c.ldb = ldb;
+  g.c.n = n;
+  g.c.na = na;
+  g.c.nb = nb;
+  g.c.tiles_i = na / 16;
+  g.c.tiles_j = nb / 16;
+  g.c.partials = work_dev;
+  g.c.pair_a = pair_a;
+  g.c.pair_p = pair_p;
+#ifdef HSR_GRAM_STAMPS
+  g.c.stamps = g_gram_stamps;
+#endif
+  static std::once_flag lds_once;
+  constexpr size_t lds_bytes = (size_t)kGramLdsDoubles * sizeof(double);
+  std::call_once(lds_once, [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gram_f64_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_bytes);
+  });
+  const int ti = na / 16, tj = nb / 16;
+  hipLaunchKernelGGL(gram_f64_lds_kernel, dim3(8 * (unsigned)g.c.per_xcd, (unsigned)npairs), dim3(kGramThreads), lds_bytes, s, g);
+  hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj, (unsigned)npairs), dim3(256), 0, s, work_dev, ti * tj, g.c.chunks_wide, tj,
+                     sym, kGpCols / 16, g.c.narrow_col / 16, g.c.chunks_narrow, g.c.chunks_diag, c_dev, ldc, pair_p, pair_c);
+  return true;
+}
+
 extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const double* b_dev, int64_t ldb,
                             int32_t nb, int64_t n, double* work_dev, double* c_dev, int64_t ldc,
                             hsr_stream_t stream) {
@@ -1375,33 +1519,8 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
   // result are symmetric, compute the upper block triangle only
   const int sym = (a_dev == b_dev && lda == ldb && nb >= na) ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  const bool dma_ok = (lda % 2 == 0) && (ldb % 2 == 0) && (((uintptr_t)a_dev | (uintptr_t)b_dev) & 15) == 0;
-  GramLdsArgs g{};
-  if (dma_ok && gram_lds_plan(na, nb, sym, n, &g)) {
-    g.c.A = a_dev;
-    g.c.B = b_dev;
-    g.c.lda = lda;
-    g.c.ldb = ldb;
-    g.c.n = n;
-    g.c.na = na;
-    g.c.nb = nb;
-    g.c.tiles_i = ti;
-    g.c.tiles_j = tj;
-    g.c.partials = work_dev;
-#ifdef HSR_GRAM_STAMPS
-    g.c.stamps = g_gram_stamps;
-#endif
-    static std::once_flag lds_once;
-    constexpr size_t lds_bytes = (size_t)kGramLdsDoubles * sizeof(double);
-    std::call_once(lds_once, [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gram_f64_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes);
-    });
-    hipLaunchKernelGGL(gram_f64_lds_kernel, dim3(8 * (unsigned)g.c.per_xcd), dim3(kGramThreads), lds_bytes, s, g);
+  if (launch_gram_lds(a_dev, lda, na, b_dev, ldb, nb, n, sym, work_dev, c_dev, ldc, 0, 0, 0, 1, s)) {
     HSR_LAUNCH_CHECK("gram_f64_lds_kernel");
-    hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj), dim3(256), 0, s, work_dev, ti * tj, g.c.chunks_wide, tj, sym,
-                       kGpCols / 16, g.c.narrow_col / 16, g.c.chunks_narrow, g.c.chunks_diag, c_dev, ldc);
-    HSR_LAUNCH_CHECK("gram_reduce_kernel");
     return HSR_OK;
   }
   int64_t rows = 0;
@@ -1410,8 +1529,26 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
   hipLaunchKernelGGL(gram_f64_kernel, dim3(((ti + R - 1) / R) * ((tj + R - 1) / R), (unsigned)chunks), dim3(256), 0, s,
                      a_dev, lda, ti, b_dev, ldb, tj, n, rows, sym, work_dev);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj), dim3(256), 0, s, work_dev, ti * tj, (int)chunks, tj, sym, R, tj,
-                     (int)chunks, 0, c_dev, ldc);
+                     (int)chunks, 0, c_dev, ldc, (int64_t)0, (int64_t)0);
   HSR_LAUNCH_CHECK("gram_f64_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na, int32_t nb, int64_t n, int64_t pair_a,
+                                    double* work_dev, int64_t pair_work, double* c_dev, int64_t ldc, int64_t pair_c,
+                                    int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(a_dev && work_dev && c_dev && n > 0 && npairs >= 1 && npairs <= 65535, HSR_ERR_INVALID,
+              "hsr_gram_f64_batched: bad argument");
+  HSR_REQUIRE(na >= 16 && nb >= na && na % 16 == 0 && nb % 16 == 0 && lda >= nb && ldc >= nb, HSR_ERR_INVALID,
+              "hsr_gram_f64_batched: na=%d nb=%d must be multiples of 16 inside the leading dimensions", na, nb);
+  HSR_REQUIRE(npairs == 1 || (pair_a >= n * lda && pair_c >= (int64_t)na * ldc &&
+                              (size_t)pair_work * sizeof(double) >= hsr_gram_work_bytes(na, nb, n)),
+              HSR_ERR_INVALID, "hsr_gram_f64_batched: pair strides overlap");
+  // every pair takes the plan of a single launch of its shape: its chunks, and so its bits, do not depend on the batch
+  HSR_REQUIRE(launch_gram_lds(a_dev, lda, na, a_dev, lda, nb, n, 1, work_dev, c_dev, ldc, pair_a, pair_work, pair_c, npairs,
+                              (hipStream_t)stream),
+              HSR_ERR_UNSUPPORTED, "hsr_gram_f64_batched: needs 16-byte aligned rows of an even leading dimension");
+  HSR_LAUNCH_CHECK("gram_f64_lds_kernel (batched)");
   return HSR_OK;
 }
 
@@ -1501,16 +1638,24 @@ __global__ __launch_bounds__(1024) void ridge_stats_finish_kernel(const float* _
 // B = Phi_c^T (Y - ybar) padded with zero rows (the centred normal equations of Ridge(fit_intercept=True)):
 //   A_ij = G[1+i][1+j] - s_i s_j / cnt (+ alpha on the diagonal),  B_it = G[1+i][na+t] - s_i ybar_t,
 //   s = G[0][1..nf] (column sums), cnt = G[0][0], ybar_t = G[0][na+t] / cnt.   Also clears the Cholesky status word.
+// Batched form: blockIdx.y is the pair (G, A, Bm offset by their pair strides, one status word per pair), and a pair without a
+// single training row (cnt == 0) gets the identity system instead of 0 / 0, so that its factorisation stays finite.
 __global__ __launch_bounds__(256) void ridge_assemble_kernel(const double* __restrict__ G, int64_t ldg, int na, int nf, int T,
                                                              double alpha, double* __restrict__ A, int npad,
-                                                             double* __restrict__ Bm, int64_t ldb, int32_t* __restrict__ info) {
+                                                             double* __restrict__ Bm, int64_t ldb, int32_t* __restrict__ info,
+                                                             int64_t pair_g, int64_t pair_a, int64_t pair_b, int empty_identity) {
+  G += blockIdx.y * pair_g;
+  A += blockIdx.y * pair_a;
+  Bm += blockIdx.y * pair_b;
+  info += blockIdx.y;
   const double cnt = G[0];
+  const bool empty = empty_identity && cnt == 0.0;
   const int64_t total = (int64_t)npad * (npad + T);
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int i = (int)(e / (npad + T)), j = (int)(e % (npad + T));
     if (j < npad) {
       double v = i == j ? 1.0 : 0.0;
-      if (i < nf && j < nf) {
+      if (i < nf && j < nf && !empty) {
         v = G[(size_t)(1 + i) * ldg + 1 + j] - (G[1 + i] * G[1 + j]) / cnt;
         if (i == j) v += alpha;
       }
@@ -1518,7 +1663,7 @@ __global__ __launch_bounds__(256) void ridge_assemble_kernel(const double* __res
     } else {
       const int t = j - npad;
       double v = 0.0;
-      if (i < nf) v = G[(size_t)(1 + i) * ldg + na + t] - G[1 + i] * (G[na + t] / cnt);
+      if (i < nf && !empty) v = G[(size_t)(1 + i) * ldg + na + t] - G[1 + i] * (G[na + t] / cnt);
       Bm[(size_t)i * ldb + t] = v;
     }
   }
@@ -1529,15 +1674,34 @@ __global__ __launch_bounds__(256) void ridge_assemble_kernel(const double* __res
 // to kpad, mean and 1 / scale as float32: everything the predict kernels read.  A block owns 32 targets: s / cnt goes to
 // LDS once, eight thread groups take every eighth feature (coalesced over the targets), partial sums joined in group
 // order.  (First version: one thread per target walking all features with a division per step - 65 us for T = 32.)
+// Batched form: blockIdx.y is the pair, every operand offset by its pair stride (FinishPairs); with `status` a pair's word
+// becomes 0 (fitted), 1 (no training row: NaN intercept, so that every prediction is NaN) or 2 (non-positive pivot).
+struct FinishPairs {
+  int64_t g, w, ms, b, w32, mi;      // element strides between pairs: G, Wm, mean / scale, b64 / b32, W32, mean32 / inv32
+  const int32_t* info;               // Cholesky status words, one per pair (batched form only)
+  int32_t* status;
+};
+
 __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restrict__ G, int na, int nf, int T,
                                                            const double* __restrict__ Wm, int64_t ldw, const double* __restrict__ mean,
                                                            const double* __restrict__ scale, int n_in, int kpad,
                                                            double* __restrict__ b64, float* __restrict__ b32,
                                                            float* __restrict__ W32, float* __restrict__ mean32,
-                                                           float* __restrict__ inv32) {
+                                                           float* __restrict__ inv32, const FinishPairs pp) {
   __shared__ double sc[kMaxFeat];
   __shared__ double part[8][32];
+  const int64_t pr = blockIdx.y;
+  G += pr * pp.g;
+  Wm += pr * pp.w;
+  mean += pr * pp.ms;
+  scale += pr * pp.ms;
+  b64 += pr * pp.b;
+  b32 += pr * pp.b;
+  W32 += pr * pp.w32;
+  mean32 += pr * pp.mi;
+  inv32 += pr * pp.mi;
   const double cnt = G[0];
+  if (pp.status && blockIdx.x == 0 && threadIdx.x == 0) pp.status[pr] = cnt == 0.0 ? 1 : (pp.info[pr] != 0 ? 2 : 0);
   const int tid = threadIdx.x;
   for (int f = tid; f < nf; f += 256) sc[f] = G[1 + f] / cnt;
   __syncthreads();
@@ -1552,7 +1716,7 @@ __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restr
     double a = part[0][tt];
 #pragma unroll
     for (int g = 1; g < 8; ++g) a += part[g][tt];
-    const double b = G[na + t] / cnt - a;
+    const double b = (pp.status && cnt == 0.0) ? __builtin_nan("") : G[na + t] / cnt - a;
     b64[t] = b;
     b32[t] = (float)b;
   }
@@ -1595,7 +1759,7 @@ extern "C" int hsr_ridge_assemble(const double* g_dev, int64_t ldg, int32_t na, 
   const int64_t total = (int64_t)npad * (npad + T);
   const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
   hipLaunchKernelGGL(ridge_assemble_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g_dev, ldg, na, nf, T, alpha, a_dev,
-                     npad, b_dev, ldb, info_dev);
+                     npad, b_dev, ldb, info_dev, (int64_t)0, (int64_t)0, (int64_t)0, 0);
   HSR_LAUNCH_CHECK("ridge_assemble_kernel");
   return HSR_OK;
 }
@@ -1613,8 +1777,46 @@ extern "C" int hsr_ridge_finish(const double* g_dev, int32_t na, int32_t nf, int
   const int64_t cpy = ((int64_t)kpad * T + 1023) / 1024;   // so there are at least enough blocks for 4 elements per thread
   if (cpy > grid) grid = (int)(cpy < 64 ? cpy : 64);
   hipLaunchKernelGGL(ridge_finish_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g_dev, na, nf, T, w_dev, ldw, mean_dev,
-                     scale_dev, n_in, kpad, b64_dev, b32_dev, w32_dev, mean32_dev, inv32_dev);
+                     scale_dev, n_in, kpad, b64_dev, b32_dev, w32_dev, mean32_dev, inv32_dev, FinishPairs{});
   HSR_LAUNCH_CHECK("ridge_finish_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_ridge_assemble_batched(const double* g_dev, int64_t ldg, int64_t pair_g, int32_t na, int32_t nf, int32_t T,
+                                          double alpha, double* a_dev, int32_t npad, int64_t pair_a, double* b_dev, int64_t ldb,
+                                          int64_t pair_b, int32_t* info_dev, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(g_dev && a_dev && b_dev && info_dev, HSR_ERR_INVALID, "hsr_ridge_assemble_batched: NULL pointer");
+  HSR_REQUIRE(nf >= 1 && na >= nf + 1 && npad >= nf && T >= 1 && ldg >= na + T && ldb >= T && npairs >= 1 && npairs <= 65535,
+              HSR_ERR_INVALID, "hsr_ridge_assemble_batched: bad shape (na=%d nf=%d npad=%d T=%d P=%d)", na, nf, npad, T, npairs);
+  HSR_REQUIRE(npairs == 1 || (pair_g >= (int64_t)na * ldg && pair_a >= (int64_t)npad * npad && pair_b >= (int64_t)npad * ldb),
+              HSR_ERR_INVALID, "hsr_ridge_assemble_batched: pair strides overlap");
+  const int64_t total = (int64_t)npad * (npad + T);
+  const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+  hipLaunchKernelGGL(ridge_assemble_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, (hipStream_t)stream, g_dev, ldg, na, nf, T,
+                     alpha, a_dev, npad, b_dev, ldb, info_dev, pair_g, pair_a, pair_b, 1);
+  HSR_LAUNCH_CHECK("ridge_assemble_kernel (batched)");
+  return HSR_OK;
+}
+
+extern "C" int hsr_ridge_finish_batched(const double* g_dev, int64_t pair_g, int32_t na, int32_t nf, int32_t T, const double* w_dev,
+                                        int64_t ldw, int64_t pair_w, const double* mean_dev, const double* scale_dev, int64_t pair_ms,
+                                        int32_t n_in, int32_t kpad, double* b64_dev, float* b32_dev, int64_t pair_b, float* w32_dev,
+                                        int64_t pair_w32, float* mean32_dev, float* inv32_dev, int64_t pair_mi,
+                                        const int32_t* info_dev, int32_t* status_dev, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(g_dev && w_dev && mean_dev && scale_dev && b64_dev && b32_dev && w32_dev && mean32_dev && inv32_dev && info_dev &&
+              status_dev, HSR_ERR_INVALID, "hsr_ridge_finish_batched: NULL pointer");
+  HSR_REQUIRE(nf >= 1 && na >= nf + 1 && T >= 1 && ldw >= T && kpad >= nf && n_in >= 1 && npairs >= 1 && npairs <= 65535,
+              HSR_ERR_INVALID, "hsr_ridge_finish_batched: bad shape");
+  HSR_REQUIRE(nf <= kMaxFeat, HSR_ERR_UNSUPPORTED, "hsr_ridge_finish_batched: nf=%d > %d", nf, kMaxFeat);
+  HSR_REQUIRE(npairs == 1 || (pair_b >= T && pair_w32 >= (int64_t)kpad * T && pair_mi >= n_in), HSR_ERR_INVALID,
+              "hsr_ridge_finish_batched: output pair strides overlap");
+  int grid = (T + 31) / 32;                       // the grid of a single launch, per pair
+  const int64_t cpy = ((int64_t)kpad * T + 1023) / 1024;
+  if (cpy > grid) grid = (int)(cpy < 64 ? cpy : 64);
+  const FinishPairs pp{pair_g, pair_w, pair_ms, pair_b, pair_w32, pair_mi, info_dev, status_dev};
+  hipLaunchKernelGGL(ridge_finish_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, (hipStream_t)stream, g_dev, na, nf, T, w_dev,
+                     ldw, mean_dev, scale_dev, n_in, kpad, b64_dev, b32_dev, w32_dev, mean32_dev, inv32_dev, pp);
+  HSR_LAUNCH_CHECK("ridge_finish_kernel (batched)");
   return HSR_OK;
 }
 
@@ -1659,4 +1861,48 @@ extern "C" int hsr_polyfeat_predict_cube(const float* x_dev, int64_t x_ps, int64
   a.out = out_dev;
   a.out_stride = out_stride;
   return launch_predict(a, degree, (hipStream_t)stream);
+}
+
+extern "C" int hsr_polyfeat_predict_cube_batched(const float* x_dev, int64_t x_ps, int64_t x_cs, int64_t pair_x,
+                                                 const float* mean_dev, const float* inv_scale_dev, int64_t pair_mi, int64_t npix,
+                                                 int32_t n_in, int32_t degree, const float* w_dev, int64_t ldw, int64_t pair_w,
+                                                 const float* bias_dev, int64_t pair_b, int32_t T, int32_t activation,
+                                                 int32_t nan_bad_pixels, float nodata, int32_t use_nodata, float* out_dev,
+                                                 int64_t out_stride, int64_t pair_out, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(x_dev && mean_dev && inv_scale_dev && w_dev && bias_dev && out_dev, HSR_ERR_INVALID,
+              "hsr_polyfeat_predict_cube_batched: NULL pointer");
+  HSR_REQUIRE(npix > 0 && T >= 1 && ldw >= T && out_stride >= npix && npairs >= 1 && npairs <= 65535, HSR_ERR_INVALID,
+              "hsr_polyfeat_predict_cube_batched: bad shape");
+  HSR_REQUIRE(npairs == 1 || pair_out >= (int64_t)T * out_stride, HSR_ERR_INVALID,
+              "hsr_polyfeat_predict_cube_batched: output pair stride %lld overlaps", (long long)pair_out);
+  HSR_REQUIRE(g_table_nin == n_in && g_table_deg == degree && g_table_dev, HSR_ERR_INVALID,
+              "hsr_polyfeat_predict_cube_batched: call hsr_polyfeat_prepare(%d, %d) first", n_in, degree);
+  PredArgs a{};
+  a.x = x_dev;
+  a.x_ps = x_ps;
+  a.x_cs = x_cs;
+  a.mean = mean_dev;
+  a.inv = inv_scale_dev;
+  a.npix = npix;
+  a.n_in = n_in;
+  a.nfeat = g_table_nfeat;
+  a.kpad = (g_table_nfeat + 1) & ~1;
+  a.table = g_table_dev;
+  a.W = w_dev;
+  a.ldw = ldw;
+  a.bias = bias_dev;
+  a.T = T;
+  a.ttiles = (T + 31) / 32;
+  a.act = activation;
+  a.nan_bad = nan_bad_pixels != 0;
+  a.use_nodata = use_nodata != 0;
+  a.nodata = nodata;
+  a.out = out_dev;
+  a.out_stride = out_stride;
+  a.pair_x = pair_x;
+  a.pair_mi = pair_mi;
+  a.pair_w = pair_w;
+  a.pair_b = pair_b;
+  a.pair_out = pair_out;
+  return launch_predict(a, degree, (hipStream_t)stream, npairs);
 }

@@ -156,6 +156,19 @@ SIGNATURES = {
     "hsr_ridge_finish": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hsr_polyfeat_predict_cube": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _i32,
                                             _i32, _f32, _i32, _vp, _i64, _vp]),
+    "hsr_pair_prep": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _i64, _i32, _i32, _i32, _i32, _f32, _i32, _f32,
+                                _i32, _vp, _vp, _vp, _i32, _vp]),
+    "hsr_pair_stats": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "hsr_pair_expand_f64": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f64, _vp, _i64,
+                                      _i64, _i32, _i32, _vp]),
+    "hsr_gram_f64_batched": (C.c_int, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+    "hsr_ridge_assemble_batched": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _f64, _vp, _i32, _i64, _vp, _i64, _i64, _vp, _i32,
+                                             _vp]),
+    "hsr_chol_solve_f64_batched": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp]),
+    "hsr_ridge_finish_batched": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp,
+                                           _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "hsr_polyfeat_predict_cube_batched": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp,
+                                                    _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _i64, _i32, _vp]),
     "hsr_block_mean": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample_mask_hist": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

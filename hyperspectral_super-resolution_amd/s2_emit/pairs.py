@@ -1,0 +1,278 @@
+"""Tile pairs -> the fused 10 m cube: the per-pair flow of legacy_notebooks/Spectral_matching.ipynb for a batch of pairs.
+
+One pair is what ``tiles_helpers/utils.py:223-395`` writes: an EMIT tile (285, h, w) - uint16 reflectance x 1e4 with nodata
+65535, or float32 reflectance - and an S2 tile (10, h f, w f).  The notebook reads the pair (raw lines 265-266), keeps 32
+evenly spaced EMIT bands (``subsample_bands_evenly``, :327), brings S2 to the EMIT grid (:377), drops unusable pixels
+(``flatten_pixels``, :410, def :108-126), fits ``StandardScaler -> PolynomialFeatures(3) -> Ridge(1.0)`` on
+``logit(clip(y, 1e-4, 1 - 1e-4))`` (:434, :475-490) and predicts the (32, h f, w f) cube with ``predict_cube_logit`` (:561).
+
+Here the whole flow of P pairs of one shape is a fixed number of launches on the current stream, whatever P is
+(csrc/hsr_pairs.hip, csrc/hsr_ridge.hip, csrc/hsr_chol.hip): pair prep (block mean, band gather and decode, training mask),
+masked scaler statistics, masked expand, Gram, assembly, P Cholesky factorisations side by side, model read-out and the
+10 m prediction.  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
+does not depend on the batch: ``fuse_tile_pairs`` of a batch gives the bits of ``fuse_tile_pair`` of each of its pairs.
+
+S2 -> EMIT grid: an f x f block mean (float64 sum of the f^2 samples, stored as float32: the bits of ``hsr_block_mean``);
+a coarse pixel whose block holds a non-finite or ``s2_nodata`` sample is NaN and so leaves the training set.  The
+notebook's GDAL bilinear ``reproject`` is NOT reproduced (rasterio is absent, that parity is unpinned); a caller who has
+S2 on the EMIT grid already (e.g. from GDAL) passes it as ``s2_coarse`` and reproduces the notebook exactly.
+"""
+from __future__ import annotations
+
+import operator
+from dataclasses import dataclass, field
+from typing import Any, Optional
+
+import numpy as np
+
+from . import _native as nat
+from ._engine import _ptr, _stream
+from .ridge import PolyRidge, subsample_bands_evenly
+
+_DTYPES = {"uint16": 2, "float32": 0}      # hsr_pair_prep's dtype codes
+
+
+def _is_torch(x) -> bool:
+    return type(x).__module__.startswith("torch")
+
+
+def _dtype_name(a) -> str:
+    return str(a.dtype).replace("torch.", "")
+
+
+def _describe(x, what: str, ndim: int):
+    """(batched shape, dtype name) of a cube or a batch of cubes: a (P, ...) array / tensor or a list of (...) ones."""
+    if isinstance(x, (list, tuple)):
+        if not x:
+            raise ValueError(f"{what}: empty list")
+        shapes = {tuple(e.shape) for e in x}
+        dts = {_dtype_name(e) for e in x}
+        if len(shapes) != 1 or len(dts) != 1:
+            raise ValueError(f"{what}: the pairs of a batch must share one shape and dtype, got {sorted(shapes)} {sorted(dts)}")
+        shape, dt = (len(x),) + shapes.pop(), dts.pop()
+    else:
+        shape, dt = tuple(x.shape), _dtype_name(x)
+    if len(shape) != ndim + 1:
+        raise ValueError(f"{what}: expected (P, {', '.join('abc'[:ndim])}) / a list of {ndim}-d cubes, got shape {shape}")
+    return shape, dt
+
+
+def _bands_index(bands, nbands: int) -> np.ndarray:
+    if isinstance(bands, str):
+        if bands != "all":
+            raise ValueError(f"bands={bands!r}: an int, an index array or 'all'")
+        return np.arange(nbands, dtype=np.int32)
+    if isinstance(bands, (bool, np.bool_)):
+        raise ValueError("bands: a bool is not a band count")
+    if isinstance(bands, (int, np.integer)):
+        if not 1 <= int(bands) <= nbands:
+            raise ValueError(f"bands={bands}: keep between 1 and {nbands} of the EMIT bands")
+        return subsample_bands_evenly(nbands, int(bands)).astype(np.int32)
+    idx = np.asarray(bands)
+    if idx.ndim != 1 or idx.size == 0 or idx.dtype.kind not in "iu":
+        raise ValueError(f"bands: a non-empty 1-d integer index array, got {idx.dtype} of shape {idx.shape}")
+    if idx.min() < 0 or idx.max() >= nbands:
+        raise ValueError(f"bands: indices must lie in [0, {nbands}), got [{idx.min()}, {idx.max()}]")
+    return idx.astype(np.int32)
+
+
+@dataclass
+class _Plan:
+    P: int
+    nbands: int
+    h: int
+    w: int
+    nb: int
+    factor: int
+    bands: np.ndarray
+    emit_dtype: str
+    s2_dtype: str
+
+
+def _plan(emits, s2s, bands, degree, factor, s2_coarse) -> _Plan:
+    """Every check that needs no GPU: shapes, dtypes, the factor and the bands."""
+    try:
+        f = operator.index(factor)
+    except TypeError:
+        raise ValueError(f"factor={factor!r}: the S2 / EMIT pixel ratio must be an integer") from None
+    if f < 1:
+        raise ValueError(f"factor={f}: must be >= 1")
+    if not 1 <= int(degree) <= 3:
+        raise ValueError(f"degree={degree}: 1, 2 or 3")
+    (P, B, h, w), edt = _describe(emits, "emit", 3)
+    (P2, nb, H, W), sdt = _describe(s2s, "s2", 3)
+    if P2 != P:
+        raise ValueError(f"{P} EMIT tiles but {P2} S2 tiles")
+    if edt not in _DTYPES or sdt not in _DTYPES:
+        raise ValueError(f"emit is {edt}, s2 is {sdt}: each must be uint16 or float32")
+    if (H, W) != (h * f, w * f):
+        raise ValueError(f"s2 is {H} x {W} but emit {h} x {w} at factor {f} needs {h * f} x {w * f}")
+    if not 1 <= nb <= nat.HSR_MAX_BANDS:
+        raise ValueError(f"s2 has {nb} bands: 1 .. {nat.HSR_MAX_BANDS} supported")
+    if s2_coarse is not None:
+        cshape, cdt = _describe(s2_coarse, "s2_coarse", 3)
+        if cshape != (P, nb, h, w) or cdt != "float32":
+            raise ValueError(f"s2_coarse: expected float32 {(P, nb, h, w)}, got {cdt} {cshape}")
+    return _Plan(P, B, h, w, nb, f, _bands_index(bands, B), edt, sdt)
+
+
+def _stack_dev(x, torch, dev):
+    """A (P, ...) contiguous device tensor from a batch tensor / array or a list of cubes (stacked ON the device; uint16 is
+    moved as int16 bits, which every torch operation supports)."""
+    def one(e):
+        if _is_torch(e):
+            return e
+        a = np.ascontiguousarray(e)
+        return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a)
+
+    if isinstance(x, (list, tuple)):
+        if all(not _is_torch(e) for e in x):                     # NumPy pairs: stacked on the host, copied once
+            return _stack_dev(np.stack([np.asarray(e) for e in x]), torch, dev)
+        parts = [one(e).to(dev) for e in x]
+        parts = [p.view(torch.int16) if p.dtype == torch.uint16 else p for p in parts]
+        out = torch.stack(parts)
+    else:
+        out = one(x).to(dev)
+        if out.dtype == torch.uint16:
+            out = out.view(torch.int16)
+    return out.contiguous()
+
+
+_BANDS_CACHE: dict = {}
+
+
+def _bands_dev(idx: np.ndarray, torch, dev):
+    key = (idx.tobytes(), str(dev))
+    t = _BANDS_CACHE.get(key)
+    if t is None:
+        t = _BANDS_CACHE[key] = torch.from_numpy(idx.copy()).to(dev)
+    return t
+
+
+@dataclass
+class TilePairOutput:
+    """What ``fuse_tile_pairs`` returns (device tensors, nothing copied to the host):
+
+    cube     (P, T, h f, w f) float32 = sigmoid(clip(model(S2 at 10 m), +-50)), NaN where predict_cube_logit leaves NaN (a
+             non-finite or ``s2_nodata`` input) and everywhere for a pair without training pixels;
+    n_train  (P,) int64, the pixels that survived the flatten rule;
+    status   (P,) int32: 0 fitted, 1 no training pixel (that pair's cube is all NaN), 2 non-positive Cholesky pivot;
+    mask     (P, h, w) bool, the training mask (flatten_pixels' rule on the EMIT grid);
+    s2_coarse (P, nb, h, w) float32, S2 on the EMIT grid as the fit saw it (the block mean, or the caller's ``s2_coarse``);
+    bands    (T,) the EMIT band indices of the targets.
+    ``model(i)`` is pair i's model as a ``PolyRidge`` (its host attributes are copied on first access)."""
+    cube: Any
+    n_train: Any
+    status: Any
+    mask: Any
+    s2_coarse: Any
+    bands: np.ndarray
+    degree: int
+    alpha: float
+    _fit: dict = field(repr=False, default_factory=dict)
+
+    def model(self, i: int) -> PolyRidge:
+        f = self._fit
+        m = PolyRidge(self.degree, self.alpha)
+        m.n_in, m.n_feat, m.n_targets = f["n_in"], f["nf"], len(self.bands)
+        m._fit64 = (f["mean"][i], f["scale"][i], f["Bp"][i, :f["nf"]], f["b64"][i])
+        m._dev = dict(W=f["W32"][i], b=f["b32"][i], mean=f["mean32"][i], inv=f["inv32"][i])
+        return m
+
+
+def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
+                    emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
+                    eps: float = 1e-4) -> TilePairOutput:
+    """P tile pairs -> their fused 10 m cubes (see the module docstring).
+
+    emits: (P, bands, h, w) uint16 (decoded as ``u == 65535 ? NaN : float32(u) * 1e-4f``) or float32 reflectance (with an
+    optional ``emit_nodata``, tested with the isclose rule); s2s: (P, nb, h f, w f) uint16 DN or float32 (optional
+    ``s2_nodata``).  Device tensors, NumPy arrays (copied once) or lists of per-pair cubes (stacked on the device).
+    bands: an int (evenly subsampled, ``subsample_bands_evenly``), an index array or ``"all"``."""
+    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse)
+    torch = nat.require_gpu()
+    lib = nat.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    P, nb, h, w, f = plan.P, plan.nb, plan.h, plan.w, plan.factor
+    T, npix, npix10 = len(plan.bands), h * w, h * w * f * f
+    E = _stack_dev(emits, torch, dev)
+    S = _stack_dev(s2s, torch, dev)
+    Sc = _stack_dev(s2_coarse, torch, dev) if s2_coarse is not None else None
+    st = _stream(torch)
+    nat.check(lib.hsr_polyfeat_prepare(nb, int(degree)), "hsr_polyfeat_prepare")
+    nf = lib.hsr_polyfeat_count(nb, int(degree))
+    na = (nf + 1 + 15) // 16 * 16                     # [1 | features] padded
+    ldq = na + (T + 15) // 16 * 16                    # ... | targets] padded
+    npad = (nf + 31) // 32 * 32
+    kpad = (nf + 1) // 2 * 2
+    f64 = dict(dtype=torch.float64, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+
+    # 1. pair prep: block mean, band gather / decode, training mask
+    x = torch.empty((P, nb, npix), **f32)
+    y = torch.empty((P, T, npix), **f32)
+    mask = torch.empty((P, npix), dtype=torch.uint8, device=dev)
+    src, src_dt, pair_s, fac = (Sc, 0, nb * npix, 0) if Sc is not None else (S, _DTYPES[plan.s2_dtype], S.stride(0), f)
+    nat.check(lib.hsr_pair_prep(_ptr(E), _DTYPES[plan.emit_dtype], E.stride(0), plan.nbands, _ptr(_bands_dev(plan.bands, torch, dev)),
+                                T, _ptr(src), src_dt, pair_s, nb, h, w, fac, 0.0 if emit_nodata is None else float(emit_nodata),
+                                0 if emit_nodata is None else 1, 0.0 if s2_nodata is None else float(s2_nodata),
+                                0 if s2_nodata is None else 1, _ptr(x), _ptr(y), _ptr(mask), P, st), "hsr_pair_prep")
+    # 2. StandardScaler over the training pixels
+    stats = torch.empty((P, 1 + 2 * nb), **f64)
+    mean = torch.empty((P, nb), **f64)
+    scale = torch.empty((P, nb), **f64)
+    n_train = torch.empty(P, dtype=torch.int64, device=dev)
+    nat.check(lib.hsr_pair_stats(_ptr(x), _ptr(mask), npix, nb, _ptr(stats), _ptr(mean), _ptr(scale), _ptr(n_train), P, st),
+              "hsr_pair_stats")
+    # 3. [1 | Phi | logit(y)] rows of the training pixels, zero rows for the others; 4. their Gram
+    Q = torch.empty((P, npix, ldq), **f64)
+    nat.check(lib.hsr_pair_expand_f64(_ptr(x), nb * npix, _ptr(mean), _ptr(scale), nb, _ptr(y), T * npix, _ptr(mask), npix, npix,
+                                      nb, int(degree), T, float(eps), _ptr(Q), ldq, npix * ldq, na, P, st), "hsr_pair_expand_f64")
+    wq = lib.hsr_gram_work_bytes(na, ldq, npix) // 8
+    work = torch.empty((P, wq), **f64)
+    G = torch.empty((P, na, ldq), **f64)
+    nat.check(lib.hsr_gram_f64_batched(_ptr(Q), ldq, na, ldq, npix, npix * ldq, _ptr(work), wq, _ptr(G), ldq, na * ldq, P, st),
+              "hsr_gram_f64_batched")
+    # 5. centred ridge systems, P Cholesky factorisations side by side, model read-out
+    Gp = torch.empty((P, npad, npad), **f64)
+    Bp = torch.empty((P, npad, T), **f64)
+    info = torch.empty(P, dtype=torch.int32, device=dev)
+    nat.check(lib.hsr_ridge_assemble_batched(_ptr(G), ldq, na * ldq, na, nf, T, float(alpha), _ptr(Gp), npad, npad * npad, _ptr(Bp),
+                                             T, npad * T, _ptr(info), P, st), "hsr_ridge_assemble_batched")
+    cw = lib.hsr_chol_work_bytes(npad) // 8
+    cwork = torch.empty((P, cw), **f64)
+    nat.check(lib.hsr_chol_solve_f64_batched(_ptr(Gp), npad, npad, npad * npad, _ptr(Bp), T, T, npad * T, _ptr(cwork), _ptr(info), P,
+                                             st), "hsr_chol_solve_f64_batched")
+    b64 = torch.empty((P, T), **f64)
+    W32 = torch.empty((P, kpad, T), **f32)
+    b32 = torch.empty((P, T), **f32)
+    mean32 = torch.empty((P, nb), **f32)
+    inv32 = torch.empty((P, nb), **f32)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    nat.check(lib.hsr_ridge_finish_batched(_ptr(G), na * ldq, na, nf, T, _ptr(Bp), T, npad * T, _ptr(mean), _ptr(scale), nb, nb, kpad,
+                                           _ptr(b64), _ptr(b32), T, _ptr(W32), kpad * T, _ptr(mean32), _ptr(inv32), nb, _ptr(info),
+                                           _ptr(status), P, st), "hsr_ridge_finish_batched")
+    # 6. the 10 m prediction: predict_cube_logit's rule for unusable pixels, per pair
+    if plan.s2_dtype == "uint16":                      # DN as float32 (exact), from the int16 bits
+        Xf = (S.to(torch.int32) & 0xFFFF).to(torch.float32)
+    else:
+        Xf = S
+    Xf = Xf.reshape(P, nb, npix10)
+    cube = torch.empty((P, T, npix10), **f32)
+    nat.check(lib.hsr_polyfeat_predict_cube_batched(_ptr(Xf), 1, npix10, nb * npix10, _ptr(mean32), _ptr(inv32), nb, npix10, nb,
+                                                    int(degree), _ptr(W32), T, kpad * T, _ptr(b32), T, T, 1, 1,
+                                                    0.0 if s2_nodata is None else float(s2_nodata), 0 if s2_nodata is None else 1,
+                                                    _ptr(cube), npix10, T * npix10, P, st), "hsr_polyfeat_predict_cube_batched")
+    fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
+    return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask.view(P, h, w).bool(),
+                          s2_coarse=x.view(P, nb, h, w), bands=plan.bands, degree=int(degree), alpha=float(alpha), _fit=fit)
+
+
+def fuse_tile_pair(emit, s2, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
+                   emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
+                   eps: float = 1e-4) -> TilePairOutput:
+    """One tile pair: emit (bands, h, w), s2 (nb, h f, w f) -> a TilePairOutput with P = 1 (``cube[0]`` is (T, h f, w f)).
+    The same launches as ``fuse_tile_pairs``, so a pair gives the same bits alone as in any batch."""
+    batch = lambda a: None if a is None else ([a] if not _is_torch(a) and not isinstance(a, np.ndarray) else a[None])
+    return fuse_tile_pairs(batch(emit), batch(s2), bands=bands, degree=degree, alpha=alpha, factor=factor,
+                           emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps)

@@ -488,6 +488,52 @@ int hsr_polyfeat_predict_cube(const float* x_dev, int64_t x_ps, int64_t x_cs, co
                               int32_t activation, int32_t nan_bad_pixels, float nodata, int32_t use_nodata,
                               float* out_dev, int64_t out_stride, hsr_stream_t stream);
 
+/* ---- tile pairs: the notebook's per-pair flow for a batch of P pairs of one shape (s2_emit.fuse_tile_pairs) -------------
+ * Spectral_matching.ipynb: read an EMIT (bands, H, W) / S2 (nb, H f, W f) pair, keep T EMIT bands, bring S2 to the EMIT grid,
+ * flatten_pixels, logit, fit StandardScaler -> PolynomialFeatures -> Ridge, predict_cube_logit at 10 m.  Every call below takes
+ * the pair count and per-pair element strides; a pair's arithmetic does not depend on the batch it is in.
+ * hsr_pair_prep: S2 -> x (P, nb, H W) f x f block mean (float64 sum, float32 store; NaN for a block holding a non-finite or
+ *   s2_nodata sample; factor 0: s2 is already the (P, nb, H, W) float32 coarse image), the T EMIT bands bands_dev[] -> y (P, T, H W)
+ *   (uint16: 65535 -> NaN, else u * 1e-4f) and mask (P, H W) = flatten_pixels' rule (all finite, none close to its nodata value).
+ *   dtypes: 0 float32, 2 uint16.  GDAL's bilinear reproject is not reproduced (parity unpinned).
+ * hsr_pair_stats: over the masked pixels: stats (P, 1 + 2 nb) = [n, mean.., M2..], mean / scale (P, nb) (StandardScaler's; no
+ *   training pixel: 0 / 1), n_train (P) int64.
+ * hsr_pair_expand_f64: Q (P, H W, ldq) rows [1 | monomials | 0 | logit(clip(y, eps, 1 - eps)) | 0] for masked pixels (targets from
+ *   column na), all-zero rows for the others, so that hsr_gram_f64_batched over all rows counts the training pixels in G[0][0].
+ * hsr_gram_f64_batched: C = A^T A[:, :nb] per pair (the symmetric Gram of hsr_gram_f64, its row-chunk plan per pair);
+ *   pair_work >= hsr_gram_work_bytes(na, nb, n) / 8.
+ * hsr_ridge_assemble_batched / hsr_ridge_finish_batched: hsr_ridge_assemble / hsr_ridge_finish per pair; a pair whose G[0][0] is 0
+ *   gets an identity system and a NaN intercept, and status (P) = 0 fitted, 1 no training pixel, 2 non-positive pivot.
+ * hsr_chol_solve_f64_batched: hsr_chol_solve_f64 per pair (one factorisation workgroup per system); work: P x hsr_chol_work_bytes.
+ * hsr_polyfeat_predict_cube_batched: hsr_polyfeat_predict_cube per pair. */
+int hsr_pair_prep(const void* emit_dev, int32_t emit_dtype, int64_t pair_emit, int32_t emit_bands, const int32_t* bands_dev,
+                  int32_t T, const void* s2_dev, int32_t s2_dtype, int64_t pair_s2, int32_t nb, int32_t H, int32_t W,
+                  int32_t factor, float emit_nodata, int32_t use_emit_nodata, float s2_nodata, int32_t use_s2_nodata,
+                  float* x_dev, float* y_dev, uint8_t* mask_dev, int32_t npairs, hsr_stream_t stream);
+int hsr_pair_stats(const float* x_dev, const uint8_t* mask_dev, int64_t npix, int32_t nb, double* stats_dev, double* mean_dev,
+                   double* scale_dev, int64_t* n_train_dev, int32_t npairs, hsr_stream_t stream);
+int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const double* mean_dev, const double* scale_dev, int64_t pair_ms,
+                        const float* y_dev, int64_t pair_y, const uint8_t* mask_dev, int64_t pair_m, int64_t npix, int32_t n_in,
+                        int32_t degree, int32_t T, double eps, double* q_dev, int64_t ldq, int64_t pair_q, int32_t na,
+                        int32_t npairs, hsr_stream_t stream);
+int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na, int32_t nb, int64_t n, int64_t pair_a, double* work_dev,
+                         int64_t pair_work, double* c_dev, int64_t ldc, int64_t pair_c, int32_t npairs, hsr_stream_t stream);
+int hsr_ridge_assemble_batched(const double* g_dev, int64_t ldg, int64_t pair_g, int32_t na, int32_t nf, int32_t T, double alpha,
+                               double* a_dev, int32_t npad, int64_t pair_a, double* b_dev, int64_t ldb, int64_t pair_b,
+                               int32_t* info_dev, int32_t npairs, hsr_stream_t stream);
+int hsr_chol_solve_f64_batched(double* a_dev, int64_t lda, int32_t n, int64_t pair_a, double* b_dev, int64_t ldb, int32_t nrhs,
+                               int64_t pair_b, double* work_dev, int32_t* info_dev, int32_t npairs, hsr_stream_t stream);
+int hsr_ridge_finish_batched(const double* g_dev, int64_t pair_g, int32_t na, int32_t nf, int32_t T, const double* w_dev,
+                             int64_t ldw, int64_t pair_w, const double* mean_dev, const double* scale_dev, int64_t pair_ms,
+                             int32_t n_in, int32_t kpad, double* b64_dev, float* b32_dev, int64_t pair_b, float* w32_dev,
+                             int64_t pair_w32, float* mean32_dev, float* inv32_dev, int64_t pair_mi, const int32_t* info_dev,
+                             int32_t* status_dev, int32_t npairs, hsr_stream_t stream);
+int hsr_polyfeat_predict_cube_batched(const float* x_dev, int64_t x_ps, int64_t x_cs, int64_t pair_x, const float* mean_dev,
+                                      const float* inv_scale_dev, int64_t pair_mi, int64_t npix, int32_t n_in, int32_t degree,
+                                      const float* w_dev, int64_t ldw, int64_t pair_w, const float* bias_dev, int64_t pair_b,
+                                      int32_t T, int32_t activation, int32_t nan_bad_pixels, float nodata, int32_t use_nodata,
+                                      float* out_dev, int64_t out_stride, int64_t pair_out, int32_t npairs, hsr_stream_t stream);
+
 /* ---- f1: grid-aligned resamplers between the phases -----------------------------------------------
  * downsample_s2_to_grid ('average') and reproject_stack_to_grid ('bilinear') of the notebook
  * (Pairs_EMIT_S2_demo-2.ipynb cell 73, raw lines 4538-4599) for exactly aligned integer-factor grids:

@@ -1,0 +1,181 @@
+"""Benchmark of s2_emit.fuse_tile_pairs (tile pairs -> fused 10 m cubes) at the notebook's shape.
+
+    python tools/bench_tile_pairs.py                       # every configuration, each in a fresh process
+    python tools/bench_tile_pairs.py --profile DIR         # the same under rocprofv3 --kernel-trace --stats (kernel times)
+
+Configurations: P = 1, 8, 64 pairs at T = 32 targets, and P = 64 at T = 285 (EMIT 285 x 100 x 100 uint16, S2 10 x 600 x 600
+uint16, factor 6).  One JSON line per configuration:
+  ms_per_pair         the batch (fuse_tile_pairs) over device events after warm-up, divided by P;
+  loop_ms_per_pair    fuse_tile_pair called once per pair in a loop, same process, same events;
+  host_ms_per_pair    today's host-driven chain for one pair: D2H, NumPy block mean / flatten_pixels / logit, PolyRidge.fit,
+                      predict_cube (wall clock, synchronised; up to 4 pairs);
+  ratio               ms_per_pair / loop_ms_per_pair;
+and with --profile, from the kernel trace: launches_per_batch, the Gram's float64 and the predict's float32 FLOP rates over
+their kernel time, and the per-kernel share of a batch.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CONFIGS = [(1, 32), (8, 32), (64, 32), (64, 285)]
+
+
+def _pairs(torch, P, seed=0):
+    """P synthetic pairs on the device: S2 DN from three sources, EMIT reflectance correlated with them (uint16 x 1e4)."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    ab = torch.rand((P, 3, 100, 100), generator=g, device="cuda")
+    spec = 0.05 + 0.4 * torch.rand((3, 285), generator=g, device="cuda")
+    resp = 600 + 2200 * torch.rand((3, 10), generator=g, device="cuda")
+    emit = (1e4 * torch.einsum("pkij,kb->pbij", ab, spec)).round().clamp(1, 9000).to(torch.int32)
+    coarse = torch.einsum("pkij,kc->pcij", ab, resp)
+    fine = coarse.repeat_interleave(6, dim=2).repeat_interleave(6, dim=3)
+    s2 = (fine + 20 * torch.rand(fine.shape, generator=g, device="cuda")).round().clamp(1, 10000).to(torch.int32)
+    return emit.to(torch.int16).view(torch.uint16), s2.to(torch.int16).view(torch.uint16)
+
+
+def _host_chain(torch, s2_emit, E, S, bands):
+    """The chain a caller runs today for one pair (wall clock, synchronised)."""
+    import numpy as np
+    t0 = time.perf_counter()
+    e = (E.view(torch.int16).to(torch.int32) & 0xFFFF).cpu().numpy()
+    s = (S.view(torch.int16).to(torch.int32) & 0xFFFF).cpu().numpy()
+    X = s.astype(np.float64).reshape(10, 100, 6, 100, 6).sum(axis=(2, 4)) / 36.0
+    X = np.where((s == 0).reshape(10, 100, 6, 100, 6).any(axis=(2, 4)), np.nan, X).astype(np.float32)
+    Y = np.where(e[bands] == 65535, np.float32(np.nan), e[bands].astype(np.float32) * np.float32(1e-4))
+    Xtr, Ytr = s2_emit.flatten_pixels(X, Y, x_nodata=0.0)
+    Yl = s2_emit.ridge.logit(Ytr.astype(np.float64))
+    m = s2_emit.PolyRidge(3, 1.0).fit(torch.from_numpy(Xtr).cuda(), torch.from_numpy(Yl).cuda())
+    cube = m.predict_cube(torch.from_numpy(s.astype(np.float32)).cuda(), nodata=0.0)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, cube
+
+
+def child(P, T, iters, warmup, host_pairs):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
+    import torch
+    import s2_emit
+    bands = 32 if T == 32 else "all"
+    E, S = _pairs(torch, P)
+    kw = dict(bands=bands, s2_nodata=0.0)
+    for _ in range(warmup):
+        s2_emit.fuse_tile_pairs(E, S, **kw)
+        for i in range(P):
+            s2_emit.fuse_tile_pair(E[i], S[i], **kw)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    batch_ms, loop_ms = [], []
+    for _ in range(iters):
+        ev[0].record()
+        out = s2_emit.fuse_tile_pairs(E, S, **kw)
+        ev[1].record()
+        for i in range(P):
+            s2_emit.fuse_tile_pair(E[i], S[i], **kw)
+        ev[2].record()
+        torch.cuda.synchronize()
+        batch_ms.append(ev[0].elapsed_time(ev[1]))
+        loop_ms.append(ev[1].elapsed_time(ev[2]))
+        del out
+    host = []
+    if host_pairs:
+        idx = s2_emit.subsample_bands_evenly(285, 32) if T == 32 else list(range(285))
+        _host_chain(torch, s2_emit, E[0], S[0], idx)                      # warm-up
+        for i in range(min(host_pairs, P)):
+            host.append(_host_chain(torch, s2_emit, E[i], S[i], idx)[0])
+    bm, lm = sorted(batch_ms)[len(batch_ms) // 2], sorted(loop_ms)[len(loop_ms) // 2]
+    rec = dict(P=P, T=T, iters=iters, ms_per_batch=round(bm, 4), ms_per_pair=round(bm / P, 4),
+               loop_ms_per_pair=round(lm / P, 4), ratio=round(bm / lm, 3))
+    if host:
+        rec["host_ms_per_pair"] = round(sorted(host)[len(host) // 2], 3)
+    print(json.dumps(rec), flush=True)
+
+
+def _kernel_stats(out_dir):
+    rows = []
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as fh:
+            rows += list(csv.DictReader(fh))
+    return rows
+
+
+def profile_one(P, T, iters, out_dir):
+    """One configuration under rocprofv3, twice (1 and 1 + iters batches after the input generation): the difference of the two
+    traces is `iters` batches alone - launches per batch, kernel time per batch, and the Gram / predict FLOP rates over it."""
+    def run(n):
+        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}")
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
+               os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"]
+        subprocess.run(cmd, check=True, cwd=ROOT)
+        per = {}
+        for r in _kernel_stats(d):
+            c, t = per.get(r["Name"], (0, 0.0))
+            per[r["Name"]] = (c + int(r["Calls"]), t + float(r["TotalDurationNs"]))
+        for path in glob.glob(os.path.join(d, "**", "*"), recursive=True):     # keep the stats, drop the full trace
+            if os.path.isfile(path) and not path.endswith("kernel_stats.csv"):
+                os.remove(path)
+        return per
+    a, b = run(1), run(1 + iters)
+    diff = {k: (b[k][0] - a.get(k, (0, 0.0))[0], b[k][1] - a.get(k, (0, 0.0))[1]) for k in b}
+    diff = {k: v for k, v in diff.items() if v[0] > 0}
+    calls = sum(v[0] for v in diff.values())
+    nf, na = 285, 288
+    ldq = na + (T + 15) // 16 * 16
+    npix, npix10 = 100 * 100, 600 * 600
+
+    def ns(pred):
+        return sum(v[1] for k, v in diff.items() if pred(k)) / iters
+    gram_ns = ns(lambda n: "gram_f64_lds_kernel" in n)
+    pred_ns = ns(lambda n: "predict" in n)
+    total_ns = ns(lambda n: True)
+    rec = dict(P=P, T=T, launches_per_batch=calls / iters, kernel_ms_per_batch=round(total_ns / 1e6, 4),
+               kernel_ms_per_pair=round(total_ns / 1e6 / P, 4),
+               gram_tflops_f64=round(2.0 * npix * na * ldq * P / gram_ns / 1e3, 2) if gram_ns else None,
+               predict_tflops_f32=round(2.0 * npix10 * nf * T * P / pred_ns / 1e3, 2) if pred_ns else None,
+               kernel_us_per_batch={k.split("(")[0][-60:]: round(v[1] / iters / 1e3, 1) for k, v in sorted(diff.items(), key=lambda kv: -kv[1][1])})
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", default=None, help="P,T: run one configuration in this process")
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--host-pairs", type=int, default=4)
+    ap.add_argument("--batch-only", action="store_true", help="(profiling) time the batch only, no per-pair loop")
+    ap.add_argument("--profile", default=None, help="directory for rocprofv3 output: profile every configuration")
+    ap.add_argument("--configs", default=None, help="P,T;P,T... (default: all)")
+    a = ap.parse_args()
+    if a.child:
+        P, T = map(int, a.child.split(","))
+        if a.batch_only:
+            sys.path.insert(0, ROOT)
+            sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
+            import torch
+            import s2_emit
+            E, S = _pairs(torch, P)
+            for _ in range(a.iters):
+                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0)
+            torch.cuda.synchronize()
+            return
+        child(P, T, a.iters, a.warmup, a.host_pairs)
+        return
+    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else CONFIGS
+    for P, T in configs:
+        if a.profile:
+            profile_one(P, T, a.iters, a.profile)
+        else:
+            iters = a.iters if P * T < 64 * 285 else max(2, a.iters // 2)
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(iters),
+                            "--warmup", str(a.warmup), "--host-pairs", str(a.host_pairs)], check=True)
+
+
+if __name__ == "__main__":
+    main()
