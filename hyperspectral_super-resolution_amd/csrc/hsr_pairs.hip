@@ -133,6 +133,167 @@ __global__ __launch_bounds__(kPairStatsThreads) void pair_stats_kernel(const flo
   }
 }
 
+// Fit report (fuse_tile_pairs(report=True)): the notebook's cell 26 - predict the training pixels with the fitted model, sigmoid,
+// per-band R^2 and RMSE against the decoded targets - on the expanded rows Q the fit has just read.  Columns 0 .. na-1 of a row of
+// Q are [1 | phi | 0] (all zero for an untrained pixel), so the in-sample logit is Q[:, :na] . [b64; Bp[:nf]; 0], a
+// (npix x na) . (na x T) product per pair on v_mfma_f64_16x16x4_f64; the cast, sigmoid, residual and masking run in the MFMA
+// epilogue, in registers.
+//   partial  grid (chunks, ceil(T / 32), P): a workgroup owns kRepRows rows (a plan that depends on npix only) and 32 bands;
+//            each wave 4 strips of 16 rows x 2 band tiles.  The coefficient panel is staged in LDS kRepKc features at a time.
+//            k order: MFMA step u of k-tile kt contracts features kt + 4 kk + u (kk = lane >> 4), so a lane reads 4
+//            consecutive doubles of its row as two 16-byte loads and takes the coefficients of the same 4 features.
+//            Per (pair, chunk, band) partial: [sum d^2, n, mean(yt), M2(yt)], every lane in a fixed order, lanes and waves
+//            joined in a fixed order (Chan's merge).
+//   finish   one workgroup per pair: the chunks merged in index order; r2 = 1 - ss_res / (M2 + 1e-8), rmse = sqrt(ss_res / n),
+//            NaN for a pair whose status is not 0.
+// A pair's numbers therefore depend on neither the batch size nor its position in the batch.
+constexpr int kRepRows = 256;          // rows per chunk: 4 waves x 4 strips x 16
+constexpr int kRepKc = 96;             // features per LDS coefficient panel (6 k-tiles)
+constexpr int kRepLd = 36;             // panel row pitch in doubles: the kk = 0 / 1 halves of a wave read disjoint banks
+
+typedef double rep_f64x4 __attribute__((ext_vector_type(4)));
+
+struct PairReportArgs {
+  const double* q;                     // (P, npix, ldq): [1 | phi | 0-pad] in columns 0 .. na-1
+  const double* b64;                   // (P, T) intercepts
+  const double* bp;                    // (P, >= nf, ldbp) coefficients on phi
+  const float* y;                      // (P, T, npix) decoded targets
+  const uint8_t* mask;                 // (P, npix) training mask
+  double* work;                        // (P, pair_work): [chunk][T][4]
+  int64_t ldq, pair_q, pair_b, ldbp, pair_bp, pair_y, pair_m, pair_work, npix;
+  int32_t na, nf, T;
+};
+
+struct RepStat {
+  double sd, n, mu, m2;
+};
+
+__device__ __forceinline__ RepStat rep_merge(RepStat a, RepStat b) {   // Chan et al.: a then b
+  if (b.n == 0.0) {
+    a.sd += b.sd;
+    return a;
+  }
+  if (a.n == 0.0) {
+    b.sd += a.sd;
+    return b;
+  }
+  const double n = a.n + b.n, delta = b.mu - a.mu;
+  return RepStat{a.sd + b.sd, n, a.mu + delta * (b.n / n), a.m2 + b.m2 + delta * delta * (a.n * b.n / n)};
+}
+
+__global__ __launch_bounds__(256) void pair_report_partial_kernel(const PairReportArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[kRepKc * kRepLd];
+  const int64_t pr = blockIdx.z;
+  const int chunk = blockIdx.x, j0 = blockIdx.y * 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, kk = lane >> 4;
+  const double* q = a.q + pr * a.pair_q;
+  const double* b64 = a.b64 + pr * a.pair_b;
+  const double* bp = a.bp + pr * a.pair_bp;
+  const int64_t row_w = (int64_t)chunk * kRepRows + wave * 64;
+  // A operand row of this lane in strip s: row_w + 16 s + c (clamped to row 0 past the end: its results are never used)
+  const double* qrow[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int64_t r = row_w + 16 * s + c;
+    qrow[s] = q + (r < a.npix ? r : 0) * a.ldq + 4 * kk;
+  }
+  rep_f64x4 acc[4][2];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[s][b] = rep_f64x4{0.0, 0.0, 0.0, 0.0};
+  for (int k0 = 0; k0 < a.na; k0 += kRepKc) {
+    const int kc = min(kRepKc, a.na - k0);
+    __syncthreads();                                   // the previous panel is consumed
+    for (int e = threadIdx.x; e < kc * 32; e += 256) {
+      const int kr = e >> 5, jb = e & 31, k = k0 + kr, j = j0 + jb;
+      double v = 0.0;
+      if (j < a.T) v = k == 0 ? b64[j] : (k <= a.nf ? bp[(int64_t)(k - 1) * a.ldbp + j] : 0.0);
+      lds[kr * kRepLd + jb] = v;
+    }
+    __syncthreads();
+    for (int kt = 0; kt < kc; kt += 16) {
+      double2 qa[4][2];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const double2* p = reinterpret_cast<const double2*>(qrow[s] + k0 + kt);
+        qa[s][0] = p[0];
+        qa[s][1] = p[1];
+      }
+      const double* pan = lds + (kt + 4 * kk) * kRepLd + c;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double b0 = pan[u * kRepLd], b1 = pan[u * kRepLd + 16];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const double av = u == 0 ? qa[s][0].x : u == 1 ? qa[s][0].y : u == 2 ? qa[s][1].x : qa[s][1].y;
+          acc[s][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b0, acc[s][0], 0, 0, 0);
+          acc[s][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b1, acc[s][1], 0, 0, 0);
+        }
+      }
+    }
+  }
+  // epilogue: D[row = kk + 4 g][col = c] (the f64 map) = pixel row_w + 16 s + kk + 4 g, band j0 + 16 b + c
+  const float* y = a.y + pr * a.pair_y;
+  const uint8_t* mask = a.mask + pr * a.pair_m;
+  RepStat st[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int64_t pix = row_w + 16 * s + kk + 4 * g;
+      if (pix >= a.npix || !mask[pix]) continue;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int j = j0 + 16 * b + c;
+        if (j >= a.T) continue;
+        const float z = (float)acc[s][b][g];
+        const float zc = z < -50.0f ? -50.0f : (z > 50.0f ? 50.0f : z);   // np.clip: NaN stays NaN
+        const float yp = 1.0f / (1.0f + expf(-zc));
+        const float yt = y[(int64_t)j * a.npix + pix];
+        const float d = yt - yp;
+        RepStat& r = st[b];
+        r.sd += (double)d * (double)d;
+        r.n += 1.0;
+        const double delta = (double)yt - r.mu;
+        r.mu += delta / r.n;
+        r.m2 += delta * ((double)yt - r.mu);
+      }
+    }
+  __syncthreads();                                     // the panel is free: it holds the 16 lane sets of 32 bands now
+  RepStat* red = reinterpret_cast<RepStat*>(lds);      // [wave * 4 + kk][32]
+#pragma unroll
+  for (int b = 0; b < 2; ++b) red[(wave * 4 + kk) * 32 + 16 * b + c] = st[b];
+  __syncthreads();
+  if (threadIdx.x < 32 && j0 + (int)threadIdx.x < a.T) {
+    RepStat r = red[threadIdx.x];
+    for (int i = 1; i < 16; ++i) r = rep_merge(r, red[i * 32 + threadIdx.x]);
+    double* out = a.work + pr * a.pair_work + ((int64_t)chunk * a.T + j0 + threadIdx.x) * 4;
+    out[0] = r.sd;
+    out[1] = r.n;
+    out[2] = r.mu;
+    out[3] = r.m2;
+  }
+}
+
+__global__ __launch_bounds__(256) void pair_report_finish_kernel(const double* __restrict__ work, int64_t pair_work, int chunks,
+                                                                 int T, const int32_t* __restrict__ status, double* __restrict__ r2,
+                                                                 double* __restrict__ rmse, int64_t pair_out) {
+  const int64_t pr = blockIdx.x;
+  work += pr * pair_work;
+  const bool ok = status[pr] == 0;
+  for (int j = threadIdx.x; j < T; j += 256) {
+    RepStat r{0.0, 0.0, 0.0, 0.0};
+    for (int ch = 0; ch < chunks; ++ch) {
+      const double* p = work + ((int64_t)ch * T + j) * 4;
+      r = rep_merge(r, RepStat{p[0], p[1], p[2], p[3]});
+    }
+    const double nan = __builtin_nan("");
+    r2[pr * pair_out + j] = ok ? 1.0 - r.sd / (r.m2 + 1e-8) : nan;
+    rmse[pr * pair_out + j] = ok ? sqrt(r.sd / r.n) : nan;
+  }
+}
+
 }  // namespace hsr
 
 using namespace hsr;
@@ -170,5 +331,40 @@ extern "C" int hsr_pair_stats(const float* x_dev, const uint8_t* mask_dev, int64
   hipLaunchKernelGGL(pair_stats_kernel, dim3((unsigned)npairs), dim3(kPairStatsThreads), 0, (hipStream_t)stream, x_dev, mask_dev,
                      npix, nb, stats_dev, mean_dev, scale_dev, n_train_dev);
   HSR_LAUNCH_CHECK("pair_stats_kernel");
+  return HSR_OK;
+}
+
+extern "C" size_t hsr_pair_report_work_bytes(int64_t npix, int32_t T) {
+  if (npix < 1 || T < 1) return 0;
+  return (size_t)((npix + kRepRows - 1) / kRepRows) * (size_t)T * 4 * sizeof(double);
+}
+
+extern "C" int hsr_pair_report_f64(const double* q_dev, int64_t ldq, int64_t pair_q, int32_t na, int64_t npix, const double* b64_dev,
+                                   int64_t pair_b, const double* bp_dev, int64_t ldbp, int64_t pair_bp, int32_t nf,
+                                   const float* y_dev, int64_t pair_y, const uint8_t* mask_dev, int64_t pair_m, int32_t T,
+                                   const int32_t* status_dev, double* work_dev, int64_t pair_work, double* r2_dev,
+                                   double* rmse_dev, int64_t pair_out, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(q_dev && b64_dev && bp_dev && y_dev && mask_dev && status_dev && work_dev && r2_dev && rmse_dev, HSR_ERR_INVALID,
+              "hsr_pair_report_f64: NULL pointer");
+  HSR_REQUIRE(npix >= 1 && T >= 1 && nf >= 1 && na >= nf + 1 && na % 16 == 0 && ldq >= na && ldbp >= T && npairs >= 1 &&
+              npairs <= 65535, HSR_ERR_INVALID, "hsr_pair_report_f64: bad shape (npix=%lld na=%d nf=%d T=%d ldq=%lld P=%d)",
+              (long long)npix, na, nf, T, (long long)ldq, npairs);
+  const int64_t chunks = (npix + kRepRows - 1) / kRepRows;
+  HSR_REQUIRE(chunks <= 0x7fffffff, HSR_ERR_UNSUPPORTED, "hsr_pair_report_f64: npix=%lld too large", (long long)npix);
+  HSR_REQUIRE(pair_work >= chunks * T * 4, HSR_ERR_INVALID, "hsr_pair_report_f64: pair_work below hsr_pair_report_work_bytes / 8");
+  HSR_REQUIRE(npairs == 1 || (pair_q >= npix * ldq && pair_b >= T && pair_bp >= (int64_t)nf * ldbp && pair_y >= (int64_t)T * npix &&
+                              pair_m >= npix && pair_out >= T),
+              HSR_ERR_INVALID, "hsr_pair_report_f64: pair strides overlap");
+  // two 16-byte loads per lane and k-tile: rows and pairs of Q on 16-byte boundaries
+  HSR_REQUIRE(((uintptr_t)q_dev & 15) == 0 && ldq % 2 == 0 && pair_q % 2 == 0, HSR_ERR_UNSUPPORTED,
+              "hsr_pair_report_f64: needs 16-byte aligned rows of Q");
+  PairReportArgs a{q_dev, b64_dev, bp_dev, y_dev, mask_dev, work_dev, ldq, pair_q, pair_b, ldbp, pair_bp, pair_y, pair_m,
+                   pair_work, npix, na, nf, T};
+  hipLaunchKernelGGL(pair_report_partial_kernel, dim3((unsigned)chunks, (unsigned)((T + 31) / 32), (unsigned)npairs), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  HSR_LAUNCH_CHECK("pair_report_partial_kernel");
+  hipLaunchKernelGGL(pair_report_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, (hipStream_t)stream, work_dev,
+                     pair_work, (int)chunks, T, status_dev, r2_dev, rmse_dev, pair_out);
+  HSR_LAUNCH_CHECK("pair_report_finish_kernel");
   return HSR_OK;
 }

@@ -9,7 +9,8 @@ evenly spaced EMIT bands (``subsample_bands_evenly``, :327), brings S2 to the EM
 Here the whole flow of P pairs of one shape is a fixed number of launches on the current stream, whatever P is
 (csrc/hsr_pairs.hip, csrc/hsr_ridge.hip, csrc/hsr_chol.hip): pair prep (block mean, band gather and decode, training mask),
 masked scaler statistics, masked expand, Gram, assembly, P Cholesky factorisations side by side, model read-out and the
-10 m prediction.  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
+10 m prediction; with ``report=True`` two more launches score each fit on its own training pixels (the notebook's cell 26:
+per-band R^2 and RMSE of sigmoid(model(X_train)) against the raw targets).  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
 does not depend on the batch: ``fuse_tile_pairs`` of a batch gives the bits of ``fuse_tile_pair`` of each of its pairs.
 
 S2 -> EMIT grid: an f x f block mean (float64 sum of the f^2 samples, stored as float32: the bits of ``hsr_block_mean``);
@@ -89,8 +90,10 @@ class _Plan:
     s2_dtype: str
 
 
-def _plan(emits, s2s, bands, degree, factor, s2_coarse) -> _Plan:
-    """Every check that needs no GPU: shapes, dtypes, the factor and the bands."""
+def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
+    """Every check that needs no GPU: shapes, dtypes, the factor, the bands and the report flag."""
+    if not isinstance(report, bool):
+        raise ValueError(f"report={report!r}: must be True or False")
     try:
         f = operator.index(factor)
     except TypeError:
@@ -159,7 +162,10 @@ class TilePairOutput:
     status   (P,) int32: 0 fitted, 1 no training pixel (that pair's cube is all NaN), 2 non-positive Cholesky pivot;
     mask     (P, h, w) bool, the training mask (flatten_pixels' rule on the EMIT grid);
     s2_coarse (P, nb, h, w) float32, S2 on the EMIT grid as the fit saw it (the block mean, or the caller's ``s2_coarse``);
-    bands    (T,) the EMIT band indices of the targets.
+    bands    (T,) the EMIT band indices of the targets;
+    r2, rmse (P, T) float64 with ``report=True`` (else None): the fit scored on its own training pixels as the notebook's cell 26
+             does - yp = sigmoid(clip(float32(model(X_train)), +-50)) in float32, d = y - yp against the decoded targets,
+             r2 = 1 - sum d^2 / (sum (y - mean y)^2 + 1e-8), rmse = sqrt(mean d^2), sums in float64; NaN where status != 0.
     ``model(i)`` is pair i's model as a ``PolyRidge`` (its host attributes are copied on first access)."""
     cube: Any
     n_train: Any
@@ -170,6 +176,8 @@ class TilePairOutput:
     degree: int
     alpha: float
     _fit: dict = field(repr=False, default_factory=dict)
+    r2: Any = None
+    rmse: Any = None
 
     def model(self, i: int) -> PolyRidge:
         f = self._fit
@@ -182,14 +190,16 @@ class TilePairOutput:
 
 def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                     emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                    eps: float = 1e-4) -> TilePairOutput:
+                    eps: float = 1e-4, report: bool = False) -> TilePairOutput:
     """P tile pairs -> their fused 10 m cubes (see the module docstring).
 
     emits: (P, bands, h, w) uint16 (decoded as ``u == 65535 ? NaN : float32(u) * 1e-4f``) or float32 reflectance (with an
     optional ``emit_nodata``, tested with the isclose rule); s2s: (P, nb, h f, w f) uint16 DN or float32 (optional
     ``s2_nodata``).  Device tensors, NumPy arrays (copied once) or lists of per-pair cubes (stacked on the device).
-    bands: an int (evenly subsampled, ``subsample_bands_evenly``), an index array or ``"all"``."""
-    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse)
+    bands: an int (evenly subsampled, ``subsample_bands_evenly``), an index array or ``"all"``.
+    report: also score every pair's fit on its training pixels (``r2`` / ``rmse`` of the output); two more launches, no host
+    sync, and every other output keeps the bits it has without the report."""
+    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse, report)
     torch = nat.require_gpu()
     lib = nat.load()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -252,6 +262,15 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     nat.check(lib.hsr_ridge_finish_batched(_ptr(G), na * ldq, na, nf, T, _ptr(Bp), T, npad * T, _ptr(mean), _ptr(scale), nb, nb, kpad,
                                            _ptr(b64), _ptr(b32), T, _ptr(W32), kpad * T, _ptr(mean32), _ptr(inv32), nb, _ptr(info),
                                            _ptr(status), P, st), "hsr_ridge_finish_batched")
+    r2 = rmse = None
+    if report:                                         # the notebook's cell 26 on the rows Q the fit read
+        rw = lib.hsr_pair_report_work_bytes(npix, T) // 8
+        rwork = torch.empty((P, rw), **f64)
+        r2 = torch.empty((P, T), **f64)
+        rmse = torch.empty((P, T), **f64)
+        nat.check(lib.hsr_pair_report_f64(_ptr(Q), ldq, npix * ldq, na, npix, _ptr(b64), T, _ptr(Bp), T, npad * T, nf, _ptr(y),
+                                          T * npix, _ptr(mask), npix, T, _ptr(status), _ptr(rwork), rw, _ptr(r2), _ptr(rmse), T, P,
+                                          st), "hsr_pair_report_f64")
     # 6. the 10 m prediction: predict_cube_logit's rule for unusable pixels, per pair
     if plan.s2_dtype == "uint16":                      # DN as float32 (exact), from the int16 bits
         Xf = (S.to(torch.int32) & 0xFFFF).to(torch.float32)
@@ -265,14 +284,15 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
                                                     _ptr(cube), npix10, T * npix10, P, st), "hsr_polyfeat_predict_cube_batched")
     fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
     return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask.view(P, h, w).bool(),
-                          s2_coarse=x.view(P, nb, h, w), bands=plan.bands, degree=int(degree), alpha=float(alpha), _fit=fit)
+                          s2_coarse=x.view(P, nb, h, w), bands=plan.bands, degree=int(degree), alpha=float(alpha), _fit=fit,
+                          r2=r2, rmse=rmse)
 
 
 def fuse_tile_pair(emit, s2, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                    emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                   eps: float = 1e-4) -> TilePairOutput:
+                   eps: float = 1e-4, report: bool = False) -> TilePairOutput:
     """One tile pair: emit (bands, h, w), s2 (nb, h f, w f) -> a TilePairOutput with P = 1 (``cube[0]`` is (T, h f, w f)).
     The same launches as ``fuse_tile_pairs``, so a pair gives the same bits alone as in any batch."""
     batch = lambda a: None if a is None else ([a] if not _is_torch(a) and not isinstance(a, np.ndarray) else a[None])
     return fuse_tile_pairs(batch(emit), batch(s2), bands=bands, degree=degree, alpha=alpha, factor=factor,
-                           emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps)
+                           emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps, report=report)

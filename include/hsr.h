@@ -534,6 +534,20 @@ int hsr_polyfeat_predict_cube_batched(const float* x_dev, int64_t x_ps, int64_t 
                                       int32_t T, int32_t activation, int32_t nan_bad_pixels, float nodata, int32_t use_nodata,
                                       float* out_dev, int64_t out_stride, int64_t pair_out, int32_t npairs, hsr_stream_t stream);
 
+/* ---- tile pairs: the fit report (s2_emit.fuse_tile_pairs(report=True), the notebook's cell 26) -----------------------------------
+ * hsr_pair_report_f64: per pair and band j < T, over the training pixels (mask != 0; y (P, T, npix) the decoded targets, band
+ *   stride npix): z = float32(row of Q[:, :na] . [b64; Bp[:nf]; 0]) on v_mfma_f64_16x16x4_f64 (Q, b64, Bp as hsr_pair_expand_f64 /
+ *   hsr_ridge_finish_batched leave them), yp = 1 / (1 + expf(-clip(z, +-50))), d = yt - yp in float32; ss_res = sum d^2,
+ *   ss_tot = sum (yt - mean yt)^2 + 1e-8 in float64; r2 = 1 - ss_res / ss_tot, rmse = sqrt(ss_res / n) into (P, pair_out) arrays,
+ *   NaN where status_dev[pair] != 0.  Two launches; fixed 256-row chunks merged in a fixed order, so a pair's numbers do not
+ *   depend on its batch.  Q rows 16-byte aligned (even ldq and pair_q); pair_work >= hsr_pair_report_work_bytes(npix, T) / 8. */
+size_t hsr_pair_report_work_bytes(int64_t npix, int32_t T);
+int hsr_pair_report_f64(const double* q_dev, int64_t ldq, int64_t pair_q, int32_t na, int64_t npix, const double* b64_dev,
+                        int64_t pair_b, const double* bp_dev, int64_t ldbp, int64_t pair_bp, int32_t nf, const float* y_dev,
+                        int64_t pair_y, const uint8_t* mask_dev, int64_t pair_m, int32_t T, const int32_t* status_dev,
+                        double* work_dev, int64_t pair_work, double* r2_dev, double* rmse_dev, int64_t pair_out, int32_t npairs,
+                        hsr_stream_t stream);
+
 /* ---- f1: grid-aligned resamplers between the phases -----------------------------------------------
  * downsample_s2_to_grid ('average') and reproject_stack_to_grid ('bilinear') of the notebook
  * (Pairs_EMIT_S2_demo-2.ipynb cell 73, raw lines 4538-4599) for exactly aligned integer-factor grids:

@@ -2,6 +2,8 @@
 
     python tools/bench_tile_pairs.py                       # every configuration, each in a fresh process
     python tools/bench_tile_pairs.py --profile DIR         # the same under rocprofv3 --kernel-trace --stats (kernel times)
+    python tools/bench_tile_pairs.py --report              # report=False vs report=True at P = 64, T = 32 and T = 285
+    python tools/bench_tile_pairs.py --report --profile DIR   # the report=True batch under rocprofv3 (the report kernels)
 
 Configurations: P = 1, 8, 64 pairs at T = 32 targets, and P = 64 at T = 285 (EMIT 285 x 100 x 100 uint16, S2 10 x 600 x 600
 uint16, factor 6).  One JSON line per configuration:
@@ -12,6 +14,9 @@ uint16, factor 6).  One JSON line per configuration:
   ratio               ms_per_pair / loop_ms_per_pair;
 and with --profile, from the kernel trace: launches_per_batch, the Gram's float64 and the predict's float32 FLOP rates over
 their kernel time, and the per-kernel share of a batch.
+With --report: plain_ms_per_pair / report_ms_per_pair, the batch without and with ``report=True`` timed alternately in one
+process, and added_ms_per_pair, their difference; with --profile as well, report_us_per_batch (the two report kernels) and
+q_read_tbps, the bytes of Q the report reads (P x 10 000 rows x na float64) over the report's partial kernel time.
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = [(1, 32), (8, 32), (64, 32), (64, 285)]
+REPORT_CONFIGS = [(64, 32), (64, 285)]
 
 
 def _pairs(torch, P, seed=0):
@@ -98,6 +104,35 @@ def child(P, T, iters, warmup, host_pairs):
     print(json.dumps(rec), flush=True)
 
 
+def child_report(P, T, iters, warmup):
+    """report=False and report=True batches, alternately, over device events (median of each)."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
+    import torch
+    import s2_emit
+    E, S = _pairs(torch, P)
+    kw = dict(bands=32 if T == 32 else "all", s2_nodata=0.0)
+    for _ in range(warmup):
+        s2_emit.fuse_tile_pairs(E, S, **kw)
+        s2_emit.fuse_tile_pairs(E, S, report=True, **kw)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    plain, report = [], []
+    for _ in range(iters):
+        ev[0].record()
+        a = s2_emit.fuse_tile_pairs(E, S, **kw)
+        ev[1].record()
+        b = s2_emit.fuse_tile_pairs(E, S, report=True, **kw)
+        ev[2].record()
+        torch.cuda.synchronize()
+        plain.append(ev[0].elapsed_time(ev[1]))
+        report.append(ev[1].elapsed_time(ev[2]))
+        del a, b
+    pm, rm = sorted(plain)[len(plain) // 2], sorted(report)[len(report) // 2]
+    print(json.dumps(dict(P=P, T=T, iters=iters, plain_ms_per_pair=round(pm / P, 4), report_ms_per_pair=round(rm / P, 4),
+                          added_ms_per_pair=round((rm - pm) / P, 4))), flush=True)
+
+
 def _kernel_stats(out_dir):
     rows = []
     for path in glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True):
@@ -106,13 +141,13 @@ def _kernel_stats(out_dir):
     return rows
 
 
-def profile_one(P, T, iters, out_dir):
+def profile_one(P, T, iters, out_dir, report=False):
     """One configuration under rocprofv3, twice (1 and 1 + iters batches after the input generation): the difference of the two
     traces is `iters` batches alone - launches per batch, kernel time per batch, and the Gram / predict FLOP rates over it."""
     def run(n):
-        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}")
+        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}" + ("_report" if report else ""))
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
-               os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"]
+               os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"] + (["--report"] if report else [])
         subprocess.run(cmd, check=True, cwd=ROOT)
         per = {}
         for r in _kernel_stats(d):
@@ -139,8 +174,16 @@ def profile_one(P, T, iters, out_dir):
                kernel_ms_per_pair=round(total_ns / 1e6 / P, 4),
                gram_tflops_f64=round(2.0 * npix * na * ldq * P / gram_ns / 1e3, 2) if gram_ns else None,
                predict_tflops_f32=round(2.0 * npix10 * nf * T * P / pred_ns / 1e3, 2) if pred_ns else None,
+               **(report_fields(ns, P, npix, na, iters) if report else {}),
                kernel_us_per_batch={k.split("(")[0][-60:]: round(v[1] / iters / 1e3, 1) for k, v in sorted(diff.items(), key=lambda kv: -kv[1][1])})
     print(json.dumps(rec), flush=True)
+
+
+def report_fields(ns, P, npix, na, iters):
+    part_ns = ns(lambda n: "pair_report_partial" in n)
+    all_ns = ns(lambda n: "pair_report" in n)
+    return dict(report_us_per_batch=round(all_ns / 1e3, 1), report_us_per_pair=round(all_ns / 1e3 / P, 2),
+                q_read_tbps=round(P * npix * na * 8 / part_ns / 1e3, 2) if part_ns else None)
 
 
 def main():
@@ -151,7 +194,8 @@ def main():
     ap.add_argument("--host-pairs", type=int, default=4)
     ap.add_argument("--batch-only", action="store_true", help="(profiling) time the batch only, no per-pair loop")
     ap.add_argument("--profile", default=None, help="directory for rocprofv3 output: profile every configuration")
-    ap.add_argument("--configs", default=None, help="P,T;P,T... (default: all)")
+    ap.add_argument("--configs", default=None, help="P,T;P,T... (default: all; with --report 64,32;64,285)")
+    ap.add_argument("--report", action="store_true", help="time report=False against report=True")
     a = ap.parse_args()
     if a.child:
         P, T = map(int, a.child.split(","))
@@ -162,15 +206,21 @@ def main():
             import s2_emit
             E, S = _pairs(torch, P)
             for _ in range(a.iters):
-                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0)
+                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0, report=a.report)
             torch.cuda.synchronize()
             return
-        child(P, T, a.iters, a.warmup, a.host_pairs)
+        if a.report:
+            child_report(P, T, a.iters, a.warmup)
+        else:
+            child(P, T, a.iters, a.warmup, a.host_pairs)
         return
-    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else CONFIGS
+    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else (REPORT_CONFIGS if a.report else CONFIGS)
     for P, T in configs:
         if a.profile:
-            profile_one(P, T, a.iters, a.profile)
+            profile_one(P, T, a.iters, a.profile, a.report)
+        elif a.report:
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(max(a.iters, 9)),
+                            "--warmup", str(a.warmup), "--report"], check=True)
         else:
             iters = a.iters if P * T < 64 * 285 else max(2, a.iters // 2)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(iters),
