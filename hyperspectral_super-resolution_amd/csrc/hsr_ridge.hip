@@ -1231,8 +1231,27 @@ __global__ __launch_bounds__(64 * kX16Waves, kX16Wgs) void predict103_x16_kernel
   }
 }
 
-// Picks the predict kernel, its grid and its LDS for the shape in PredArgs, and launches it.  10 inputs at degree 3 with the orbit
-// rows on the device and T <= 512 take the MFMA kernels above; every other shape takes the generic predict_kernel.
+static size_t predict_generic_lds(int kpad, int n_in) {
+  return ((size_t)kPredPix * (kpad + 1) + (size_t)kPredPix * (n_in + 1) + kPredPix) * sizeof(float);
+}
+
+// The predict kernel of a shape, the one rule behind launch_predict and hsr_polyfeat_predict_kernel: 10 inputs at degree 3 with
+// the orbit rows on the device and T <= 512 take the MFMA kernels above (0 x16 for T <= 16, else slice<per> with per = the
+// 32-target tiles of a slice: 1 .. 3); every other shape takes the generic predict_kernel<1 / 2 / 4> (4 .. 6, by the target
+// tiles a wave pair covers), or none (-1) when its feature tile does not fit in LDS.
+static int predict_slot(int n_in, int nfeat, int degree, int T, bool orb_rows) {
+  const int tt = (T + 31) / 32;
+  if (degree == 3 && n_in == 10 && nfeat == 285 && orb_rows && tt <= 16) {
+    if (T <= 16) return 0;
+    const int slices = (tt + 2) / 3;
+    return (tt + slices - 1) / slices;
+  }
+  if (predict_generic_lds((nfeat + 1) & ~1, n_in) > 150 * 1024) return -1;
+  const int per_wave = (tt + 1) / 2;                    // target tiles a wave pair must cover
+  return 4 + (per_wave <= 1 ? 0 : (per_wave <= 2 ? 1 : 2));
+}
+
+// Picks the predict kernel (predict_slot), its grid and its LDS for the shape in PredArgs, and launches it.
 typedef void (*PredOrbKernel)(PredArgs, const int16_t*);
 typedef void (*PredGenericKernel)(PredArgs);
 static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npairs = 1) {
@@ -1241,16 +1260,16 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
   PredGenericKernel generic = nullptr;
   const void* kern;
   const char* what;
-  int slot, gx, slices = 1, threads;
+  int gx, slices = 1, threads;
   size_t lds;
   const int16_t* rows = nullptr;
   const int tt = a.ttiles;
-  if (degree == 3 && a.n_in == 10 && a.nfeat == 285 && g_orb_rows_dev != nullptr && tt <= 16) {
+  const int slot = predict_slot(a.n_in, a.nfeat, degree, a.T, g_orb_rows_dev != nullptr);
+  if (slot >= 0 && slot <= 3) {
     int waves, wgs_per_cu = 1;
-    if (a.T <= 16) {                                    // 16-target tiles (v_mfma_f32_16x16x4_f32)
+    if (slot == 0) {                                    // 16-target tiles (v_mfma_f32_16x16x4_f32)
       orb = predict103_x16_kernel;
       what = "predict103_x16_kernel launch";
-      slot = 0;
       waves = kX16Waves;
       wgs_per_cu = kX16Wgs;
       lds = (size_t)4 * kStepsOrb * 16 * 4;
@@ -1259,10 +1278,9 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
       // T <= 32: one 16-wave workgroup per CU, W (36.6 KB) staged once per CU (0.209 -> 0.199 ms);
       // T <= 512: slices of 64 or 96 targets, as few and as narrow as T allows
       slices = (tt + 2) / 3;
-      const int per = (tt + slices - 1) / slices;       // 32-target tiles per slice: 1 only for tt == 1
-      orb = per == 1 ? predict103_slice_kernel<1> : (per <= 2 ? predict103_slice_kernel<2> : predict103_slice_kernel<3>);
+      const int per = slot;                             // 32-target tiles per slice: 1 only for tt == 1
+      orb = per == 1 ? predict103_slice_kernel<1> : (per == 2 ? predict103_slice_kernel<2> : predict103_slice_kernel<3>);
       what = "predict103_slice_kernel launch";
-      slot = per;
       waves = slice_waves(per);
       lds = (size_t)2 * kStepsOrb2 * per * 32 * 4;
       rows = g_orb_rows_dev + 4 * kStepsOrb;            // kOrb2.src
@@ -1275,16 +1293,13 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
     threads = 64 * waves;
     kern = reinterpret_cast<const void*>(orb);
   } else {
-    lds = ((size_t)kPredPix * (a.kpad + 1) + (size_t)kPredPix * (a.n_in + 1) + kPredPix) * sizeof(float);
-    HSR_REQUIRE(lds <= 150 * 1024, HSR_ERR_UNSUPPORTED, "hsr_polyfeat_predict: %zu bytes of LDS needed", lds);
+    lds = predict_generic_lds(a.kpad, a.n_in);
+    HSR_REQUIRE(slot >= 4, HSR_ERR_UNSUPPORTED, "hsr_polyfeat_predict: %zu bytes of LDS needed", lds);
     const int64_t tiles = (a.npix + kPredPix - 1) / kPredPix;
     gx = (int)(tiles < 512 ? tiles : 512);
     threads = kPredThreads;
-    const int per_wave = (tt + 1) / 2;                  // target tiles a wave pair must cover
-    const int variant = per_wave <= 1 ? 0 : (per_wave <= 2 ? 1 : 2);
-    generic = variant == 0 ? predict_kernel<1> : (variant == 1 ? predict_kernel<2> : predict_kernel<4>);
+    generic = slot == 4 ? predict_kernel<1> : (slot == 5 ? predict_kernel<2> : predict_kernel<4>);
     what = "predict_kernel launch";
-    slot = 4 + variant;
     kern = reinterpret_cast<const void*>(generic);
   }
   // a batch shares the chip's workgroups among its pairs: fewer per pair, each walking more of its pair's tiles with W staged once
@@ -1345,6 +1360,14 @@ extern "C" int hsr_polyfeat_table(int32_t n_in, int32_t degree, uint8_t* idx_out
     for (int k = 0; k < 3; ++k) idx_out[f * 3 + k] = g_table_host.idx[f][k];
   g_table_nin = -1;   // host table was rebuilt: force the device copy to refresh on next use
   return HSR_OK;
+}
+
+extern "C" int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t orbit_rows) {
+  const int nf = hsr_polyfeat_count(n_in, degree);
+  const bool orb = orbit_rows < 0 ? g_orb_rows_dev != nullptr : orbit_rows != 0;
+  const int slot = nf > 0 && T >= 1 ? predict_slot(n_in, nf, degree, T, orb) : -1;
+  if (slot < 0) set_error("hsr_polyfeat_predict_kernel: no predict kernel for n_in=%d degree=%d T=%d", n_in, degree, T);
+  return slot;
 }
 
 // Not a launch-path call: uploads the monomial table once per (n_in, degree) (hipMalloc + copy).
@@ -1675,7 +1698,8 @@ __global__ __launch_bounds__(256) void ridge_assemble_kernel(const double* __res
 // LDS once, eight thread groups take every eighth feature (coalesced over the targets), partial sums joined in group
 // order.  (First version: one thread per target walking all features with a division per step - 65 us for T = 32.)
 // Batched form: blockIdx.y is the pair, every operand offset by its pair stride (FinishPairs); with `status` a pair's word
-// becomes 0 (fitted), 1 (no training row: NaN intercept, so that every prediction is NaN) or 2 (non-positive pivot).
+// becomes 0 (fitted), 1 (no training row) or 2 (non-positive pivot), and a pair whose word is not 0 gets NaN intercepts, so that
+// every prediction of it is NaN whatever its failed factorisation left in W.
 struct FinishPairs {
   int64_t g, w, ms, b, w32, mi;      // element strides between pairs: G, Wm, mean / scale, b64 / b32, W32, mean32 / inv32
   const int32_t* info;               // Cholesky status words, one per pair (batched form only)
@@ -1701,7 +1725,8 @@ __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restr
   mean32 += pr * pp.mi;
   inv32 += pr * pp.mi;
   const double cnt = G[0];
-  if (pp.status && blockIdx.x == 0 && threadIdx.x == 0) pp.status[pr] = cnt == 0.0 ? 1 : (pp.info[pr] != 0 ? 2 : 0);
+  const int status = pp.status ? (cnt == 0.0 ? 1 : (pp.info[pr] != 0 ? 2 : 0)) : 0;
+  if (pp.status && blockIdx.x == 0 && threadIdx.x == 0) pp.status[pr] = status;
   const int tid = threadIdx.x;
   for (int f = tid; f < nf; f += 256) sc[f] = G[1 + f] / cnt;
   __syncthreads();
@@ -1716,7 +1741,7 @@ __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restr
     double a = part[0][tt];
 #pragma unroll
     for (int g = 1; g < 8; ++g) a += part[g][tt];
-    const double b = (pp.status && cnt == 0.0) ? __builtin_nan("") : G[na + t] / cnt - a;
+    const double b = status != 0 ? __builtin_nan("") : G[na + t] / cnt - a;
     b64[t] = b;
     b32[t] = (float)b;
   }

@@ -28,9 +28,10 @@ import numpy as np
 
 from . import _native as nat
 from ._engine import _ptr, _stream
-from .ridge import PolyRidge, subsample_bands_evenly
+from .ridge import PolyRidge, check_fit_features, subsample_bands_evenly
 
 _DTYPES = {"uint16": 2, "float32": 0}      # hsr_pair_prep's dtype codes
+_MAX_FACTOR = 64                           # hsr_pair_prep's bound on the S2 / EMIT pixel ratio
 
 
 def _is_torch(x) -> bool:
@@ -91,7 +92,7 @@ class _Plan:
 
 
 def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
-    """Every check that needs no GPU: shapes, dtypes, the factor, the bands and the report flag."""
+    """Every check that needs no GPU: shapes, dtypes, the factor, the bands, the size of the ridge system and the report flag."""
     if not isinstance(report, bool):
         raise ValueError(f"report={report!r}: must be True or False")
     try:
@@ -100,6 +101,8 @@ def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
         raise ValueError(f"factor={factor!r}: the S2 / EMIT pixel ratio must be an integer") from None
     if f < 1:
         raise ValueError(f"factor={f}: must be >= 1")
+    if f > _MAX_FACTOR:
+        raise ValueError(f"factor={f}: the pair prep takes at most {_MAX_FACTOR}")
     if not 1 <= int(degree) <= 3:
         raise ValueError(f"degree={degree}: 1, 2 or 3")
     (P, B, h, w), edt = _describe(emits, "emit", 3)
@@ -112,6 +115,7 @@ def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
         raise ValueError(f"s2 is {H} x {W} but emit {h} x {w} at factor {f} needs {h * f} x {w * f}")
     if not 1 <= nb <= nat.HSR_MAX_BANDS:
         raise ValueError(f"s2 has {nb} bands: 1 .. {nat.HSR_MAX_BANDS} supported")
+    check_fit_features(nb, degree)
     if s2_coarse is not None:
         cshape, cdt = _describe(s2_coarse, "s2_coarse", 3)
         if cshape != (P, nb, h, w) or cdt != "float32":
@@ -159,7 +163,9 @@ class TilePairOutput:
     cube     (P, T, h f, w f) float32 = sigmoid(clip(model(S2 at 10 m), +-50)), NaN where predict_cube_logit leaves NaN (a
              non-finite or ``s2_nodata`` input) and everywhere for a pair without training pixels;
     n_train  (P,) int64, the pixels that survived the flatten rule;
-    status   (P,) int32: 0 fitted, 1 no training pixel (that pair's cube is all NaN), 2 non-positive Cholesky pivot;
+    status   (P,) int32: 0 fitted, 1 no training pixel, 2 non-positive Cholesky pivot (e.g. alpha = 0 and training pixels
+             that all carry one S2 vector); a pair with status != 0 has NaN intercepts (``model(i).intercept_``), an all-NaN
+             cube and NaN ``r2`` / ``rmse``, while its other fit outputs are whatever the failed solve left;
     mask     (P, h, w) bool, the training mask (flatten_pixels' rule on the EMIT grid);
     s2_coarse (P, nb, h, w) float32, S2 on the EMIT grid as the fit saw it (the block mean, or the caller's ``s2_coarse``);
     bands    (T,) the EMIT band indices of the targets;

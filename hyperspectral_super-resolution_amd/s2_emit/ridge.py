@@ -11,6 +11,7 @@ the prediction is one fused expand + float32-MFMA + sigmoid kernel (``hsr_polyfe
 """
 from __future__ import annotations
 
+from math import comb
 from typing import Optional
 
 import numpy as np
@@ -21,6 +22,20 @@ from ._engine import _ptr, _stream
 
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
+
+
+MAX_FIT_FEATURES = 512     # the Cholesky solve's bound on the ridge system (hsr_chol_solve_f64: n <= 512)
+
+
+def check_fit_features(n_in: int, degree: int) -> int:
+    """The monomial count of a degree-``degree`` fit of ``n_in`` inputs; ValueError when the ridge system would be larger than
+    the Cholesky kernels take (at degree 3: 13 or more inputs).  Needs no GPU."""
+    n_in, degree = int(n_in), int(degree)
+    nf = sum(comb(n_in + d - 1, d) for d in range(1, degree + 1)) if n_in >= 1 and degree >= 1 else 0
+    if nf > MAX_FIT_FEATURES:
+        raise ValueError(f"{n_in} inputs at degree {degree} give nf={nf} polynomial features; the ridge solve takes at most "
+                         f"{MAX_FIT_FEATURES}")
+    return nf
 
 
 def subsample_bands_evenly(num_bands_total: int, num_keep: int = 32) -> np.ndarray:
@@ -147,9 +162,10 @@ class PolyRidge:
 
     def local_gram(self, Xd, Yd, mean, scale):
         """[1 | Phi(z)]^T [1 | Phi(z) | Y] of this shard on the float64 matrix cores -> (na, na + tp) device tensor."""
+        n, n_in = Xd.shape
+        check_fit_features(n_in, self.degree)
         torch = nat.require_gpu()
         lib = nat.load()
-        n, n_in = Xd.shape
         T = Yd.shape[1]
         nf = lib.hsr_polyfeat_count(n_in, self.degree)
         if nf <= 0:
@@ -209,6 +225,8 @@ class PolyRidge:
         """X (N, n_in), Y (N, T) - NumPy or GPU tensors; rows must be finite (see flatten_pixels).
         Inside an initialised torch.distributed job of more than one rank (or distributed=True) X, Y are this
         rank's pixels and the fit is over the union of all ranks' pixels (two small collectives, see above)."""
+        shape = np.shape(X)
+        check_fit_features(shape[1] if len(shape) == 2 else 1, self.degree)
         torch = nat.require_gpu()
         Xd, Yd = self._to_dev(X, Y)
         if distributed is None:

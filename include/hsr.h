@@ -740,6 +740,12 @@ int hsr_probe_read(const void* buf_dev, int64_t bytes, int32_t mode, float* sink
  * (deg in [0, HSR_MAX_DEG], variant in [0, 22)).  The variant numbering is the enum SrfVariant of csrc/hsr_srf.hip. */
 int hsr_srf_last_launch(int32_t* deg, int32_t* variant, int64_t* lds_bytes);
 int hsr_srf_kernel_instance(int32_t deg, int32_t variant);
+/* Which predict kernel hsr_polyfeat_predict / _predict_cube / _predict_cube_batched launch for (n_in, degree, T): 0
+ * predict103_x16_kernel, 1 .. 3 predict103_slice_kernel<1 .. 3>, 4 .. 6 predict_kernel<1 / 2 / 4>; -1 (and the error text) for a
+ * shape no kernel takes.  The MFMA kernels (0 .. 3) need the orbit rows that the first hsr_polyfeat_prepare uploads:
+ * orbit_rows < 0 answers for the library as it stands, 0 / 1 as if the rows were absent / on the device.  Host only; it
+ * adds no record and changes no entry point, so HSR_ABI_VERSION stays. */
+int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t orbit_rows);
 
 #ifdef __cplusplus
 }

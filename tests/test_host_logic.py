@@ -314,6 +314,50 @@ def test_polyfeat_table_matches_sklearn_order():
     np.testing.assert_array_equal(expo, load_golden("g7_ridge")["powers"])     # sklearn's powers_
 
 
+def test_polyfeat_predict_kernel_selection_host_side():
+    """hsr_polyfeat_predict_kernel, the rule launch_predict takes, at every slot boundary: (10, 3) with the orbit rows on the
+    device takes x16 (0) up to 16 targets, then slice<per> (1 .. 3) for the 32-target tiles per slice up to 512; every other
+    shape - and (10, 3) without the rows - the generic predict_kernel<1 / 2 / 4> (4 .. 6) by the tiles a wave pair covers."""
+    lib = nat.load()
+    q = lib.hsr_polyfeat_predict_kernel
+    orb = {1: 0, 16: 0, 17: 1, 32: 1, 33: 2, 64: 2, 65: 3, 96: 3, 97: 2, 128: 2, 129: 3, 192: 3, 193: 3, 256: 3, 257: 3,
+           285: 3, 512: 3, 513: 6}
+    generic = {1: 4, 16: 4, 17: 4, 32: 4, 33: 4, 64: 4, 65: 5, 96: 5, 97: 5, 128: 5, 129: 6, 256: 6, 257: 6, 285: 6, 513: 6}
+    for T, slot in orb.items():
+        assert q(10, 3, T, 1) == slot, T
+    for T, slot in generic.items():
+        assert q(10, 3, T, 0) == slot, T
+        for n_in, deg in ((9, 3), (10, 2), (1, 1), (4, 3), (16, 2), (12, 3), (13, 3)):
+            assert q(n_in, deg, T, 1) == slot and q(n_in, deg, T, 0) == slot and q(n_in, deg, T, -1) == slot, (n_in, deg, T)
+    # as the library stands: the rows are either on the device (after a (10, 3) prepare on a GPU) or not, for every T alike
+    now = [q(10, 3, T, -1) for T in orb]
+    assert now == list(orb.values()) or now == [q(10, 3, T, 0) for T in orb], now
+    # shapes no kernel takes: no monomial table, no target, or a feature tile beyond the generic kernel's LDS
+    for n_in, deg, T in ((17, 3, 32), (10, 4, 32), (0, 1, 32), (10, 3, 0), (14, 3, 32), (16, 3, 1)):
+        assert q(n_in, deg, T, 1) == -1 and b"hsr_polyfeat_predict_kernel" in lib.hsr_last_error(), (n_in, deg, T)
+
+
+def test_polyridge_rejects_systems_beyond_the_cholesky_bound(monkeypatch):
+    """More than 512 polynomial features (13 inputs at degree 3: 559) is a ValueError naming nf and the bound, raised by fit and
+    local_gram before anything is launched (the GPU is never asked for); 12 inputs (454) pass the check."""
+    from s2_emit import ridge
+
+    def no_gpu():
+        raise AssertionError("the GPU was asked for")
+
+    monkeypatch.setattr(nat, "require_gpu", no_gpu)
+    assert ridge.check_fit_features(12, 3) == 454 == nat.load().hsr_polyfeat_count(12, 3)
+    assert ridge.check_fit_features(16, 2) == 152 and ridge.check_fit_features(10, 3) == 285
+    for n_in, deg, nf in ((13, 3, 559), (16, 3, 968)):
+        X, Y = np.zeros((20, n_in), np.float32), np.zeros((20, 2))
+        with pytest.raises(ValueError, match=f"nf={nf} .* at most 512"):
+            s2_emit.PolyRidge(deg, 1.0).fit(X, Y)
+        with pytest.raises(ValueError, match=f"nf={nf} .* at most 512"):
+            s2_emit.PolyRidge(deg, 1.0).local_gram(X, Y, None, None)
+    with pytest.raises(AssertionError, match="GPU was asked"):
+        s2_emit.PolyRidge(3, 1.0).fit(np.zeros((20, 12), np.float32), np.zeros((20, 2)))
+
+
 def test_compute_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

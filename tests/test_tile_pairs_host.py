@@ -102,6 +102,9 @@ def test_argument_validation_before_gpu_work():
         (dict(emit=emit[0], s2=s2), "expected"),
         (dict(emit=emit, s2=np.zeros((17, 24, 30), np.uint16)), "bands: 1 .. 16"),
         (dict(emit=emit, s2=s2, s2_coarse=np.zeros((10, 4, 5), np.float64)), "s2_coarse"),
+        (dict(emit=emit, s2=np.zeros((13, 24, 30), np.uint16)), "nf=559 .* at most 512"),              # Sentinel-2's 13 bands
+        (dict(emit=emit, s2=np.zeros((16, 24, 30), np.uint16), degree=3), "nf=968 .* at most 512"),
+        (dict(emit=emit[:, :1, :1], s2=np.zeros((10, 65, 65), np.uint16), factor=65), "factor=65: .* at most 64"),
     ]
     for kw, msg in bad:
         with pytest.raises(ValueError, match=msg):
@@ -110,3 +113,25 @@ def test_argument_validation_before_gpu_work():
         fuse_tile_pairs(np.stack([emit, emit]), s2[None])
     with pytest.raises(ValueError, match="share one shape"):
         fuse_tile_pairs([emit, emit[:, :3]], [s2, s2])
+
+
+def test_largest_accepted_shapes_pass_the_host_checks(monkeypatch):
+    """The bounds are inclusive: 12 S2 bands at degree 3 (nf 454), 16 at degree 2 (152) and factor 64 get past every host check
+    to the GPU request (a stand-in that raises), while 13 bands at degree 3 / factor 65 never reach it."""
+    import s2_emit
+    from s2_emit import _native as nat
+
+    class Asked(Exception):
+        pass
+
+    def gpu():
+        raise Asked
+
+    monkeypatch.setattr(nat, "require_gpu", gpu)
+    emit = np.zeros((285, 2, 3), np.uint16)
+    for nb, deg, fac in ((12, 3, 1), (16, 2, 1), (10, 3, 64), (1, 1, 64)):
+        with pytest.raises(Asked):
+            s2_emit.fuse_tile_pair(emit, np.zeros((nb, 2 * fac, 3 * fac), np.uint16), degree=deg, factor=fac)
+    for nb, deg, fac in ((13, 3, 1), (10, 3, 65)):
+        with pytest.raises(ValueError):
+            s2_emit.fuse_tile_pair(emit, np.zeros((nb, 2 * fac, 3 * fac), np.uint16), degree=deg, factor=fac)
