@@ -13,6 +13,22 @@
 
 namespace hsr {
 
+// The last successful launch of this file's kernels on this thread (hsr_poly_last_launch): the kernel family and its template
+// arguments (nargs of them; bools = bit i set when argument i is a bool), formatted only when read.  family NULL = none.
+struct PolyLastLaunch {
+  const char* family = nullptr;
+  int nargs = 0, bools = 0;
+  int arg[3] = {0, 0, 0};
+};
+static thread_local PolyLastLaunch g_poly_last;
+
+// HSR_LAUNCH_CHECK that also records the instance on success.
+static int poly_launched(const char* what, const PolyLastLaunch& inst) {
+  const int rc = check_hip(hipGetLastError(), what);
+  if (rc == HSR_OK) g_poly_last = inst;
+  return rc;
+}
+
 // ------------------------------------------------------------------------------------------------
 // K2: moments of planes
 // ------------------------------------------------------------------------------------------------
@@ -568,17 +584,23 @@ static inline int stream_grid(int64_t work_items, int per_block) {
   return (int)(g > 2048 ? 2048 : g);  // 256 CUs x 8 blocks, grid-stride beyond
 }
 
+template <bool BATCH, int Q, int N>
+static int launch_apply_rows_n(const ApplyArgs& a, const hsr_batch_tile* tiles, int use_mask, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((apply_rows_kernel<Q, N, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask);
+  return poly_launched(BATCH ? "apply_rows_kernel (batched) launch" : "apply_rows_kernel launch",
+                       {"apply_rows_kernel", 3, 4, {Q, N, BATCH ? 1 : 0}});
+}
 template <bool BATCH, int Q>
 static int launch_apply_rows_q(const ApplyArgs& a, const hsr_batch_tile* tiles, int use_mask, int deg, dim3 grid, hipStream_t s) {
   switch (deg) {
-    case 0: hipLaunchKernelGGL((apply_rows_kernel<Q, 1, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask); break;
-    case 1: hipLaunchKernelGGL((apply_rows_kernel<Q, 2, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask); break;
-    case 2: hipLaunchKernelGGL((apply_rows_kernel<Q, 3, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask); break;
-    case 3: hipLaunchKernelGGL((apply_rows_kernel<Q, 4, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask); break;
-    case 4: hipLaunchKernelGGL((apply_rows_kernel<Q, 5, BATCH>), grid, dim3(256), 0, s, a, tiles, use_mask); break;
-    default: set_error("apply_rows: deg=%d", deg); return HSR_ERR_UNSUPPORTED;
+    case 0: return launch_apply_rows_n<BATCH, Q, 1>(a, tiles, use_mask, grid, s);
+    case 1: return launch_apply_rows_n<BATCH, Q, 2>(a, tiles, use_mask, grid, s);
+    case 2: return launch_apply_rows_n<BATCH, Q, 3>(a, tiles, use_mask, grid, s);
+    case 3: return launch_apply_rows_n<BATCH, Q, 4>(a, tiles, use_mask, grid, s);
+    case 4: return launch_apply_rows_n<BATCH, Q, 5>(a, tiles, use_mask, grid, s);
   }
-  return HSR_OK;
+  set_error("apply_rows: deg=%d", deg);
+  return HSR_ERR_UNSUPPORTED;
 }
 template <bool BATCH>
 static int launch_apply_rows(const ApplyArgs& a, const hsr_batch_tile* tiles, int use_mask, int q, int deg, dim3 grid, hipStream_t s) {
@@ -622,7 +644,8 @@ extern "C" int hsr_poly_moments(const float* x_dev, int64_t x_bs, int64_t x_ps, 
     case 3: hipLaunchKernelGGL(moments_kernel<3>, grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL(moments_kernel<4>, grid, block, 0, s, a); break;
   }
-  HSR_LAUNCH_CHECK("moments_kernel");
+  const int rc = poly_launched("moments_kernel launch", {"moments_kernel", 1, 0, {deg < 4 ? deg : 4}});
+  if (rc != HSR_OK) return rc;
   if (slots_out) *slots_out = a.slots;
   return HSR_OK;
 }
@@ -643,7 +666,8 @@ extern "C" int hsr_poly_moments_f64(const double* x_dev, int64_t x_stride, const
     case 3: hipLaunchKernelGGL(moments_f64_kernel<3>, grid, block, 0, s, x_dev, x_stride, y_dev, y_stride, npix, partials_dev, slots); break;
     default: hipLaunchKernelGGL(moments_f64_kernel<4>, grid, block, 0, s, x_dev, x_stride, y_dev, y_stride, npix, partials_dev, slots); break;
   }
-  HSR_LAUNCH_CHECK("moments_f64_kernel");
+  const int rc = poly_launched("moments_f64_kernel launch", {"moments_f64_kernel", 1, 0, {deg < 4 ? deg : 4}});
+  if (rc != HSR_OK) return rc;
   if (slots_out) *slots_out = slots;
   return HSR_OK;
 }
@@ -657,8 +681,7 @@ extern "C" int hsr_moments_reduce(const double* partials_dev, int32_t slots, int
   const int nrows = nb * moment_count(deg);
   hipLaunchKernelGGL(reduce_kernel, dim3((nrows + 3) / 4 < 16 ? (nrows + 3) / 4 : 16), dim3(256), 0, (hipStream_t)stream, partials_dev,
                      slots, nrows, moments_dev);
-  HSR_LAUNCH_CHECK("reduce_kernel");
-  return HSR_OK;
+  return poly_launched("reduce_kernel launch", {"reduce_kernel"});
 }
 
 extern "C" int hsr_poly_solve(const double* moments_dev, int32_t nb, int32_t deg, int64_t min_count,
@@ -668,8 +691,7 @@ extern "C" int hsr_poly_solve(const double* moments_dev, int32_t nb, int32_t deg
               "hsr_poly_solve: nb=%d deg=%d", nb, deg);
   hipLaunchKernelGGL(solve_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, moments_dev, nb, deg,
                      (long long)min_count, coeffs_dev);
-  HSR_LAUNCH_CHECK("solve_kernel");
-  return HSR_OK;
+  return poly_launched("solve_kernel launch", {"solve_kernel"});
 }
 
 extern "C" int hsr_moments_reduce_solve(const double* partials_dev, int32_t slots, int32_t nb, int32_t deg,
@@ -681,8 +703,7 @@ extern "C" int hsr_moments_reduce_solve(const double* partials_dev, int32_t slot
               "hsr_moments_reduce_solve: nb=%d deg=%d", nb, deg);
   hipLaunchKernelGGL(reduce_solve_kernel, dim3(nb), dim3(1024), 0, (hipStream_t)stream, partials_dev, slots, deg,
                      (long long)min_count, moments_dev, coeffs_dev);
-  HSR_LAUNCH_CHECK("reduce_solve_kernel");
-  return HSR_OK;
+  return poly_launched("reduce_solve_kernel launch", {"reduce_solve_kernel"});
 }
 
 extern "C" int hsr_poly_solve_host(const double* moments, int32_t nb, int32_t deg, int64_t min_count,
@@ -708,7 +729,6 @@ extern "C" int hsr_poly_apply(const float* x_dev, int64_t x_bs, int64_t x_ps, co
   if (npix == 0) return HSR_OK;
   ApplyArgs a{x_dev, x_bs, x_ps, mask_dev, coeffs_dev, lohi_dev, nb, deg, clip, npix, out_dev, out_bs, out_ps};
   hipStream_t s = (hipStream_t)stream;
-  int rc = HSR_OK;
   const bool aligned = ((((uintptr_t)x_dev) | ((uintptr_t)out_dev)) & 15) == 0;
   if (x_bs == 1 && out_bs == 1 && x_ps == out_ps && !(x_ps == 1 && nb > 1)) {  // pixel-major in and out, same rows
     const int64_t q = x_ps >> 2;
@@ -725,22 +745,17 @@ extern "C" int hsr_poly_apply(const float* x_dev, int64_t x_bs, int64_t x_ps, co
       if (gb > 8190) gb = 2046;
       gb = (gb + 2) / 3 * 3;
       const dim3 grid((unsigned)gb);
-      if (deg <= HSR_MAX_DEG) {
-        rc = launch_apply_rows<false>(a, nullptr, 0, (int)q, deg, grid, s);
-        if (rc != HSR_OK) return rc;
-      } else {
-        switch (q) {
-          case 1: hipLaunchKernelGGL(apply_rows_lds_kernel<1>, grid, dim3(256), 0, s, a); break;
-          case 2: hipLaunchKernelGGL(apply_rows_lds_kernel<2>, grid, dim3(256), 0, s, a); break;
-          case 3: hipLaunchKernelGGL(apply_rows_lds_kernel<3>, grid, dim3(256), 0, s, a); break;
-          default: hipLaunchKernelGGL(apply_rows_lds_kernel<4>, grid, dim3(256), 0, s, a); break;
-        }
+      if (deg <= HSR_MAX_DEG) return launch_apply_rows<false>(a, nullptr, 0, (int)q, deg, grid, s);
+      switch (q) {
+        case 1: hipLaunchKernelGGL(apply_rows_lds_kernel<1>, grid, dim3(256), 0, s, a); break;
+        case 2: hipLaunchKernelGGL(apply_rows_lds_kernel<2>, grid, dim3(256), 0, s, a); break;
+        case 3: hipLaunchKernelGGL(apply_rows_lds_kernel<3>, grid, dim3(256), 0, s, a); break;
+        default: hipLaunchKernelGGL(apply_rows_lds_kernel<4>, grid, dim3(256), 0, s, a); break;
       }
-    } else {
-      hipLaunchKernelGGL(apply_pixmajor_scalar_kernel, dim3(stream_grid(npix * nb, 256 * 4)), dim3(256), 0, s, a);
+      return poly_launched("apply_rows_lds_kernel launch", {"apply_rows_lds_kernel", 1, 0, {(int)q}});
     }
-    HSR_LAUNCH_CHECK("apply_rows_kernel");
-    return HSR_OK;
+    hipLaunchKernelGGL(apply_pixmajor_scalar_kernel, dim3(stream_grid(npix * nb, 256 * 4)), dim3(256), 0, s, a);
+    return poly_launched("apply_pixmajor_scalar_kernel launch", {"apply_pixmajor_scalar_kernel"});
   }
   const bool vec = aligned && x_ps == 1 && out_ps == 1 && (x_bs & 3) == 0 && (out_bs & 3) == 0 &&
                    (((uintptr_t)mask_dev) & 3) == 0;
@@ -749,8 +764,7 @@ extern "C" int hsr_poly_apply(const float* x_dev, int64_t x_bs, int64_t x_ps, co
     hipLaunchKernelGGL(apply_planar_kernel<true>, grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(apply_planar_kernel<false>, grid, dim3(256), 0, s, a);  // any mix of strides
-  HSR_LAUNCH_CHECK("apply_planar_kernel");
-  return HSR_OK;
+  return poly_launched("apply_planar_kernel launch", {"apply_planar_kernel", 1, 1, {vec ? 1 : 0}});
 }
 
 extern "C" int hsr_valid_mask(const float* x_dev, int64_t x_bs, int64_t x_ps, int32_t nbx, int32_t pos_band,
@@ -762,8 +776,7 @@ extern "C" int hsr_valid_mask(const float* x_dev, int64_t x_bs, int64_t x_ps, in
   if (npix == 0) return HSR_OK;
   hipLaunchKernelGGL(valid_mask_kernel, dim3(stream_grid(npix, 256)), dim3(256), 0, (hipStream_t)stream, x_dev,
                      x_bs, x_ps, nbx, pos_band, y_dev, y_bs, y_ps, y_dev ? nby : 0, mask_in_dev, npix, mask_out_dev);
-  HSR_LAUNCH_CHECK("valid_mask_kernel");
-  return HSR_OK;
+  return poly_launched("valid_mask_kernel launch", {"valid_mask_kernel"});
 }
 
 extern "C" int hsr_moments_reduce_solve_batched(const hsr_batch_tile* tiles_dev, int32_t ntiles, const double* partials_dev,
@@ -777,8 +790,8 @@ extern "C" int hsr_moments_reduce_solve_batched(const hsr_batch_tile* tiles_dev,
                                                                            : reduce_solve_batched_kernel<16, false>;
   hipLaunchKernelGGL(kern, dim3(ntiles), dim3(1024), 0, (hipStream_t)stream, tiles_dev, partials_dev, nb, deg,
                      (long long)min_count, moments_dev, coeffs_dev);
-  HSR_LAUNCH_CHECK("reduce_solve_batched_kernel");
-  return HSR_OK;
+  const int nbu = nb <= 8 ? 8 : nb <= 12 ? 12 : 16;
+  return poly_launched("reduce_solve_batched_kernel launch", {"reduce_solve_batched_kernel", 2, 2, {nbu, nbu <= 12 ? 1 : 0}});
 }
 
 extern "C" int hsr_poly_apply_batched(const hsr_batch_tile* tiles_dev, int32_t ntiles, int64_t max_npix, const double* coeffs_dev,
@@ -795,8 +808,23 @@ extern "C" int hsr_poly_apply_batched(const hsr_batch_tile* tiles_dev, int32_t n
   int64_t gb = (max_npix * q + 256 * kK3U - 1) / (256 * kK3U);
   if (gb > 2046) gb = 2046;
   gb = (gb + 2) / 3 * 3;
-  int rc = launch_apply_rows<true>(a, tiles_dev, use_mask, (int)q, deg, dim3((unsigned)gb, (unsigned)ntiles), (hipStream_t)stream);
-  if (rc != HSR_OK) return rc;
-  HSR_LAUNCH_CHECK("apply_rows_kernel (batched)");
-  return HSR_OK;
+  return launch_apply_rows<true>(a, tiles_dev, use_mask, (int)q, deg, dim3((unsigned)gb, (unsigned)ntiles), (hipStream_t)stream);
+}
+
+extern "C" int hsr_poly_last_launch(char* name, int32_t capacity) {
+  const PolyLastLaunch r = g_poly_last;
+  g_poly_last = PolyLastLaunch{};
+  if (!name || capacity < 1) return r.family ? 1 : 0;
+  name[0] = 0;
+  if (!r.family) return 0;
+  int len = snprintf(name, (size_t)capacity, "%s", r.family);
+  for (int i = 0; i < r.nargs && len >= 0 && len < capacity; ++i) {
+    const char* sep = i == 0 ? "<" : ", ";
+    if ((r.bools >> i) & 1)
+      len += snprintf(name + len, (size_t)(capacity - len), "%s%s", sep, r.arg[i] ? "true" : "false");
+    else
+      len += snprintf(name + len, (size_t)(capacity - len), "%s%d", sep, r.arg[i]);
+  }
+  if (r.nargs > 0 && len >= 0 && len < capacity) snprintf(name + len, (size_t)(capacity - len), ">");
+  return 1;
 }

@@ -13,8 +13,17 @@ namespace hsr {
 // of (V/s) c' = y by SVD with rcond = len(x)*eps, c = c'/s.  From the moments:
 //   A_jk = S_{(d-j)+(d-k)} / (s_j s_k),  s_j = sqrt(S_{2(d-j)}),  rhs_j = T_{d-j} / s_j,
 // eigen-decompose A (cyclic Jacobi, <= 5x5) and apply the pseudo-inverse keeping the eigenvalues
-// above rcond^2 * max (singular values of V/s are the square roots).
+// above max(rcond^2, kRankFloor) * max (singular values of V/s are the square roots).
 // Rank-revealing path: symmetric cyclic Jacobi on the scaled Gram, pseudo-inverse with NumPy's cut-off.
+//
+// kRankFloor: the Gram is built from rounded power sums, so it resolves eigenvalues only down to its own rounding.  The null
+// eigenvalue of an exactly rank-deficient band (repeated float32 values whose powers round in float64, e.g. x = 0.3) comes out
+// at ~eps * lmax, not rcond^2 * lmax; proj / lambda then inflated noise into the null space (the fitted values on the training
+// x stayed right, the polynomial elsewhere did not: np.polyfit returns the minimum-norm solution).  Measured with the host twin
+// on NumPy-summed moments (1..4 distinct values, deg <= 4, scales 1e-3..1e3): 2 eps suffices up to 1e5 pixels; at 1e6 pixels the
+// sums' own rounding puts the null eigenvalue at 4..8 eps.  A larger floor drops real directions of narrow-range bands (cond(V/s)
+// ~3e7: at 8 eps, x in [0.79, 0.81] at deg 3 went from 5e-7 to 4e-5 off np.polyfit), so 4 eps it is; see DESIGN.md (solve).
+constexpr double kRankFloor = 4 * 2.220446049250313e-16;
 // Storage is flat and caller-provided (rows of kSolveLd doubles): the stand-alone kernels and the host hand in local
 // arrays, the fused tail of K1 hands in LDS so that the dynamically indexed matrices do not make K1 a scratch-using
 // kernel.  Same arithmetic in the same order either way.
@@ -59,7 +68,7 @@ __host__ __device__ inline void solve_band_jacobi(double* A, double* V, const do
   double lmax = 0.0;
   for (int i = 0; i < n; ++i) lmax = A[i * kSolveLd + i] > lmax ? A[i * kSolveLd + i] : lmax;
   const double rcond = count * 2.220446049250313e-16;
-  const double thresh = rcond * rcond * lmax;
+  const double thresh = (rcond * rcond > kRankFloor ? rcond * rcond : kRankFloor) * lmax;
   for (int j = 0; j < n; ++j) coef[j] = 0.0;
   for (int i = 0; i < n; ++i) {
     const double lam = A[i * kSolveLd + i];
@@ -75,7 +84,11 @@ __host__ __device__ inline void solve_band_jacobi(double* A, double* V, const do
 // Fast path: Cholesky of the scaled Gram with every loop unrolled (N is a template constant, so the
 // whole factorisation lives in registers).  A pivot below 1e-13 (the scaled diagonal is exactly 1, so
 // this is cond(V/s) > ~3e6) hands the band to the rank-revealing Jacobi path, which reproduces
-// np.polyfit's singular-value cut-off; above it both paths agree to ~cond * eps.
+// np.polyfit's singular-value cut-off; above it both paths agree to ~cond * eps.  So does
+// trace(A^-1) = ||L^-1||_F^2 >= 1e14 (that trace lies in [1/lmin, n/lmin]): pivots bound lmin from
+// above only, and an exactly rank-deficient Gram whose null vector has a small last component passes
+// them with a last pivot of ~1e-12 (4 distinct x at deg 4, measured) - the Cholesky solve then puts
+// noise into the null space.  1e14 leaves every band of cond(V/s) <~ 1e7 on this path, bits unchanged.
 // EXTWORK: the Jacobi path works in ``work`` (kSolveWork doubles, e.g. LDS) instead of local arrays.
 template <int DEG, bool EXTWORK = false>
 __host__ __device__ inline void solve_band_t(const double* mom, long long min_count, double* coef, double* work = nullptr) {
@@ -136,9 +149,25 @@ __host__ __device__ inline void solve_band_t(const double* mom, long long min_co
     }
 #pragma unroll
     for (int j = 0; j < n; ++j) coef[j] = z[j] / s[j];
-    return;
+    // trace(A^-1), column i of L^-1 by forward substitution over rows i..n-1.  After the solve, so that its registers are
+    // free again (the fused tail of K1 inlines this); a band that fails it is solved again below, overwriting coef.
+    double tr = 0.0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) {
+      double w[n];
+#pragma unroll
+      for (int k = i; k < n; ++k) {
+        double v = k == i ? 1.0 : 0.0;
+#pragma unroll
+        for (int m = i; m < k; ++m) v -= L[k][m] * w[m];
+        w[k] = v / L[k][k];
+        tr += w[k] * w[k];
+      }
+    }
+    if (tr < 1e14) return;
   }
-  // rank-revealing path: the matrices move to flat storage with static indices (no scratch when ``work`` is LDS)
+  // rank-revealing path: the matrices move to flat storage with static indices (no scratch when ``work`` is LDS).  A is
+  // formed again from the moments (the same expression, so the same bits): it need not stay live through the factorisation.
   double* wk = work;
   double local[EXTWORK ? 1 : kSolveWork];
   if constexpr (!EXTWORK) wk = local;
@@ -151,7 +180,7 @@ __host__ __device__ inline void solve_band_t(const double* mom, long long min_co
     rf[j] = rhs[j];
     sf[j] = s[j];
 #pragma unroll
-    for (int k = 0; k < n; ++k) Af[j * kSolveLd + k] = A[j][k];
+    for (int k = 0; k < n; ++k) Af[j * kSolveLd + k] = S[(DEG - j) + (DEG - k)] / (s[j] * s[k]);
   }
   solve_band_jacobi(Af, Vf, rf, sf, n, count, coef);
 }

@@ -178,6 +178,7 @@ SIGNATURES = {
     "hsr_probe_read": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
     "hsr_srf_last_launch": (C.c_int, [_pi32, _pi32, C.POINTER(_i64)]),
     "hsr_srf_kernel_instance": (C.c_int, [_i32, _i32]),
+    "hsr_poly_last_launch": (C.c_int, [C.c_char_p, _i32]),
     "hsr_polyfeat_predict_kernel": (C.c_int, [_i32, _i32, _i32, _i32]),
     "hsr_step_plan_create": (C.c_int, [C.POINTER(StepDesc), C.POINTER(_vp)]),
     "hsr_step_plan_destroy": (None, [_vp]),

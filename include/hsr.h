@@ -740,6 +740,14 @@ int hsr_probe_read(const void* buf_dev, int64_t bytes, int32_t mode, float* sink
  * (deg in [0, HSR_MAX_DEG], variant in [0, 22)).  The variant numbering is the enum SrfVariant of csrc/hsr_srf.hip. */
 int hsr_srf_last_launch(int32_t* deg, int32_t* variant, int64_t* lds_bytes);
 int hsr_srf_kernel_instance(int32_t deg, int32_t variant);
+/* Which kernel instance of the moments / reduction / solve / apply / validity-mask family (csrc/hsr_poly.hip) ran.  Host only, same
+ * contract as hsr_srf_last_launch, so HSR_ABI_VERSION stays: every launch of hsr_poly_moments[_f64], hsr_moments_reduce[_solve]
+ * [_batched], hsr_poly_solve, hsr_poly_apply[_batched] and hsr_valid_mask (directly or through the executor) records its
+ * instance per thread.  hsr_poly_last_launch returns 1 and writes the calling thread's last successful such launch as a
+ * NUL-terminated name - kernel and template arguments as in the source, e.g. "apply_rows_kernel<2, 3, true>",
+ * "moments_kernel<4>", "reduce_kernel" - truncated to `capacity` bytes, then clears the record; 0 (and "") if there was no
+ * launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same. */
+int hsr_poly_last_launch(char* name, int32_t capacity);
 /* Which predict kernel hsr_polyfeat_predict / _predict_cube / _predict_cube_batched launch for (n_in, degree, T): 0
  * predict103_x16_kernel, 1 .. 3 predict103_slice_kernel<1 .. 3>, 4 .. 6 predict_kernel<1 / 2 / 4>; -1 (and the error text) for a
  * shape no kernel takes.  The MFMA kernels (0 .. 3) need the orbit rows that the first hsr_polyfeat_prepare uploads:

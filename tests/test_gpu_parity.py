@@ -1215,6 +1215,9 @@ def test_fused_degenerate_fits(torch_gpu):
         warnings.simplefilter("ignore")
         ref = np.polyfit(np.full(256, np.float64(np.float32(x0))), real[0].reshape(-1).astype(np.float64), 2)
     np.testing.assert_allclose(np.polyval(out.coeffs[0].cpu().numpy(), x0), np.polyval(ref, x0), rtol=1e-6)
+    # ... and the coefficients themselves, which K3 evaluates at every pixel: the minimum-norm solution is unique
+    c0 = out.coeffs[0].cpu().numpy()
+    assert np.max(np.abs(c0 - ref)) <= 1e-9 * np.max(np.abs(ref)), (c0, ref)
     # (4) a single band and deg 4
     one = {"B4": srf["B4"]}
     r1 = torch.from_numpy(real[names.index("B4")][None]).cuda()

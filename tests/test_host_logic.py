@@ -418,6 +418,84 @@ def test_solve_host_fallbacks_and_rank_loss():
             warnings.simplefilter("ignore")
             ref = np.polyfit(x, y, 2)
     np.testing.assert_allclose(c, ref, rtol=1e-9, atol=1e-12)
+    # x = 0.3: its powers round in float64, so the Gram is singular only up to rounding; the coefficients (the unique
+    # minimum-norm solution) must still be np.polyfit's, not noise inflated into the null space
+    x = np.full(10000, np.float32(0.3))
+    y = np.random.default_rng(0).uniform(0, 1, 10000).astype(np.float32)
+    for deg in (1, 2, 3, 4):
+        c = eng.poly_solve_host(_moments(x, y, deg)[None], deg, 50)[0]
+        ref = _polyfit_quiet(x, y, deg)
+        assert np.max(np.abs(c - ref)) <= 1e-9 * np.max(np.abs(ref)), (deg, c, ref)
+
+
+def _polyfit_quiet(x, y, deg):
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return np.polyfit(x.astype(np.float64), y.astype(np.float64), deg)
+
+
+RANK_VALUES = {1: [0.3], 2: [0.2, 0.7], 3: [0.2, 0.5, 0.9], 4: [0.1, 0.4, 0.7, 0.95]}
+
+
+@pytest.mark.parametrize("nd", [1, 2, 3, 4])
+def test_solve_host_rank_deficient_matches_polyfit_coefficients(nd):
+    """Exactly rank-deficient bands (nd distinct float32 values, deg >= nd) have one minimum-norm solution: the host twin
+    must return np.polyfit's coefficients, and the polynomial must agree beyond the data.  Worst measured: 2e-11."""
+    rng = np.random.default_rng(nd)
+    for n in (50, 333, 1000, 10000, 100000):
+        for scale in (1e-3, 1.0, 1e3):
+            for deg in range(nd, 5):
+                x = np.repeat(np.float32(np.array(RANK_VALUES[nd]) * scale), (n + nd - 1) // nd)[:n]
+                y = rng.uniform(0, 1, n).astype(np.float32)
+                c = eng.poly_solve_host(_moments(x, y, deg)[None], deg, 0)[0]
+                ref = _polyfit_quiet(x, y, deg)
+                what = (nd, n, scale, deg, c, ref)
+                assert np.max(np.abs(c - ref)) <= 1e-9 * np.max(np.abs(ref)), what
+                grid = np.linspace(0, 1.5 * scale, 64)
+                pr = np.polyval(ref, grid)
+                assert np.max(np.abs(np.polyval(c, grid) - pr)) <= 1e-9 * np.max(np.abs(pr)), what
+
+
+def test_solve_host_conditioning_envelope():
+    """Raw power sums lose the centred information of a narrow x range (solve).  Whenever cond(V/s) <= 1e5 the
+    predictions on the training x must match np.polyfit's to 1e-9; the sweep reaches cond ~1e16 and must stay finite."""
+    rng = np.random.default_rng(0)
+    checked = 0
+    for lo, hi in ((0.0, 1.0), (0.1, 0.12), (0.28, 0.32), (0.30, 0.31), (0.79, 0.81), (0.5, 0.505), (0.9, 0.9001)):
+        for deg in (1, 2, 3, 4):
+            x = rng.uniform(lo, hi, 10000).astype(np.float32)
+            y = (np.sin(3 * x) + 0.5 * x * x + 0.01 * rng.standard_normal(10000)).astype(np.float32)
+            X = x.astype(np.float64)
+            V = np.vander(X, deg + 1)
+            cond = np.linalg.cond(V / np.sqrt((V * V).sum(0)))
+            c = eng.poly_solve_host(_moments(x, y, deg)[None], deg, 0)[0]
+            err = np.max(np.abs(np.polyval(c, X) - np.polyval(_polyfit_quiet(x, y, deg), X)))
+            assert np.isfinite(c).all() and err < 1e-2, (lo, hi, deg, cond, err)
+            if cond <= 1e5:
+                assert err <= 1e-9, (lo, hi, deg, cond, err)
+                checked += 1
+    assert checked >= 12
+
+
+def test_poly_launch_record_host_side():
+    """hsr_poly_last_launch: empty at the start, no record after calls refused before their launch, cleared on read."""
+    lib = nat.load()
+    buf = ctypes.create_string_buffer(64)
+    lib.hsr_poly_last_launch(None, 0)                            # whatever an earlier test left
+    buf.value = b"junk"
+    assert lib.hsr_poly_last_launch(buf, 64) == 0 and buf.value == b""
+    f = ctypes.c_void_p(16)
+    assert lib.hsr_poly_apply(None, 1, 4, None, None, 1, 1, 10, None, 0, None, 1, 4, None) == 1
+    assert lib.hsr_poly_apply(f, 1, 4, None, None, 17, 1, 10, None, 0, f, 1, 4, None) == 2
+    assert lib.hsr_poly_moments(f, 1, 4, f, 1, 4, None, 10, 1, 9, 0.0, 0.0, None, None, f, None, None) == 2
+    assert lib.hsr_moments_reduce(f, 0, 1, 1, f, None) == 1 and lib.hsr_moments_reduce_solve(f, 5000, 1, 1, 0, f, f, None) == 1
+    assert lib.hsr_poly_solve(None, 1, 1, 0, f, None) == 1 and lib.hsr_valid_mask(None, 1, 1, 1, 0, None, 0, 0, 0, None, 1, f, None) == 1
+    assert lib.hsr_moments_reduce_solve_batched(f, 0, f, 1, 1, 0, f, f, None) == 2
+    assert lib.hsr_poly_apply_batched(f, 1, 10, f, 4, 1, 2, 0, 0, None) == 2
+    assert lib.hsr_poly_apply(f, 1, 4, None, None, 1, 1, 0, None, 0, f, 1, 4, None) == 0      # npix 0: nothing launched
+    assert lib.hsr_poly_last_launch(buf, 64) == 0 and buf.value == b""
+    assert lib.hsr_poly_last_launch(None, 0) == 0
 
 
 # ---------------------------------------------------------------------------------------------
