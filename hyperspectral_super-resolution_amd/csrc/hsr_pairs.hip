@@ -294,6 +294,348 @@ __global__ __launch_bounds__(256) void pair_report_finish_kernel(const double* _
   }
 }
 
+// Hold-out (fuse_tile_pairs(train_mask=...)): the fit's mask = the flatten rule's mask & the caller's, and the group code of every
+// pixel for the validation score: 1 fit, 2 held out (valid but kept from the fit), 0 neither.
+__global__ __launch_bounds__(256) void pair_holdout_kernel(const uint8_t* __restrict__ valid, const uint8_t* __restrict__ train,
+                                                           int64_t pair_train, int64_t npix, uint8_t* __restrict__ mask,
+                                                           uint8_t* __restrict__ group) {
+  const int64_t pr = blockIdx.y;
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= npix) return;
+  const bool v = valid[pr * npix + p] != 0, t = train[pr * pair_train + p] != 0;
+  mask[pr * npix + p] = v && t ? 1 : 0;
+  group[pr * npix + p] = v ? (t ? 1 : 2) : 0;
+}
+
+// Validation score (fuse_tile_pairs(validate=True)): one view of the prediction on the EMIT grid, pred (P, T, npix), against the
+// decoded targets y (P, T, npix), for the two pixel groups of group (P, npix) at once.  Two reductions cross on the band-major
+// layout - per band along the pixels (error statistics), per pixel along the bands (spectral angle) - and both are fed from ONE
+// pass over pred and y:
+//   partial  grid (chunks, P), one wave per workgroup.  A wave owns kScorePix consecutive pixels (a plan that depends on npix
+//            only), a lane 4 kScoreVec of them as kScoreVec 16-byte loads per array and band (the vectorised instance; the plain
+//            one loads the same pixels one by one with bounds checks: same lanes, same order, same bits).  The lane walks the
+//            bands in order with its pixels' dot / |y|^2 / |p|^2 sums in registers (float64), and forms per band and group the
+//            statistics of its own pixels: n, sum d^2, mean = sum / n and M2 = sum (y - mean)^2 - two passes over <= 8 values in
+//            registers, so equal targets give M2 == 0 exactly.  A chunk without held-out pixels (always, without a train_mask)
+//            takes an instance of the walk that computes the fit group only.  The 64 lane partials of kScoreBands bands are joined through LDS:
+//            lane (band b, group g, segment s) merges lanes 8 s .. 8 s + 7 in lane order (Chan), three shuffle-down steps merge
+//            the segments left to right, and the segment-0 lanes store the chunk's partial [sum d^2, n, mean, M2].  Angles: per
+//            pixel at the end, float32 into sam_map, their float64 sum and count per group into the chunk's partial.
+//   finish   one workgroup per pair, a thread per band: chunks merged in index order (their partials loaded four chunks ahead of
+//            the merge chain); n, rmse, r2, mean_ref per band and group, ERGAS over the bands (a lane adds its bands in order,
+//            lanes by the xor butterfly, waves in wave order), the mean angle.
+// Every order depends on (npix, T) only: a pair's numbers depend on neither the batch size nor its position in the batch.
+constexpr int kScoreVec = 2;                         // 16-byte loads per lane, array and band
+constexpr int kScoreLanePix = 4 * kScoreVec;         // pixels of a lane
+constexpr int kScorePix = 64 * kScoreLanePix;        // pixels of a chunk
+constexpr int kScoreBands = 4;                       // bands per LDS join: 4 bands x 2 groups x 8 segments = 64 lanes
+constexpr int kScoreHalf = 2;                        // bands per group of loads (kept one group ahead of the arithmetic)
+constexpr int kScorePitch = 72;                      // 64 lane partials + one pad per 8: the 8 segments start on disjoint banks
+
+struct PairScoreArgs {
+  const float* pred;                   // (P, T, npix)
+  const float* y;                      // (P, T, npix)
+  const uint8_t* group;                // (P, npix): 0 skip, 1 fit, 2 held out
+  double* work;                        // (P, pair_work): [chunk][T][2][4] then [chunk][2][2]
+  float* sam_map;                      // (P, npix)
+  int64_t pair_pred, pair_y, pair_group, pair_work, pair_map, npix;
+  int32_t T, chunks;
+};
+
+// Chan's merge without branches: an empty side has mean 0 and M2 0, so its terms vanish (frac = 0, or delta * 1 from mean 0), and
+// delta == 0 leaves mean and M2 + M2 untouched: equal targets keep M2 == 0 exactly.
+__device__ __forceinline__ RepStat score_merge(const RepStat& a, const RepStat& b) {
+  const double n = a.n + b.n, delta = b.mu - a.mu;
+  const double frac = n > 0.0 ? b.n / n : 0.0;
+  return RepStat{a.sd + b.sd, n, a.mu + delta * frac, a.m2 + b.m2 + delta * delta * (a.n * frac)};
+}
+
+struct ScoreLane {                     // what a lane keeps across the bands
+  int64_t p0[kScoreVec];               // first pixel of each of its vectors
+  int grp[kScoreLanePix];              // group code of each pixel (0 past the end)
+  double dot[kScoreLanePix], sa[kScoreLanePix], sb[kScoreLanePix];
+};
+
+// Bands j0 and j0 + 1 of this lane's pixels (zeros past T and past npix).
+template <bool kVec>
+__device__ __forceinline__ void score_load(const PairScoreArgs& a, const float* __restrict__ pred, const float* __restrict__ y,
+                                           const ScoreLane& L, int j0, float (&pv)[kScoreHalf][kScoreLanePix],
+                                           float (&yv)[kScoreHalf][kScoreLanePix]) {
+#pragma unroll
+  for (int jj = 0; jj < kScoreHalf; ++jj) {
+    const int j = j0 + jj;
+#pragma unroll
+    for (int v = 0; v < kScoreVec; ++v) {
+      const int64_t off = (int64_t)j * a.npix + L.p0[v];
+      if (kVec) {
+        float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), y4 = p4;
+        if (j < a.T && L.p0[v] < a.npix) {
+          p4 = *reinterpret_cast<const float4*>(pred + off);
+          y4 = *reinterpret_cast<const float4*>(y + off);
+        }
+        pv[jj][4 * v] = p4.x, pv[jj][4 * v + 1] = p4.y, pv[jj][4 * v + 2] = p4.z, pv[jj][4 * v + 3] = p4.w;
+        yv[jj][4 * v] = y4.x, yv[jj][4 * v + 1] = y4.y, yv[jj][4 * v + 2] = y4.z, yv[jj][4 * v + 3] = y4.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool in = j < a.T && L.p0[v] + e < a.npix;
+          pv[jj][4 * v + e] = in ? pred[off + e] : 0.f;
+          yv[jj][4 * v + e] = in ? y[off + e] : 0.f;
+        }
+      }
+    }
+  }
+}
+
+// One band of this lane's pixels: the angle sums, and the lane's partial of each group into slot `slot` of the join.
+// Products of two float32 values are exact in float64, so fma(x, y, s) below carries the bits of s + x * y.
+template <int kGroups>
+__device__ __forceinline__ void score_band(const float (&pv)[kScoreLanePix], const float (&yv)[kScoreLanePix], bool live, ScoreLane& L,
+                                           RepStat* part, int slot) {
+  const int lane = threadIdx.x;
+  int n[kGroups];
+  double sy[kGroups], sd[kGroups];
+  bool in[kGroups][kScoreLanePix];
+#pragma unroll
+  for (int g = 0; g < kGroups; ++g) n[g] = 0, sy[g] = 0.0, sd[g] = 0.0;
+#pragma unroll
+  for (int e = 0; e < kScoreLanePix; ++e) {
+    const float pe = pv[e], ye = yv[e];
+    const bool f = live && __builtin_isfinite(pe) && __builtin_isfinite(ye);   // a band past T: empty partials
+    const float d = ye - pe;
+#pragma unroll
+    for (int g = 0; g < kGroups; ++g) {
+      const bool s = f && L.grp[e] == g + 1;
+      in[g][e] = s;
+      const float ds = s ? d : 0.f, ys = s ? ye : 0.f;
+      n[g] += s ? 1 : 0;
+      sy[g] += (double)ys;
+      sd[g] = fma((double)ds, (double)ds, sd[g]);
+    }
+    const double y64 = ye, p64 = pe;                   // a band past T adds exact zeros
+    L.dot[e] = fma(y64, p64, L.dot[e]);
+    L.sa[e] = fma(y64, y64, L.sa[e]);
+    L.sb[e] = fma(p64, p64, L.sb[e]);
+  }
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    RepStat r{0.0, 0.0, 0.0, 0.0};
+    if (g < kGroups) {
+      const int gi = g < kGroups ? g : 0;
+      const double nn = (double)n[gi];
+      const double mu = nn > 0.0 ? sy[gi] / nn : 0.0;
+      double m2 = 0.0;
+#pragma unroll
+      for (int e = 0; e < kScoreLanePix; ++e) {
+        const double c = in[gi][e] ? (double)yv[e] - mu : 0.0;
+        m2 = fma(c, c, m2);
+      }
+      r = RepStat{sd[gi], nn, mu, m2};
+    }
+    part[(slot * 2 + g) * kScorePitch + lane + (lane >> 3)] = r;
+  }
+}
+
+// The walk over the bands for kGroups = 1 (no held-out pixel in the chunk: group 2's partials are empty without being computed)
+// or 2.  Bands are loaded two at a time, one pair of bands ahead of the arithmetic, and joined four at a time.
+template <bool kVec, int kGroups>
+__device__ __forceinline__ void score_walk(const PairScoreArgs& a, const float* __restrict__ pred, const float* __restrict__ y,
+                                           double* __restrict__ work, RepStat* part, ScoreLane& L) {
+  const int chunk = blockIdx.x, lane = threadIdx.x;
+  const int jb = lane >> 4, jg = (lane >> 3) & 1, seg = lane & 7;
+  float pa[kScoreHalf][kScoreLanePix], ya[kScoreHalf][kScoreLanePix], pb[kScoreHalf][kScoreLanePix], yb[kScoreHalf][kScoreLanePix];
+  score_load<kVec>(a, pred, y, L, 0, pa, ya);
+  for (int j0 = 0; j0 < a.T; j0 += kScoreBands) {
+    score_load<kVec>(a, pred, y, L, j0 + 2, pb, yb);
+    __syncthreads();                                   // the previous join has read its partials
+    score_band<kGroups>(pa[0], ya[0], j0 < a.T, L, part, 0);
+    score_band<kGroups>(pa[1], ya[1], j0 + 1 < a.T, L, part, 1);
+    score_load<kVec>(a, pred, y, L, j0 + 4, pa, ya);
+    score_band<kGroups>(pb[0], yb[0], j0 + 2 < a.T, L, part, 2);
+    score_band<kGroups>(pb[1], yb[1], j0 + 3 < a.T, L, part, 3);
+    __syncthreads();
+    const RepStat* src = part + (jb * 2 + jg) * kScorePitch + 9 * seg;
+    RepStat r = src[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) r = score_merge(r, src[i]);
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {            // segment 0 ends with ((0 1)(2 3))((4 5)(6 7))
+      const RepStat o{__shfl_down(r.sd, off, 64), __shfl_down(r.n, off, 64), __shfl_down(r.mu, off, 64), __shfl_down(r.m2, off, 64)};
+      r = score_merge(r, o);
+    }
+    if (seg == 0 && j0 + jb < a.T) {
+      double* out = work + (((int64_t)chunk * a.T + j0 + jb) * 2 + jg) * 4;
+      out[0] = r.sd;
+      out[1] = r.n;
+      out[2] = r.mu;
+      out[3] = r.m2;
+    }
+  }
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(64) void pair_score_partial_kernel(const PairScoreArgs a) {
+  __shared__ __attribute__((aligned(16))) RepStat part[kScoreBands * 2 * kScorePitch];
+  const int64_t pr = blockIdx.y;
+  const int chunk = blockIdx.x, lane = threadIdx.x;
+  const float* pred = a.pred + pr * a.pair_pred;
+  const float* y = a.y + pr * a.pair_y;
+  const uint8_t* group = a.group + pr * a.pair_group;
+  double* work = a.work + pr * a.pair_work;
+  // pixel e of vector v of this lane: chunk kScorePix + 256 v + 4 lane + e
+  ScoreLane L;
+#pragma unroll
+  for (int v = 0; v < kScoreVec; ++v) {
+    L.p0[v] = (int64_t)chunk * kScorePix + 256 * v + 4 * lane;
+    if (kVec) {                                        // npix % 4 == 0: a vector is inside or outside as a whole
+      uchar4 g4 = make_uchar4(0, 0, 0, 0);
+      if (L.p0[v] < a.npix) g4 = *reinterpret_cast<const uchar4*>(group + L.p0[v]);
+      L.grp[4 * v] = g4.x;
+      L.grp[4 * v + 1] = g4.y;
+      L.grp[4 * v + 2] = g4.z;
+      L.grp[4 * v + 3] = g4.w;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) L.grp[4 * v + e] = L.p0[v] + e < a.npix ? group[L.p0[v] + e] : 0;
+    }
+  }
+  bool held = false;
+#pragma unroll
+  for (int e = 0; e < kScoreLanePix; ++e) {
+    L.grp[e] = L.grp[e] == 1 || L.grp[e] == 2 ? L.grp[e] : 0;
+    held = held || L.grp[e] == 2;
+    L.dot[e] = L.sa[e] = L.sb[e] = 0.0;
+  }
+  if (__ballot(held) != 0)                             // the same for the whole wave
+    score_walk<kVec, 2>(a, pred, y, work, part, L);
+  else
+    score_walk<kVec, 1>(a, pred, y, work, part, L);
+  // spectral angles of this lane's pixels: a non-finite value in any band has made sa or sb non-finite
+  double asum[2] = {0.0, 0.0}, acnt[2] = {0.0, 0.0};
+  float ang32[kScoreLanePix];
+#pragma unroll
+  for (int e = 0; e < kScoreLanePix; ++e) {
+    ang32[e] = __builtin_nanf("");
+    if (L.grp[e] != 0 && __builtin_isfinite(L.sa[e]) && __builtin_isfinite(L.sb[e]) && L.sa[e] > 0.0 && L.sb[e] > 0.0) {
+      double c = L.dot[e] / sqrt(L.sa[e] * L.sb[e]);
+      c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+      const double ang = acos(c) * (180.0 / 3.14159265358979323846);
+      ang32[e] = (float)ang;
+      asum[L.grp[e] - 1] += ang;
+      acnt[L.grp[e] - 1] += 1.0;
+    }
+  }
+  float* map = a.sam_map + pr * a.pair_map;
+#pragma unroll
+  for (int v = 0; v < kScoreVec; ++v) {
+    if (kVec) {
+      if (L.p0[v] < a.npix)
+        *reinterpret_cast<float4*>(map + L.p0[v]) = make_float4(ang32[4 * v], ang32[4 * v + 1], ang32[4 * v + 2], ang32[4 * v + 3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (L.p0[v] + e < a.npix) map[L.p0[v] + e] = ang32[4 * v + e];
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    asum[g] = wave_sum(asum[g]);
+    acnt[g] = wave_sum(acnt[g]);
+  }
+  if (lane == 0) {
+    double* out = work + (int64_t)a.chunks * a.T * 8 + (int64_t)chunk * 4;
+    out[0] = asum[0];
+    out[1] = acnt[0];
+    out[2] = asum[1];
+    out[3] = acnt[1];
+  }
+}
+
+struct PairScoreOut {
+  int64_t* n;                          // (P, pair_out): [group][T]
+  double* rmse;
+  double* r2;
+  double* mean_ref;
+  double* sam;                         // (P, pair_sam): [group]
+  int64_t* n_sam;
+  double* ergas;
+  int64_t pair_out, pair_sam;
+};
+
+constexpr int kScoreFinishThreads = 512;
+constexpr int kScoreFinishAhead = 4;   // chunks whose partials are loaded before their merges: the loads do not wait for the chain
+
+__global__ __launch_bounds__(kScoreFinishThreads) void pair_score_finish_kernel(const double* __restrict__ work, int64_t pair_work,
+                                                                                 int chunks, int T, double ergas_scale,
+                                                                                 const PairScoreOut o) {
+  __shared__ double red[2][2][kScoreFinishThreads / 64];
+  const int64_t pr = blockIdx.x;
+  work += pr * pair_work;
+  const double nan = __builtin_nan("");
+  double es[2] = {0.0, 0.0}, ec[2] = {0.0, 0.0};
+  for (int j = threadIdx.x; j < T; j += kScoreFinishThreads) {
+    RepStat r[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+    for (int c0 = 0; c0 < chunks; c0 += kScoreFinishAhead) {
+      double2 buf[kScoreFinishAhead][4];                 // [chunk][group 0: sd n | mu m2 | group 1: sd n | mu m2]
+#pragma unroll
+      for (int u = 0; u < kScoreFinishAhead; ++u)
+        if (c0 + u < chunks) {
+          const double2* p = reinterpret_cast<const double2*>(work + ((int64_t)(c0 + u) * T + j) * 8);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) buf[u][q] = p[q];
+        }
+#pragma unroll
+      for (int u = 0; u < kScoreFinishAhead; ++u)
+        if (c0 + u < chunks) {
+#pragma unroll
+          for (int g = 0; g < 2; ++g)
+            r[g] = score_merge(r[g], RepStat{buf[u][2 * g].x, buf[u][2 * g].y, buf[u][2 * g + 1].x, buf[u][2 * g + 1].y});
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const bool ok = r[g].n > 0.0;
+      const double rm = ok ? sqrt(r[g].sd / r[g].n) : nan;
+      const int64_t at = pr * o.pair_out + (int64_t)g * T + j;
+      o.n[at] = (int64_t)r[g].n;
+      o.rmse[at] = rm;
+      o.r2[at] = ok ? 1.0 - r[g].sd / (r[g].m2 + 1e-8) : nan;
+      o.mean_ref[at] = ok ? r[g].mu : nan;
+      if (ok && r[g].mu != 0.0) {
+        const double q = rm / r[g].mu;
+        es[g] += q * q;
+        ec[g] += 1.0;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int g = 0; g < 2; ++g) {
+    const double s = wave_sum(es[g]), c = wave_sum(ec[g]);
+    if (lane == 0) {
+      red[g][0][wave] = s;
+      red[g][1][wave] = c;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int g = threadIdx.x;
+    double s = 0.0, c = 0.0;
+    for (int w = 0; w < kScoreFinishThreads / 64; ++w) {
+      s += red[g][0][w];
+      c += red[g][1][w];
+    }
+    o.ergas[pr * o.pair_sam + g] = c > 0.0 ? ergas_scale * sqrt(s / c) : nan;
+    const double* ap = work + (int64_t)chunks * T * 8;
+    double as = 0.0, an = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) {
+      as += ap[(int64_t)ch * 4 + 2 * g];
+      an += ap[(int64_t)ch * 4 + 2 * g + 1];
+    }
+    o.sam[pr * o.pair_sam + g] = an > 0.0 ? as / an : nan;
+    o.n_sam[pr * o.pair_sam + g] = (int64_t)an;
+  }
+}
+
 }  // namespace hsr
 
 using namespace hsr;
@@ -366,5 +708,59 @@ extern "C" int hsr_pair_report_f64(const double* q_dev, int64_t ldq, int64_t pai
   hipLaunchKernelGGL(pair_report_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, (hipStream_t)stream, work_dev,
                      pair_work, (int)chunks, T, status_dev, r2_dev, rmse_dev, pair_out);
   HSR_LAUNCH_CHECK("pair_report_finish_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_pair_holdout(const uint8_t* valid_dev, const uint8_t* train_dev, int64_t pair_train, int64_t npix,
+                                uint8_t* mask_dev, uint8_t* group_dev, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(valid_dev && train_dev && mask_dev && group_dev, HSR_ERR_INVALID, "hsr_pair_holdout: NULL pointer");
+  HSR_REQUIRE(npix >= 1 && npix <= (int64_t)0x7fffffff * 256 && npairs >= 1 && npairs <= 65535 && (npairs == 1 || pair_train >= npix),
+              HSR_ERR_INVALID, "hsr_pair_holdout: bad shape (npix=%lld pair_train=%lld P=%d)", (long long)npix, (long long)pair_train,
+              npairs);
+  hipLaunchKernelGGL(pair_holdout_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)npairs), dim3(256), 0, (hipStream_t)stream,
+                     valid_dev, train_dev, pair_train, npix, mask_dev, group_dev);
+  HSR_LAUNCH_CHECK("pair_holdout_kernel");
+  return HSR_OK;
+}
+
+extern "C" size_t hsr_pair_score_work_bytes(int64_t npix, int32_t T) {
+  if (npix < 1 || T < 1) return 0;
+  return (size_t)((npix + kScorePix - 1) / kScorePix) * ((size_t)T * 8 + 4) * sizeof(double);
+}
+
+extern "C" int hsr_pair_score_f64(const float* pred_dev, int64_t pair_pred, const float* y_dev, int64_t pair_y,
+                                  const uint8_t* group_dev, int64_t pair_group, int64_t npix, int32_t T, double ergas_scale,
+                                  double* work_dev, int64_t pair_work, int64_t* n_dev, double* rmse_dev, double* r2_dev,
+                                  double* mean_ref_dev, int64_t pair_out, double* sam_dev, int64_t* n_sam_dev, double* ergas_dev,
+                                  int64_t pair_sam, float* sam_map_dev, int64_t pair_map, int32_t npairs, hsr_stream_t stream) {
+  HSR_REQUIRE(pred_dev && y_dev && group_dev && work_dev && n_dev && rmse_dev && r2_dev && mean_ref_dev && sam_dev && n_sam_dev &&
+              ergas_dev && sam_map_dev, HSR_ERR_INVALID, "hsr_pair_score_f64: NULL pointer");
+  HSR_REQUIRE(npix >= 1 && T >= 1 && npairs >= 1 && npairs <= 65535, HSR_ERR_INVALID,
+              "hsr_pair_score_f64: bad shape (npix=%lld T=%d P=%d)", (long long)npix, T, npairs);
+  const int64_t chunks = (npix + kScorePix - 1) / kScorePix;
+  HSR_REQUIRE(chunks <= 0x7fffffff, HSR_ERR_UNSUPPORTED, "hsr_pair_score_f64: npix=%lld too large", (long long)npix);
+  HSR_REQUIRE(pair_work >= chunks * ((int64_t)T * 8 + 4), HSR_ERR_INVALID,
+              "hsr_pair_score_f64: pair_work below hsr_pair_score_work_bytes / 8");
+  HSR_REQUIRE(((uintptr_t)work_dev & 15) == 0 && pair_work % 2 == 0, HSR_ERR_UNSUPPORTED,
+              "hsr_pair_score_f64: needs a 16-byte aligned workspace and an even pair_work");
+  HSR_REQUIRE(npairs == 1 || (pair_pred >= (int64_t)T * npix && pair_y >= (int64_t)T * npix && pair_group >= npix &&
+                              pair_out >= 2 * (int64_t)T && pair_sam >= 2 && pair_map >= npix),
+              HSR_ERR_INVALID, "hsr_pair_score_f64: pair strides overlap");
+  PairScoreArgs a{pred_dev, y_dev, group_dev, work_dev, sam_map_dev, pair_pred, pair_y, pair_group, pair_work, pair_map, npix, T,
+                  (int32_t)chunks};
+  // 16-byte loads and stores need band rows that start 16-byte aligned in every array; anything else takes the plain instance
+  const bool vec = npix % 4 == 0 && pair_pred % 4 == 0 && pair_y % 4 == 0 && pair_group % 4 == 0 && pair_map % 4 == 0 &&
+                   ((uintptr_t)pred_dev & 15) == 0 && ((uintptr_t)y_dev & 15) == 0 && ((uintptr_t)group_dev & 3) == 0 &&
+                   ((uintptr_t)sam_map_dev & 15) == 0;
+  const dim3 grid((unsigned)chunks, (unsigned)npairs);
+  if (vec)
+    hipLaunchKernelGGL(pair_score_partial_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(pair_score_partial_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a);
+  HSR_LAUNCH_CHECK("pair_score_partial_kernel");
+  const PairScoreOut o{n_dev, rmse_dev, r2_dev, mean_ref_dev, sam_dev, n_sam_dev, ergas_dev, pair_out, pair_sam};
+  hipLaunchKernelGGL(pair_score_finish_kernel, dim3((unsigned)npairs), dim3(kScoreFinishThreads), 0, (hipStream_t)stream, work_dev, pair_work,
+                     (int)chunks, T, ergas_scale, o);
+  HSR_LAUNCH_CHECK("pair_score_finish_kernel");
   return HSR_OK;
 }

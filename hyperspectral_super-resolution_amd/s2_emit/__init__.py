@@ -16,7 +16,7 @@ from .color import (
 from .poly_regression import fit_ot_poly_rgb, apply_poly_rgb
 from .fusion import SpectralFusion, fuse_pair, match_pair, calibrate_pseudo_to_real_linear
 from .ridge import PolyRidge, predict_cube_logit, flatten_pixels, subsample_bands_evenly
-from .pairs import TilePairOutput, fuse_tile_pair, fuse_tile_pairs
+from .pairs import TilePairOutput, TilePairValidation, fuse_tile_pair, fuse_tile_pairs
 from ._native import HsrUnavailable, HsrError
 
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
@@ -30,5 +30,5 @@ _REFERENCE_SURFACE = (
 _COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb"]
 _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real_linear",
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
-          "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput"]
+          "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation"]
 __all__ = _REFERENCE_SURFACE + _COPIED_BY_CALLERS + _FUSED

@@ -10,7 +10,9 @@ Here the whole flow of P pairs of one shape is a fixed number of launches on the
 (csrc/hsr_pairs.hip, csrc/hsr_ridge.hip, csrc/hsr_chol.hip): pair prep (block mean, band gather and decode, training mask),
 masked scaler statistics, masked expand, Gram, assembly, P Cholesky factorisations side by side, model read-out and the
 10 m prediction; with ``report=True`` two more launches score each fit on its own training pixels (the notebook's cell 26:
-per-band R^2 and RMSE of sigmoid(model(X_train)) against the raw targets).  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
+per-band R^2 and RMSE of sigmoid(model(X_train)) against the raw targets).  ``train_mask`` keeps pixels out of the fit (one more
+launch) and ``validate=True`` scores the result against the EMIT tile on the fit and the held-out pixels, for the model applied
+to S2 on the EMIT grid and for the 10 m cube averaged back to it (see ``TilePairValidation``).  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
 does not depend on the batch: ``fuse_tile_pairs`` of a batch gives the bits of ``fuse_tile_pair`` of each of its pairs.
 
 S2 -> EMIT grid: an f x f block mean (float64 sum of the f^2 samples, stored as float32: the bits of ``hsr_block_mean``);
@@ -32,6 +34,9 @@ from .ridge import PolyRidge, check_fit_features, subsample_bands_evenly
 
 _DTYPES = {"uint16": 2, "float32": 0}      # hsr_pair_prep's dtype codes
 _MAX_FACTOR = 64                           # hsr_pair_prep's bound on the S2 / EMIT pixel ratio
+_MAX_PLANES = 65535                        # hsr_block_mean's bound on the planes of one call
+VIEWS = ("coarse", "degraded")
+GROUPS = ("fit", "held_out")
 
 
 def _is_torch(x) -> bool:
@@ -89,12 +94,25 @@ class _Plan:
     bands: np.ndarray
     emit_dtype: str
     s2_dtype: str
+    plane_slices: tuple = ()
 
 
-def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
-    """Every check that needs no GPU: shapes, dtypes, the factor, the bands, the size of the ridge system and the report flag."""
+def _plane_slices(P: int, T: int, limit: int = _MAX_PLANES):
+    """The pairs [p0, p1) of each hsr_block_mean call over a (P, T, ...) cube seen as P T planes: whole pairs, at most ``limit``
+    planes a call, so the number of calls is ceil(P / floor(limit / T))."""
+    if not 1 <= T <= limit:
+        raise ValueError(f"validate: {T} target bands, the block mean takes at most {limit} planes a call")
+    step = limit // T
+    return tuple((p0, min(p0 + step, P)) for p0 in range(0, P, step))
+
+
+def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False, train_mask=None, validate=False) -> _Plan:
+    """Every check that needs no GPU: shapes, dtypes, the factor, the bands, the size of the ridge system, the report and
+    validate flags and the training mask."""
     if not isinstance(report, bool):
         raise ValueError(f"report={report!r}: must be True or False")
+    if not isinstance(validate, bool):
+        raise ValueError(f"validate={validate!r}: must be True or False")
     try:
         f = operator.index(factor)
     except TypeError:
@@ -120,7 +138,12 @@ def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False) -> _Plan:
         cshape, cdt = _describe(s2_coarse, "s2_coarse", 3)
         if cshape != (P, nb, h, w) or cdt != "float32":
             raise ValueError(f"s2_coarse: expected float32 {(P, nb, h, w)}, got {cdt} {cshape}")
-    return _Plan(P, B, h, w, nb, f, _bands_index(bands, B), edt, sdt)
+    if train_mask is not None:
+        mshape, mdt = _describe(train_mask, "train_mask", 2)
+        if mshape != (P, h, w) or mdt not in ("bool", "uint8"):
+            raise ValueError(f"train_mask: expected bool or uint8 {(P, h, w)}, got {mdt} {mshape}")
+    idx = _bands_index(bands, B)
+    return _Plan(P, B, h, w, nb, f, idx, edt, sdt, _plane_slices(P, len(idx)) if validate else ())
 
 
 def _stack_dev(x, torch, dev):
@@ -157,16 +180,51 @@ def _bands_dev(idx: np.ndarray, torch, dev):
 
 
 @dataclass
+class TilePairValidation:
+    """``fuse_tile_pairs(validate=True).validation`` (device tensors): two views of the prediction on the EMIT grid, each scored
+    against the decoded EMIT targets for two groups of pixels.  Axes V = ``views``, G = ``groups``.
+
+    views    ("coarse", "degraded"): the pair's model applied to ``s2_coarse`` (what the fit was trained to do), and the 10 m
+             ``cube`` averaged over each f x f block (``hsr_block_mean``'s arithmetic; a NaN sample makes the block NaN) - the
+             consistency half of Wald's protocol;
+    groups   ("fit", "held_out"): ``mask``, and ``held_out`` = ``valid & ~train_mask``;
+    pred_coarse, cube_coarse  (P, T, h, w) float32, the two views themselves;
+    n        (P, V, G, T) int64, the group's pixels with a finite prediction and target in the band;
+    rmse, r2, mean_ref  (P, V, G, T) float64 over those: d = y - p in float32, rmse = sqrt(mean d^2), mean_ref = mean y,
+             r2 = 1 - sum d^2 / (sum (y - mean_ref)^2 + 1e-8), sums in float64; NaN where n == 0;
+    sam, n_sam  (P, V, G) float64 / int64: the mean spectral angle in degrees over the group's pixels that have one (every band
+             of prediction and target finite, neither spectrum zero) and their count;
+    ergas    (P, V, G) float64 = 100 / factor * sqrt(mean over the bands with n > 0 and mean_ref != 0 of (rmse / mean_ref)^2);
+    sam_map  (P, V, h, w) float32, the angle of every such pixel, NaN elsewhere.
+    A pair with ``status != 0`` has an all-NaN cube: n = 0 and NaN throughout."""
+    pred_coarse: Any
+    cube_coarse: Any
+    n: Any
+    rmse: Any
+    r2: Any
+    mean_ref: Any
+    sam: Any
+    n_sam: Any
+    ergas: Any
+    sam_map: Any
+    views: tuple = VIEWS
+    groups: tuple = GROUPS
+
+
+@dataclass
 class TilePairOutput:
     """What ``fuse_tile_pairs`` returns (device tensors, nothing copied to the host):
 
     cube     (P, T, h f, w f) float32 = sigmoid(clip(model(S2 at 10 m), +-50)), NaN where predict_cube_logit leaves NaN (a
              non-finite or ``s2_nodata`` input) and everywhere for a pair without training pixels;
-    n_train  (P,) int64, the pixels that survived the flatten rule;
+    n_train  (P,) int64, the pixels the fit used: those that survived the flatten rule and, if given, ``train_mask``;
     status   (P,) int32: 0 fitted, 1 no training pixel, 2 non-positive Cholesky pivot (e.g. alpha = 0 and training pixels
              that all carry one S2 vector); a pair with status != 0 has NaN intercepts (``model(i).intercept_``), an all-NaN
              cube and NaN ``r2`` / ``rmse``, while its other fit outputs are whatever the failed solve left;
-    mask     (P, h, w) bool, the training mask (flatten_pixels' rule on the EMIT grid);
+    mask     (P, h, w) bool, the pixels the fit used: ``valid & train_mask``;
+    valid    (P, h, w) bool, flatten_pixels' rule on the EMIT grid (equal to ``mask`` without a ``train_mask``);
+    held_out (P, h, w) bool = ``valid & ~train_mask`` (all False without a ``train_mask``);
+    validation  a ``TilePairValidation`` with ``validate=True`` (else None);
     s2_coarse (P, nb, h, w) float32, S2 on the EMIT grid as the fit saw it (the block mean, or the caller's ``s2_coarse``);
     bands    (T,) the EMIT band indices of the targets;
     r2, rmse (P, T) float64 with ``report=True`` (else None): the fit scored on its own training pixels as the notebook's cell 26
@@ -184,6 +242,9 @@ class TilePairOutput:
     _fit: dict = field(repr=False, default_factory=dict)
     r2: Any = None
     rmse: Any = None
+    valid: Any = None
+    held_out: Any = None
+    validation: Optional[TilePairValidation] = None
 
     def model(self, i: int) -> PolyRidge:
         f = self._fit
@@ -196,7 +257,7 @@ class TilePairOutput:
 
 def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                     emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                    eps: float = 1e-4, report: bool = False) -> TilePairOutput:
+                    eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False) -> TilePairOutput:
     """P tile pairs -> their fused 10 m cubes (see the module docstring).
 
     emits: (P, bands, h, w) uint16 (decoded as ``u == 65535 ? NaN : float32(u) * 1e-4f``) or float32 reflectance (with an
@@ -204,8 +265,12 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     ``s2_nodata``).  Device tensors, NumPy arrays (copied once) or lists of per-pair cubes (stacked on the device).
     bands: an int (evenly subsampled, ``subsample_bands_evenly``), an index array or ``"all"``.
     report: also score every pair's fit on its training pixels (``r2`` / ``rmse`` of the output); two more launches, no host
-    sync, and every other output keeps the bits it has without the report."""
-    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse, report)
+    sync, and every other output keeps the bits it has without the report.
+    train_mask: (P, h, w) bool / uint8 (array, tensor or list of (h, w) ones): the fit uses ``valid & train_mask``; ``n_train``,
+    ``status`` and the report follow that mask, the other valid pixels are ``held_out``.
+    validate: also score the prediction against the EMIT tile (``validation``, see ``TilePairValidation``); a fixed number of
+    launches more, no host sync, and every other output keeps its bits."""
+    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse, report, train_mask, validate)
     torch = nat.require_gpu()
     lib = nat.load()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -214,6 +279,7 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     E = _stack_dev(emits, torch, dev)
     S = _stack_dev(s2s, torch, dev)
     Sc = _stack_dev(s2_coarse, torch, dev) if s2_coarse is not None else None
+    Tm = _stack_dev(train_mask, torch, dev) if train_mask is not None else None
     st = _stream(torch)
     nat.check(lib.hsr_polyfeat_prepare(nb, int(degree)), "hsr_polyfeat_prepare")
     nf = lib.hsr_polyfeat_count(nb, int(degree))
@@ -233,6 +299,12 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
                                 T, _ptr(src), src_dt, pair_s, nb, h, w, fac, 0.0 if emit_nodata is None else float(emit_nodata),
                                 0 if emit_nodata is None else 1, 0.0 if s2_nodata is None else float(s2_nodata),
                                 0 if s2_nodata is None else 1, _ptr(x), _ptr(y), _ptr(mask), P, st), "hsr_pair_prep")
+    valid = group = mask                               # without a train_mask: one array, codes 0 / 1
+    if Tm is not None:                                 # the fit's mask = the rule's & the caller's; 1 fit, 2 held out
+        Tm = Tm.view(torch.uint8) if Tm.dtype == torch.bool else Tm
+        mask = torch.empty_like(valid)
+        group = torch.empty_like(valid)
+        nat.check(lib.hsr_pair_holdout(_ptr(valid), _ptr(Tm), npix, npix, _ptr(mask), _ptr(group), P, st), "hsr_pair_holdout")
     # 2. StandardScaler over the training pixels
     stats = torch.empty((P, 1 + 2 * nb), **f64)
     mean = torch.empty((P, nb), **f64)
@@ -288,17 +360,61 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
                                                     int(degree), _ptr(W32), T, kpad * T, _ptr(b32), T, T, 1, 1,
                                                     0.0 if s2_nodata is None else float(s2_nodata), 0 if s2_nodata is None else 1,
                                                     _ptr(cube), npix10, T * npix10, P, st), "hsr_polyfeat_predict_cube_batched")
+    validation = None
+    if validate:
+        validation = _validate(lib, torch, st, plan, x, y, group, cube, mean32, inv32, W32, b32, kpad, int(degree), s2_nodata)
+    held = (group == 2) if Tm is not None else torch.zeros_like(mask, dtype=torch.bool)
     fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
-    return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask.view(P, h, w).bool(),
+    mask_b = mask.view(P, h, w).bool()
+    valid_b = mask_b if Tm is None else valid.view(P, h, w).bool()
+    return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask_b,
                           s2_coarse=x.view(P, nb, h, w), bands=plan.bands, degree=int(degree), alpha=float(alpha), _fit=fit,
-                          r2=r2, rmse=rmse)
+                          r2=r2, rmse=rmse, valid=valid_b, held_out=held.view(P, h, w), validation=validation)
+
+
+def _validate(lib, torch, st, plan, x, y, group, cube, mean32, inv32, W32, b32, kpad, degree, s2_nodata) -> TilePairValidation:
+    """The two views on the EMIT grid and their scores: one predict launch, one block mean per slice of planes, two launches per
+    view (csrc/hsr_pairs.hip); the launch count depends on ceil(P T / 65535) only."""
+    P, nb, h, w, f = plan.P, plan.nb, plan.h, plan.w, plan.factor
+    T, npix, npix10 = len(plan.bands), h * w, h * w * f * f
+    dev = x.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    i64 = dict(dtype=torch.int64, device=dev)
+    views = torch.empty((2, P, T, npix), dtype=torch.float32, device=dev)
+    pred, coarse = views[0], views[1]
+    nat.check(lib.hsr_polyfeat_predict_cube_batched(_ptr(x), 1, npix, nb * npix, _ptr(mean32), _ptr(inv32), nb, npix, nb, degree,
+                                                    _ptr(W32), T, kpad * T, _ptr(b32), T, T, 1, 1,
+                                                    0.0 if s2_nodata is None else float(s2_nodata), 0 if s2_nodata is None else 1,
+                                                    _ptr(pred), npix, T * npix, P, st), "hsr_polyfeat_predict_cube_batched")
+    for p0, p1 in plan.plane_slices:
+        nat.check(lib.hsr_block_mean(_ptr(cube[p0:p1]), 0, npix10, 1, (p1 - p0) * T, h, w, f, 1.0, _ptr(coarse[p0:p1]), npix, 1, st),
+                  "hsr_block_mean")
+    V, G = len(VIEWS), len(GROUPS)
+    n = torch.empty((P, V, G, T), **i64)
+    rmse = torch.empty((P, V, G, T), **f64)
+    r2 = torch.empty((P, V, G, T), **f64)
+    mean_ref = torch.empty((P, V, G, T), **f64)
+    sam = torch.empty((P, V, G), **f64)
+    n_sam = torch.empty((P, V, G), **i64)
+    ergas = torch.empty((P, V, G), **f64)
+    sam_map = torch.empty((P, V, npix), dtype=torch.float32, device=dev)
+    sw = lib.hsr_pair_score_work_bytes(npix, T) // 8
+    work = torch.empty((P, sw), **f64)
+    for v in range(V):
+        nat.check(lib.hsr_pair_score_f64(_ptr(views[v]), T * npix, _ptr(y), T * npix, _ptr(group), npix, npix, T, 100.0 / f,
+                                         _ptr(work), sw, _ptr(n[:, v]), _ptr(rmse[:, v]), _ptr(r2[:, v]), _ptr(mean_ref[:, v]),
+                                         V * G * T, _ptr(sam[:, v]), _ptr(n_sam[:, v]), _ptr(ergas[:, v]), V * G,
+                                         _ptr(sam_map[:, v]), V * npix, P, st), "hsr_pair_score_f64")
+    return TilePairValidation(pred_coarse=pred.view(P, T, h, w), cube_coarse=coarse.view(P, T, h, w), n=n, rmse=rmse, r2=r2,
+                              mean_ref=mean_ref, sam=sam, n_sam=n_sam, ergas=ergas, sam_map=sam_map.view(P, V, h, w))
 
 
 def fuse_tile_pair(emit, s2, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                    emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                   eps: float = 1e-4, report: bool = False) -> TilePairOutput:
+                   eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False) -> TilePairOutput:
     """One tile pair: emit (bands, h, w), s2 (nb, h f, w f) -> a TilePairOutput with P = 1 (``cube[0]`` is (T, h f, w f)).
     The same launches as ``fuse_tile_pairs``, so a pair gives the same bits alone as in any batch."""
     batch = lambda a: None if a is None else ([a] if not _is_torch(a) and not isinstance(a, np.ndarray) else a[None])
     return fuse_tile_pairs(batch(emit), batch(s2), bands=bands, degree=degree, alpha=alpha, factor=factor,
-                           emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps, report=report)
+                           emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps, report=report,
+                           train_mask=batch(train_mask), validate=validate)

@@ -548,6 +548,30 @@ int hsr_pair_report_f64(const double* q_dev, int64_t ldq, int64_t pair_q, int32_
                         double* work_dev, int64_t pair_work, double* r2_dev, double* rmse_dev, int64_t pair_out, int32_t npairs,
                         hsr_stream_t stream);
 
+/* ---- tile pairs: hold-out and validation (s2_emit.fuse_tile_pairs(train_mask=..., validate=True)) ------------------------------
+ * hsr_pair_holdout: valid (P, npix) is hsr_pair_prep's mask, train (P, npix; pair stride pair_train) the caller's (non-zero = may
+ *   train): mask (P, npix) = valid & train, the fit's mask, and group (P, npix) = 1 fit, 2 held out (valid & !train), 0 neither.
+ * hsr_pair_score_f64: ONE view of the prediction on the EMIT grid, pred (P, T, npix) float32 with band stride npix, against the
+ *   decoded targets y (P, T, npix), for both groups of group (P, npix; other codes count as 0) in one pass over pred and y.
+ *   Per band j and group g, over S = the group's pixels with pred and y finite: d = y - pred in float32, ss_res = sum d^2,
+ *   n = |S|, mean_ref / M2 = mean and centred sum of squares of y over S (float64; equal targets give M2 == 0 exactly),
+ *   rmse = sqrt(ss_res / n), r2 = 1 - ss_res / (M2 + 1e-8); n == 0 -> NaN.  n (int64), rmse, r2, mean_ref: (P, pair_out) arrays
+ *   written at [g * T + j], pair_out >= 2 T.  Per pixel of a group whose T values of pred and y are all finite, with
+ *   a = sum y^2 > 0 and b = sum pred^2 > 0 (float64, band order): angle = acos(clamp(sum y pred / sqrt(a b), -1, 1)) * 180 / pi;
+ *   sam_map (P, pair_map) = float32(angle), NaN for every other pixel; sam[g] = the float64 mean of a group's angles, n_sam[g]
+ *   their count (int64), ergas[g] = ergas_scale * sqrt(mean over the bands with n > 0 and mean_ref != 0 of (rmse / mean_ref)^2),
+ *   NaN without such a band: (P, pair_sam) arrays written at [g], pair_sam >= 2.  Two launches; 512-pixel chunks merged in
+ *   index order, so a pair's numbers do not depend on its batch.  16-byte loads when npix and the pair strides are multiples
+ *   of 4 and the bases aligned, else a plain instance with the same bits.  pair_work >= hsr_pair_score_work_bytes(npix, T) / 8. */
+int hsr_pair_holdout(const uint8_t* valid_dev, const uint8_t* train_dev, int64_t pair_train, int64_t npix, uint8_t* mask_dev,
+                     uint8_t* group_dev, int32_t npairs, hsr_stream_t stream);
+size_t hsr_pair_score_work_bytes(int64_t npix, int32_t T);
+int hsr_pair_score_f64(const float* pred_dev, int64_t pair_pred, const float* y_dev, int64_t pair_y, const uint8_t* group_dev,
+                       int64_t pair_group, int64_t npix, int32_t T, double ergas_scale, double* work_dev, int64_t pair_work,
+                       int64_t* n_dev, double* rmse_dev, double* r2_dev, double* mean_ref_dev, int64_t pair_out, double* sam_dev,
+                       int64_t* n_sam_dev, double* ergas_dev, int64_t pair_sam, float* sam_map_dev, int64_t pair_map,
+                       int32_t npairs, hsr_stream_t stream);
+
 /* ---- f1: grid-aligned resamplers between the phases -----------------------------------------------
  * downsample_s2_to_grid ('average') and reproject_stack_to_grid ('bilinear') of the notebook
  * (Pairs_EMIT_S2_demo-2.ipynb cell 73, raw lines 4538-4599) for exactly aligned integer-factor grids:

@@ -4,6 +4,8 @@
     python tools/bench_tile_pairs.py --profile DIR         # the same under rocprofv3 --kernel-trace --stats (kernel times)
     python tools/bench_tile_pairs.py --report              # report=False vs report=True at P = 64, T = 32 and T = 285
     python tools/bench_tile_pairs.py --report --profile DIR   # the report=True batch under rocprofv3 (the report kernels)
+    python tools/bench_tile_pairs.py --validate            # validate=False vs validate=True at P = 64, T = 32 and T = 285
+    python tools/bench_tile_pairs.py --validate --profile DIR # the validate=True batch under rocprofv3 (the score kernels)
 
 Configurations: P = 1, 8, 64 pairs at T = 32 targets, and P = 64 at T = 285 (EMIT 285 x 100 x 100 uint16, S2 10 x 600 x 600
 uint16, factor 6).  One JSON line per configuration:
@@ -17,6 +19,13 @@ their kernel time, and the per-kernel share of a batch.
 With --report: plain_ms_per_pair / report_ms_per_pair, the batch without and with ``report=True`` timed alternately in one
 process, and added_ms_per_pair, their difference; with --profile as well, report_us_per_batch (the two report kernels) and
 q_read_tbps, the bytes of Q the report reads (P x 10 000 rows x na float64) over the report's partial kernel time.
+With --validate: the same pair of timings for ``validate=True`` (validate_ms_per_pair, added_ms_per_pair), and the score call of
+one view alone against a yardstick that is not the code under test, timed alternately over device events in the same process:
+score_us_per_view (hsr_pair_score_f64 on (P, T, 10 000) float32 pred and y, every valid pixel in the fit group),
+score_held_out_us_per_view (the same with a checkerboard of 10 x 10 blocks held out, so both groups in every chunk) and clone_us (torch ``clone()`` of one such tensor,
+which moves the same 2 P T npix 4 bytes), their rates and score_over_clone.  With --profile as well, from the kernel trace:
+score_us_per_batch (both views), score_read_tbps (4 P T npix 4 bytes over the partial kernels' time), and the block mean's and
+the coarse predict's time per batch.
 """
 from __future__ import annotations
 
@@ -104,17 +113,18 @@ def child(P, T, iters, warmup, host_pairs):
     print(json.dumps(rec), flush=True)
 
 
-def child_report(P, T, iters, warmup):
-    """report=False and report=True batches, alternately, over device events (median of each)."""
+def child_report(P, T, iters, warmup, flag="report"):
+    """The plain batch and the batch with report=True (or validate=True), alternately, over device events (median of each)."""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
     import torch
     import s2_emit
     E, S = _pairs(torch, P)
     kw = dict(bands=32 if T == 32 else "all", s2_nodata=0.0)
+    on = {flag: True}
     for _ in range(warmup):
         s2_emit.fuse_tile_pairs(E, S, **kw)
-        s2_emit.fuse_tile_pairs(E, S, report=True, **kw)
+        s2_emit.fuse_tile_pairs(E, S, **on, **kw)
     torch.cuda.synchronize()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
     plain, report = [], []
@@ -122,15 +132,75 @@ def child_report(P, T, iters, warmup):
         ev[0].record()
         a = s2_emit.fuse_tile_pairs(E, S, **kw)
         ev[1].record()
-        b = s2_emit.fuse_tile_pairs(E, S, report=True, **kw)
+        b = s2_emit.fuse_tile_pairs(E, S, **on, **kw)
         ev[2].record()
         torch.cuda.synchronize()
         plain.append(ev[0].elapsed_time(ev[1]))
         report.append(ev[1].elapsed_time(ev[2]))
         del a, b
     pm, rm = sorted(plain)[len(plain) // 2], sorted(report)[len(report) // 2]
-    print(json.dumps(dict(P=P, T=T, iters=iters, plain_ms_per_pair=round(pm / P, 4), report_ms_per_pair=round(rm / P, 4),
-                          added_ms_per_pair=round((rm - pm) / P, 4))), flush=True)
+    rec = dict(P=P, T=T, iters=iters, plain_ms_per_pair=round(pm / P, 4))
+    rec[f"{flag}_ms_per_pair"] = round(rm / P, 4)
+    rec["added_ms_per_pair"] = round((rm - pm) / P, 4)
+    if flag == "validate":
+        rec.update(_score_vs_clone(torch, s2_emit, E, S, kw, max(iters, 20)))
+    print(json.dumps(rec), flush=True)
+
+
+def _score_vs_clone(torch, s2_emit, E, S, kw, iters):
+    """hsr_pair_score_f64 on one view of a validate=True batch against torch's clone() of one (P, T, npix) float32 tensor:
+    the same bytes moved (pred and y read once / one tensor read and written), alternately, median over device events."""
+    from s2_emit import _native as nat
+    from s2_emit._engine import _ptr, _stream
+    lib = nat.load()
+    out = s2_emit.fuse_tile_pairs(E, S, validate=True, **kw)
+    val = out.validation
+    pred, y = val.pred_coarse, val.cube_coarse                       # two (P, T, h, w) float32 arrays of the real thing
+    P, T, h, w = pred.shape
+    npix = h * w
+    group = out.mask.to(torch.uint8).contiguous()
+    sw = lib.hsr_pair_score_work_bytes(npix, T) // 8
+    work = torch.empty((P, sw), dtype=torch.float64, device=pred.device)
+    o = val
+    n, rmse, r2, mean_ref = [torch.empty_like(t[:, 0].contiguous()) for t in (o.n, o.rmse, o.r2, o.mean_ref)]
+    sam, n_sam, ergas = [torch.empty_like(t[:, 0].contiguous()) for t in (o.sam, o.n_sam, o.ergas)]
+    sam_map = torch.empty((P, npix), dtype=torch.float32, device=pred.device)
+    st = _stream(torch)
+
+    def score():                                                      # reads `group` as bound at the call
+        nat.check(lib.hsr_pair_score_f64(_ptr(pred), T * npix, _ptr(y), T * npix, _ptr(group), npix, npix, T, 100.0 / 6, _ptr(work),
+                                         sw, _ptr(n), _ptr(rmse), _ptr(r2), _ptr(mean_ref), 2 * T, _ptr(sam), _ptr(n_sam),
+                                         _ptr(ergas), 2, _ptr(sam_map), npix, P, st), "hsr_pair_score_f64")
+    fit_only = group
+    ii, jj = torch.meshgrid(torch.arange(h, device=pred.device), torch.arange(w, device=pred.device), indexing="ij")
+    board = (((ii // 10 + jj // 10) % 2) + 1).to(torch.uint8).expand(P, h, w)
+    held_out = (out.mask.to(torch.uint8) * board).contiguous()       # a checkerboard of 10 x 10 blocks held out (code 2)
+    for _ in range(3):
+        score()
+        c = pred.clone()
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    ts, th, tc = [], [], []
+    for _ in range(iters):
+        group = fit_only
+        ev[0].record()
+        score()
+        ev[1].record()
+        c = pred.clone()
+        ev[2].record()
+        group = held_out
+        score()
+        ev[3].record()
+        torch.cuda.synchronize()
+        ts.append(ev[0].elapsed_time(ev[1]))
+        tc.append(ev[1].elapsed_time(ev[2]))
+        th.append(ev[2].elapsed_time(ev[3]))
+        del c
+    sm, cm, hm = (sorted(t)[len(t) // 2] for t in (ts, tc, th))
+    nbytes = 2.0 * P * T * npix * 4
+    return dict(score_us_per_view=round(sm * 1e3, 1), score_held_out_us_per_view=round(hm * 1e3, 1), clone_us=round(cm * 1e3, 1),
+                score_tbps=round(nbytes / sm / 1e9, 2), clone_tbps=round(nbytes / cm / 1e9, 2),
+                score_over_clone=round(sm / cm, 2), score_held_out_over_clone=round(hm / cm, 2))
 
 
 def _kernel_stats(out_dir):
@@ -141,13 +211,14 @@ def _kernel_stats(out_dir):
     return rows
 
 
-def profile_one(P, T, iters, out_dir, report=False):
+def profile_one(P, T, iters, out_dir, report=False, validate=False):
     """One configuration under rocprofv3, twice (1 and 1 + iters batches after the input generation): the difference of the two
     traces is `iters` batches alone - launches per batch, kernel time per batch, and the Gram / predict FLOP rates over it."""
     def run(n):
-        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}" + ("_report" if report else ""))
+        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}" + ("_report" if report else "") + ("_validate" if validate else ""))
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
-               os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"] + (["--report"] if report else [])
+               os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"] + \
+              (["--report"] if report else []) + (["--validate"] if validate else [])
         subprocess.run(cmd, check=True, cwd=ROOT)
         per = {}
         for r in _kernel_stats(d):
@@ -175,6 +246,7 @@ def profile_one(P, T, iters, out_dir, report=False):
                gram_tflops_f64=round(2.0 * npix * na * ldq * P / gram_ns / 1e3, 2) if gram_ns else None,
                predict_tflops_f32=round(2.0 * npix10 * nf * T * P / pred_ns / 1e3, 2) if pred_ns else None,
                **(report_fields(ns, P, npix, na, iters) if report else {}),
+               **(validate_fields(ns, P, npix, T) if validate else {}),
                kernel_us_per_batch={k.split("(")[0][-60:]: round(v[1] / iters / 1e3, 1) for k, v in sorted(diff.items(), key=lambda kv: -kv[1][1])})
     print(json.dumps(rec), flush=True)
 
@@ -184,6 +256,15 @@ def report_fields(ns, P, npix, na, iters):
     all_ns = ns(lambda n: "pair_report" in n)
     return dict(report_us_per_batch=round(all_ns / 1e3, 1), report_us_per_pair=round(all_ns / 1e3 / P, 2),
                 q_read_tbps=round(P * npix * na * 8 / part_ns / 1e3, 2) if part_ns else None)
+
+
+def validate_fields(ns, P, npix, T):
+    part_ns = ns(lambda n: "pair_score_partial" in n)
+    all_ns = ns(lambda n: "pair_score" in n)
+    return dict(score_us_per_batch=round(all_ns / 1e3, 1), score_us_per_pair=round(all_ns / 1e3 / P, 2),
+                score_read_tbps=round(4.0 * P * T * npix * 4 / part_ns / 1e3, 2) if part_ns else None,
+                block_mean_us_per_batch=round(ns(lambda n: "block_mean" in n) / 1e3, 1),
+                holdout_us_per_batch=round(ns(lambda n: "pair_holdout" in n) / 1e3, 1))
 
 
 def main():
@@ -196,6 +277,8 @@ def main():
     ap.add_argument("--profile", default=None, help="directory for rocprofv3 output: profile every configuration")
     ap.add_argument("--configs", default=None, help="P,T;P,T... (default: all; with --report 64,32;64,285)")
     ap.add_argument("--report", action="store_true", help="time report=False against report=True")
+    ap.add_argument("--validate", action="store_true", help="time validate=False against validate=True, and the score call "
+                    "against a clone of the same bytes")
     a = ap.parse_args()
     if a.child:
         P, T = map(int, a.child.split(","))
@@ -206,21 +289,23 @@ def main():
             import s2_emit
             E, S = _pairs(torch, P)
             for _ in range(a.iters):
-                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0, report=a.report)
+                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0, report=a.report, validate=a.validate)
             torch.cuda.synchronize()
             return
-        if a.report:
+        if a.validate:
+            child_report(P, T, a.iters, a.warmup, "validate")
+        elif a.report:
             child_report(P, T, a.iters, a.warmup)
         else:
             child(P, T, a.iters, a.warmup, a.host_pairs)
         return
-    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else (REPORT_CONFIGS if a.report else CONFIGS)
+    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else (REPORT_CONFIGS if a.report or a.validate else CONFIGS)
     for P, T in configs:
         if a.profile:
-            profile_one(P, T, a.iters, a.profile, a.report)
-        elif a.report:
+            profile_one(P, T, a.iters, a.profile, a.report, a.validate)
+        elif a.report or a.validate:
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(max(a.iters, 9)),
-                            "--warmup", str(a.warmup), "--report"], check=True)
+                            "--warmup", str(a.warmup), "--validate" if a.validate else "--report"], check=True)
         else:
             iters = a.iters if P * T < 64 * 285 else max(2, a.iters // 2)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(iters),
