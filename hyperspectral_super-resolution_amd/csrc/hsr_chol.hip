@@ -186,7 +186,7 @@ __global__ __launch_bounds__(1024) void chol_factor_kernel(double* __restrict__ 
     CHOL_STAMP(5);
     // trailing update, lower triangle in 16 x 16 tiles on the float64 matrix cores: C[I][J] -= P_I P_J^T.
     // Lane (col = lane & 15, kk = lane >> 4): A operand P[16 I + col][4 s + kk], B operand P[16 J + col][4 s + kk],
-    // accumulator register g = element (row kk + 4 g, column col) of the tile (layout as in csrc/hsr_ridge.hip).
+    // accumulator register g = element (row kk + 4 g, column col) of the tile (layout as in csrc/hsr_gram.hip).
     {
       const int mt = m >> 4;                       // m is a multiple of 32
       const int ntile = mt * (mt + 1) / 2;

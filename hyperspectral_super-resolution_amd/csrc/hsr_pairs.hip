@@ -1,5 +1,5 @@
 // Tile pairs (s2_emit.fuse_tile_pairs): the front of the notebook's per-pair flow (legacy_notebooks/Spectral_matching.ipynb)
-// for a batch of pairs, before the batched ridge fit of hsr_ridge.hip / hsr_chol.hip:
+// for a batch of pairs, before the batched ridge fit of hsr_ridge.hip / hsr_gram.hip / hsr_chol.hip:
 //   pair prep  one pass over a pair: S2 (nb, H f, W f) -> its f x f block mean on the EMIT grid (float64 sum of the f^2 samples,
 //              float32 store: the bits of hsr_block_mean; a block holding a non-finite or nodata sample is NaN), the T selected
 //              EMIT bands gathered and decoded (uint16: 65535 -> NaN, else u * 1e-4f), and flatten_pixels' training mask

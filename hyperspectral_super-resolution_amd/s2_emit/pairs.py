@@ -7,7 +7,7 @@ evenly spaced EMIT bands (``subsample_bands_evenly``, :327), brings S2 to the EM
 ``logit(clip(y, 1e-4, 1 - 1e-4))`` (:434, :475-490) and predicts the (32, h f, w f) cube with ``predict_cube_logit`` (:561).
 
 Here the whole flow of P pairs of one shape is a fixed number of launches on the current stream, whatever P is
-(csrc/hsr_pairs.hip, csrc/hsr_ridge.hip, csrc/hsr_chol.hip): pair prep (block mean, band gather and decode, training mask),
+(csrc/hsr_pairs.hip, csrc/hsr_ridge.hip, csrc/hsr_gram.hip, csrc/hsr_chol.hip): pair prep (block mean, band gather and decode, mask),
 masked scaler statistics, masked expand, Gram, assembly, P Cholesky factorisations side by side, model read-out and the
 10 m prediction; with ``report=True`` two more launches score each fit on its own training pixels (the notebook's cell 26:
 per-band R^2 and RMSE of sigmoid(model(X_train)) against the raw targets).  ``train_mask`` keeps pixels out of the fit (one more
@@ -23,6 +23,7 @@ S2 on the EMIT grid already (e.g. from GDAL) passes it as ``s2_coarse`` and repr
 from __future__ import annotations
 
 import operator
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Any, Optional
 
@@ -30,17 +31,13 @@ import numpy as np
 
 from . import _native as nat
 from ._engine import _ptr, _stream
-from .ridge import PolyRidge, check_fit_features, subsample_bands_evenly
+from .ridge import PolyRidge, _is_torch, _nodata_args, _predict_batched, check_fit_features, ridge_dims, subsample_bands_evenly
 
 _DTYPES = {"uint16": 2, "float32": 0}      # hsr_pair_prep's dtype codes
 _MAX_FACTOR = 64                           # hsr_pair_prep's bound on the S2 / EMIT pixel ratio
 _MAX_PLANES = 65535                        # hsr_block_mean's bound on the planes of one call
 VIEWS = ("coarse", "degraded")
 GROUPS = ("fit", "held_out")
-
-
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
 
 
 def _dtype_name(a) -> str:
@@ -255,6 +252,12 @@ class TilePairOutput:
         return m
 
 
+# What the fit of fuse_tile_pairs (steps 1 - 5) hands to the steps that read it: fit = TilePairOutput._fit; model = the predict
+# kernels' float32 operands W, b, mean, inv (tensors of fit); x (P, nb, npix) float32 S2 on the EMIT grid; y (P, T, npix) float32
+# decoded targets; group (P, npix) uint8: 1 fit, 2 held out, 0 neither; degree.
+_FitState = namedtuple("_FitState", "fit model x y group degree")
+
+
 def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                     emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
                     eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False) -> TilePairOutput:
@@ -282,11 +285,8 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     Tm = _stack_dev(train_mask, torch, dev) if train_mask is not None else None
     st = _stream(torch)
     nat.check(lib.hsr_polyfeat_prepare(nb, int(degree)), "hsr_polyfeat_prepare")
-    nf = lib.hsr_polyfeat_count(nb, int(degree))
-    na = (nf + 1 + 15) // 16 * 16                     # [1 | features] padded
-    ldq = na + (T + 15) // 16 * 16                    # ... | targets] padded
-    npad = (nf + 31) // 32 * 32
-    kpad = (nf + 1) // 2 * 2
+    dims = ridge_dims(nb, degree, T)
+    nf, na, ldq, npad, kpad = dims.nf, dims.na, dims.ldq, dims.npad, dims.kpad
     f64 = dict(dtype=torch.float64, device=dev)
     f32 = dict(dtype=torch.float32, device=dev)
 
@@ -296,9 +296,8 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     mask = torch.empty((P, npix), dtype=torch.uint8, device=dev)
     src, src_dt, pair_s, fac = (Sc, 0, nb * npix, 0) if Sc is not None else (S, _DTYPES[plan.s2_dtype], S.stride(0), f)
     nat.check(lib.hsr_pair_prep(_ptr(E), _DTYPES[plan.emit_dtype], E.stride(0), plan.nbands, _ptr(_bands_dev(plan.bands, torch, dev)),
-                                T, _ptr(src), src_dt, pair_s, nb, h, w, fac, 0.0 if emit_nodata is None else float(emit_nodata),
-                                0 if emit_nodata is None else 1, 0.0 if s2_nodata is None else float(s2_nodata),
-                                0 if s2_nodata is None else 1, _ptr(x), _ptr(y), _ptr(mask), P, st), "hsr_pair_prep")
+                                T, _ptr(src), src_dt, pair_s, nb, h, w, fac, *_nodata_args(emit_nodata), *_nodata_args(s2_nodata),
+                                _ptr(x), _ptr(y), _ptr(mask), P, st), "hsr_pair_prep")
     valid = group = mask                               # without a train_mask: one array, codes 0 / 1
     if Tm is not None:                                 # the fit's mask = the rule's & the caller's; 1 fit, 2 held out
         Tm = Tm.view(torch.uint8) if Tm.dtype == torch.bool else Tm
@@ -355,16 +354,12 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     else:
         Xf = S
     Xf = Xf.reshape(P, nb, npix10)
-    cube = torch.empty((P, T, npix10), **f32)
-    nat.check(lib.hsr_polyfeat_predict_cube_batched(_ptr(Xf), 1, npix10, nb * npix10, _ptr(mean32), _ptr(inv32), nb, npix10, nb,
-                                                    int(degree), _ptr(W32), T, kpad * T, _ptr(b32), T, T, 1, 1,
-                                                    0.0 if s2_nodata is None else float(s2_nodata), 0 if s2_nodata is None else 1,
-                                                    _ptr(cube), npix10, T * npix10, P, st), "hsr_polyfeat_predict_cube_batched")
-    validation = None
-    if validate:
-        validation = _validate(lib, torch, st, plan, x, y, group, cube, mean32, inv32, W32, b32, kpad, int(degree), s2_nodata)
-    held = (group == 2) if Tm is not None else torch.zeros_like(mask, dtype=torch.bool)
     fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
+    state = _FitState(fit, dict(W=W32, b=b32, mean=mean32, inv=inv32), x, y, group, int(degree))
+    cube = _predict_batched(lib, st, state.degree, state.model, _ptr(Xf), 1, npix10, nb * npix10, npix10, P, 1, True, s2_nodata,
+                            torch.empty((P, T, npix10), **f32))
+    validation = _validate(lib, torch, st, plan, state, cube, s2_nodata) if validate else None
+    held = (group == 2) if Tm is not None else torch.zeros_like(mask, dtype=torch.bool)
     mask_b = mask.view(P, h, w).bool()
     valid_b = mask_b if Tm is None else valid.view(P, h, w).bool()
     return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask_b,
@@ -372,9 +367,10 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
                           r2=r2, rmse=rmse, valid=valid_b, held_out=held.view(P, h, w), validation=validation)
 
 
-def _validate(lib, torch, st, plan, x, y, group, cube, mean32, inv32, W32, b32, kpad, degree, s2_nodata) -> TilePairValidation:
+def _validate(lib, torch, st, plan, state, cube, s2_nodata) -> TilePairValidation:
     """The two views on the EMIT grid and their scores: one predict launch, one block mean per slice of planes, two launches per
     view (csrc/hsr_pairs.hip); the launch count depends on ceil(P T / 65535) only."""
+    x, y, group = state.x, state.y, state.group
     P, nb, h, w, f = plan.P, plan.nb, plan.h, plan.w, plan.factor
     T, npix, npix10 = len(plan.bands), h * w, h * w * f * f
     dev = x.device
@@ -382,10 +378,7 @@ def _validate(lib, torch, st, plan, x, y, group, cube, mean32, inv32, W32, b32, 
     i64 = dict(dtype=torch.int64, device=dev)
     views = torch.empty((2, P, T, npix), dtype=torch.float32, device=dev)
     pred, coarse = views[0], views[1]
-    nat.check(lib.hsr_polyfeat_predict_cube_batched(_ptr(x), 1, npix, nb * npix, _ptr(mean32), _ptr(inv32), nb, npix, nb, degree,
-                                                    _ptr(W32), T, kpad * T, _ptr(b32), T, T, 1, 1,
-                                                    0.0 if s2_nodata is None else float(s2_nodata), 0 if s2_nodata is None else 1,
-                                                    _ptr(pred), npix, T * npix, P, st), "hsr_polyfeat_predict_cube_batched")
+    _predict_batched(lib, st, state.degree, state.model, _ptr(x), 1, npix, nb * npix, npix, P, 1, True, s2_nodata, pred)
     for p0, p1 in plan.plane_slices:
         nat.check(lib.hsr_block_mean(_ptr(cube[p0:p1]), 0, npix10, 1, (p1 - p0) * T, h, w, f, 1.0, _ptr(coarse[p0:p1]), npix, 1, st),
                   "hsr_block_mean")

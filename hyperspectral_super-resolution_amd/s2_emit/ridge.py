@@ -7,10 +7,12 @@ Mirrors the notebook-resident pipeline of the reference, legacy_notebooks/Spectr
 (centre features and targets, solve (Phi^T Phi + alpha I) W = Phi^T Y): the Gram contraction runs on the
 float64 matrix cores (``hsr_gram_f64``), the 285 x 285 ridge system by the library's own one-workgroup blocked
 Cholesky (``hsr_chol_solve_f64``), and
-the prediction is one fused expand + float32-MFMA + sigmoid kernel (``hsr_polyfeat_predict``).
+the prediction is one fused expand + float32-MFMA + sigmoid kernel (``hsr_polyfeat_predict_cube_batched``).
+``ridge_dims`` (the padded sizes of a fit) and ``_predict_batched`` (the predict launch) serve ``pairs.py`` and the tools too.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from math import comb
 from typing import Optional
 
@@ -36,6 +38,44 @@ def check_fit_features(n_in: int, degree: int) -> int:
         raise ValueError(f"{n_in} inputs at degree {degree} give nf={nf} polynomial features; the ridge solve takes at most "
                          f"{MAX_FIT_FEATURES}")
     return nf
+
+
+_RidgeDims = namedtuple("_RidgeDims", "nf na tp ldq npad kpad")
+
+
+def ridge_dims(n_in: int, degree: int, T: int, fit: bool = True) -> _RidgeDims:
+    """The padded sizes of a degree-``degree`` fit of ``n_in`` inputs to ``T`` targets, the one statement of the rules the C entry
+    points expect: nf monomials; na = [1 | monomials] and tp = the targets in the Gram's 16-column tiles, ldq = na + tp (row of
+    [1 | Phi | Y] and of its Gram); npad = the ridge system in the Cholesky's 32-row blocks; kpad = nf rounded up to even (rows of
+    the predict kernels' float32 W).  ValueError for a shape without a monomial table and, with ``fit`` (a model loaded from
+    parameters is not bound by it), for a ridge system larger than the solve takes.  Needs no GPU."""
+    n_in, degree, T = int(n_in), int(degree), int(T)
+    if fit:
+        check_fit_features(n_in, degree)
+    nf = nat.load().hsr_polyfeat_count(n_in, degree)
+    if nf <= 0:
+        raise ValueError(f"unsupported polynomial features: n_in={n_in}, degree={degree}")
+    na, tp = (nf + 1 + 15) // 16 * 16, (T + 15) // 16 * 16
+    return _RidgeDims(nf, na, tp, na + tp, (nf + 31) // 32 * 32, (nf + 1) // 2 * 2)
+
+
+def _nodata_args(nodata):
+    """(value, flag): how the C entry points take an optional nodata value."""
+    return (0.0, 0) if nodata is None else (float(nodata), 1)
+
+
+def _predict_batched(lib, st, degree: int, model, x_ptr, x_ps: int, x_cs: int, pair_x: int, npix: int, P: int, activation: int,
+                     nan_bad: bool, nodata, out):
+    """The predict launch of P models of one shape (``model``: W (.., kpad, T), b (.., T), mean and inv (.., n_in) float32, a
+    leading P axis when P > 1) on inputs (pixel p, band c, pair i) at x_ptr[p x_ps + c x_cs + i pair_x], into out (.., T, npix).
+    P = 1 is the launch of the single entry point: the same kernel and grid, the pair strides unused."""
+    W, n_in = model["W"], model["mean"].shape[-1]
+    kpad, T = W.shape[-2:]
+    nat.check(lib.hsr_polyfeat_predict_cube_batched(x_ptr, x_ps, x_cs, pair_x, _ptr(model["mean"]), _ptr(model["inv"]), n_in, npix,
+                                                    n_in, int(degree), _ptr(W), W.stride(-2), kpad * T, _ptr(model["b"]), T, T,
+                                                    activation, 1 if nan_bad else 0, *_nodata_args(nodata), _ptr(out), npix,
+                                                    T * npix, P, st), "hsr_polyfeat_predict_cube_batched")
+    return out
 
 
 def subsample_bands_evenly(num_bands_total: int, num_keep: int = 32) -> np.ndarray:
@@ -163,28 +203,24 @@ class PolyRidge:
     def local_gram(self, Xd, Yd, mean, scale):
         """[1 | Phi(z)]^T [1 | Phi(z) | Y] of this shard on the float64 matrix cores -> (na, na + tp) device tensor."""
         n, n_in = Xd.shape
-        check_fit_features(n_in, self.degree)
+        T = Yd.shape[1]
+        dims = ridge_dims(n_in, self.degree, T)
+        na, ldq = dims.na, dims.ldq
         torch = nat.require_gpu()
         lib = nat.load()
-        T = Yd.shape[1]
-        nf = lib.hsr_polyfeat_count(n_in, self.degree)
-        if nf <= 0:
-            raise ValueError(f"unsupported polynomial features: n_in={n_in}, degree={self.degree}")
         nat.check(lib.hsr_polyfeat_prepare(n_in, self.degree), "hsr_polyfeat_prepare")
-        na = (nf + 1 + 15) // 16 * 16                                          # [1 | features] padded
-        tp = (T + 15) // 16 * 16
         if n == 0:
-            return torch.zeros((na, na + tp), dtype=torch.float64, device=Xd.device)
-        G = torch.empty((na, na + tp), dtype=torch.float64, device=Xd.device)   # hsr_gram_f64 writes every element
-        Q = torch.empty((n, na + tp), dtype=torch.float64, device=Xd.device)    # [P | Y | 0]; expand fills [0, na)
+            return torch.zeros((na, ldq), dtype=torch.float64, device=Xd.device)
+        G = torch.empty((na, ldq), dtype=torch.float64, device=Xd.device)   # hsr_gram_f64 writes every element
+        Q = torch.empty((n, ldq), dtype=torch.float64, device=Xd.device)    # [P | Y | 0]; expand fills [0, na)
         Q[:, na:na + T] = Yd
-        if tp > T:
+        if ldq > na + T:
             Q[:, na + T:].zero_()
         nat.check(lib.hsr_polyfeat_expand_f64(_ptr(Xd), Xd.stride(0), Xd.stride(1) if n_in > 1 else 1, _ptr(mean),
                                               _ptr(scale), n, n_in, self.degree, _ptr(Q), Q.stride(0), na,
                                               _stream(torch, Xd)), "hsr_polyfeat_expand_f64")
-        work = torch.empty(max(1, lib.hsr_gram_work_bytes(na, na + tp, n) // 8), dtype=torch.float64, device=Xd.device)
-        nat.check(lib.hsr_gram_f64(_ptr(Q), Q.stride(0), na, _ptr(Q), Q.stride(0), na + tp, n, _ptr(work), _ptr(G),
+        work = torch.empty(max(1, lib.hsr_gram_work_bytes(na, ldq, n) // 8), dtype=torch.float64, device=Xd.device)
+        nat.check(lib.hsr_gram_f64(_ptr(Q), Q.stride(0), na, _ptr(Q), Q.stride(0), ldq, n, _ptr(work), _ptr(G),
                                    G.stride(0), _stream(torch, Q)), "hsr_gram_f64")
         return G
 
@@ -192,12 +228,11 @@ class PolyRidge:
         """Centre, add alpha I, Cholesky-solve; stores the model (host float64 copies + device float32 operands)."""
         torch = nat.require_gpu()
         lib = nat.load()
-        nf = lib.hsr_polyfeat_count(n_in, self.degree)
-        na = (nf + 1 + 15) // 16 * 16
+        dims = ridge_dims(n_in, self.degree, T)
+        nf, na, npad, kpad = dims.nf, dims.na, dims.npad, dims.kpad
         # (Phi_c^T Phi_c + alpha I) W = Phi_c^T (Y - ybar) by the library's Cholesky (csrc/hsr_chol.hip), the system padded to
         # a multiple of 32 with an identity block and zero right-hand-side rows, which leaves the solution untouched;
         # assembly and model read-out are one launch each (hsr_ridge_assemble / hsr_ridge_finish)
-        npad = (nf + 31) // 32 * 32
         dev = G.device
         Gp = torch.empty((npad, npad), dtype=torch.float64, device=dev)
         Bp = torch.empty((npad, T), dtype=torch.float64, device=dev)
@@ -209,7 +244,6 @@ class PolyRidge:
         nat.check(lib.hsr_chol_solve_f64(_ptr(Gp), Gp.stride(0), npad, _ptr(Bp), Bp.stride(0), T, _ptr(cwork),
                                          _ptr(self._chol_info), st), "hsr_chol_solve_f64")
         Wm = Bp[:nf]                                     # (nf, T)
-        kpad = (nf + 1) // 2 * 2
         b = torch.empty(T, dtype=torch.float64, device=dev)
         f32 = torch.empty(kpad * T + T + 2 * n_in, dtype=torch.float32, device=dev)
         Wf, b32 = f32[:kpad * T].view(kpad, T), f32[kpad * T:kpad * T + T]
@@ -249,18 +283,17 @@ class PolyRidge:
         """A model from given parameters - e.g. a scikit-learn pipeline fitted elsewhere (``scaler.mean_``, ``scaler.scale_``,
         ``ridge.coef_`` (T, n_features), ``ridge.intercept_``) - ready for predict() / predict_cube() on the GPU."""
         torch = nat.require_gpu()
-        lib = nat.load()
         mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
         scale = np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
         coef = np.atleast_2d(np.asarray(coef, dtype=np.float64))
         b = np.ascontiguousarray(intercept, dtype=np.float64).reshape(-1)
         n_in, T = mean.shape[0], coef.shape[0]
-        nf = lib.hsr_polyfeat_count(n_in, int(degree))
-        if nf <= 0 or coef.shape[1] != nf or scale.shape[0] != n_in or b.shape[0] != T:
+        dims = ridge_dims(n_in, degree, T, fit=False)
+        nf, kpad = dims.nf, dims.kpad
+        if coef.shape[1] != nf or scale.shape[0] != n_in or b.shape[0] != T:
             raise ValueError(f"parameters do not describe a degree-{degree} model of {n_in} inputs: coef {coef.shape}, "
                              f"expected ({T}, {nf})")
         m = cls(degree, alpha)
-        kpad = (nf + 1) // 2 * 2
         W = np.zeros((kpad, T), dtype=np.float32)
         W[:nf] = coef.T
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -277,14 +310,9 @@ class PolyRidge:
         if not self._dev:
             raise RuntimeError("PolyRidge is not fitted")
         nat.check(lib.hsr_polyfeat_prepare(self.n_in, self.degree), "hsr_polyfeat_prepare")
-        d = self._dev
         out = torch.empty((self.n_targets, npix), dtype=torch.float32, device=x.device)
-        nat.check(lib.hsr_polyfeat_predict_cube(_ptr(x), x_ps, x_cs, _ptr(d["mean"]), _ptr(d["inv"]), npix, self.n_in,
-                                                self.degree, _ptr(d["W"]), d["W"].stride(0), _ptr(d["b"]), self.n_targets,
-                                                activation, 1 if nan_bad else 0, 0.0 if nodata is None else float(nodata),
-                                                0 if nodata is None else 1, _ptr(out), out.stride(0), _stream(torch, out)),
-                  "hsr_polyfeat_predict_cube")
-        return out
+        return _predict_batched(lib, _stream(torch, out), self.degree, self._dev, _ptr(x), x_ps, x_cs, 0, npix, 1, activation,
+                                nan_bad, nodata, out)
 
     def predict(self, X):
         """X (N, n_in) -> (N, T) float32 raw model output (logit space in the notebook's use)."""

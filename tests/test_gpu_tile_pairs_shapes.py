@@ -48,7 +48,7 @@ def torch_gpu():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# shapes and the instances they reach (mirrors of the host rules in pairs.py, csrc/hsr_chol.hip and csrc/hsr_ridge.hip)
+# shapes and the instances they reach (mirrors of the host rules in pairs.py, csrc/hsr_chol.hip, csrc/hsr_gram.hip and csrc/hsr_ridge.hip)
 # ---------------------------------------------------------------------------------------------------------------------------
 def n_features(nb, degree):
     return sum(comb(nb + d - 1, d) for d in range(1, degree + 1))

@@ -232,8 +232,8 @@ def test_block_mean_is_issued_in_slices_of_whole_pairs(monkeypatch):
     y = torch.zeros((P, T, h * w))
     group = torch.zeros((P, h * w), dtype=torch.uint8)
     cube = torch.zeros((P, T, h * w * f * f))
-    z = torch.zeros(4)
-    v = pairs._validate(Lib(), torch, ctypes.c_void_p(0), plan, x, y, group, cube, z, z, z, z, 2, 1, None)
+    model = dict(W=torch.zeros((P, 2, T)), b=torch.zeros((P, T)), mean=torch.zeros((P, nb)), inv=torch.zeros((P, nb)))
+    v = pairs._validate(Lib(), torch, ctypes.c_void_p(0), plan, pairs._FitState({}, model, x, y, group, 1), cube, None)
     names = [c[0] for c in calls]
     assert names.count("hsr_block_mean") == 2 and names.count("hsr_polyfeat_predict_cube_batched") == 1
     assert names.count("hsr_pair_score_f64") == 2

@@ -232,8 +232,10 @@ def profile_one(P, T, iters, out_dir, report=False, validate=False):
     diff = {k: (b[k][0] - a.get(k, (0, 0.0))[0], b[k][1] - a.get(k, (0, 0.0))[1]) for k in b}
     diff = {k: v for k, v in diff.items() if v[0] > 0}
     calls = sum(v[0] for v in diff.values())
-    nf, na = 285, 288
-    ldq = na + (T + 15) // 16 * 16
+    sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
+    from s2_emit.ridge import ridge_dims
+    dims = ridge_dims(10, 3, T)
+    nf, na, ldq = dims.nf, dims.na, dims.ldq
     npix, npix10 = 100 * 100, 600 * 600
 
     def ns(pred):

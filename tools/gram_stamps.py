@@ -1,5 +1,5 @@
 """Phase timeline of gram_f64_lds_kernel (library built with -DHSR_GRAM_STAMPS: tools/dbg/build_variants.sh
-"gstamp:-DHSR_GRAM_STAMPS:hsr_ridge"; HSR_LIBRARY=tools/dbg/libhsr_gstamp.so).  s_memrealtime (100 MHz) at: entry, end of
+"gstamp:-DHSR_GRAM_STAMPS:hsr_gram"; HSR_LIBRARY=tools/dbg/libhsr_gstamp.so).  s_memrealtime (100 MHz) at: entry, end of
 the prologue, end of the batch loop, end of the group combine, partial sums stored."""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,12 +7,14 @@ sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
 import numpy as np, torch
 from s2_emit import _native as nat
 from s2_emit._engine import _ptr, _stream
+from s2_emit.ridge import ridge_dims
 lib = nat.load()
 raw = C.CDLL(os.environ["HSR_LIBRARY"])
 raw.hsr_dbg_gram_stamps.argtypes = [C.c_void_p]
-n, na = 29127, 288
+n = 29127
 for T in (32, 285):
-    nb = na + (T + 15) // 16 * 16
+    dims = ridge_dims(10, 3, T)
+    na, nb = dims.na, dims.ldq
     Q = torch.rand((n, nb), device="cuda", dtype=torch.float64)
     work = torch.empty(lib.hsr_gram_work_bytes(na, nb, n) // 8, dtype=torch.float64, device="cuda")
     G = torch.empty((na, nb), dtype=torch.float64, device="cuda")

@@ -5,10 +5,12 @@ sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
 import torch
 from s2_emit import _native as nat
 from s2_emit._engine import _ptr, _stream
+from s2_emit.ridge import ridge_dims
 lib = nat.load()
-n, na = 29127, 288
+n = 29127
 for T in (32, 285):
-    nb = na + (T + 15) // 16 * 16
+    dims = ridge_dims(10, 3, T)
+    na, nb = dims.na, dims.ldq
     Q = torch.rand((n, nb), device="cuda", dtype=torch.float64)
     work = torch.empty(lib.hsr_gram_work_bytes(na, nb, n) // 8, dtype=torch.float64, device="cuda")
     G = torch.empty((na, nb), dtype=torch.float64, device="cuda")
