@@ -31,6 +31,25 @@ inline int check_hip(hipError_t e, const char* what) {
     if (rc_ != HSR_OK) return rc_;                               \
   } while (0)
 
+// Kernel instances of hsr_select.hip, hsr_resample.hip and hsr_tile.hip, the index of the name table behind hsr_aux_last_launch /
+// hsr_aux_instance_name (csrc/hsr_lib.hip).  A family's instances are consecutive: base + template-argument offset.
+enum AuxInstance : int {
+  kAuxSelectHist = 0,                      // + (PASS - 1) * 2 + MODE
+  kAuxSelectRows4 = kAuxSelectHist + 6,    // + PASS - 1
+  kAuxSelectScan = kAuxSelectRows4 + 3,    // + PASS - 1
+  kAuxSelectTiny = kAuxSelectScan + 3,
+  kAuxBlockMeanTile = kAuxSelectTiny + 1,  // + in_dtype (0 float, 1 uint8_t, 2 uint16_t)
+  kAuxBlockMean = kAuxBlockMeanTile + 3,   // + in_dtype
+  kAuxBilinearUp = kAuxBlockMean + 3,      // + VEC4 + IN4: <false, false>, <true, false>, <true, true>
+  kAuxBilinearUpHist = kAuxBilinearUp + 3, // + IN4
+  kAuxTileEncode = kAuxBilinearUpHist + 2, // + vec
+  kAuxTileDecode = kAuxTileEncode + 2,     // + vec
+  kAuxTranspose = kAuxTileDecode + 2,      // + 0 <float, float>, 1 <uint16_t, uint16_t>, 2 <uint16_t, float>, 3 <int16_t, float>
+  kAuxInstances = kAuxTranspose + 4
+};
+// HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_aux_last_launch).
+int aux_launched(const char* what, int instance);
+
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
 // records, and clears the error a refused request leaves: the launch itself then reports it.
 inline void raise_lds_limit(const void* kernel, size_t bytes, size_t& configured) {

@@ -82,7 +82,52 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
+// The last successful launch of a kernel of hsr_select.hip / hsr_resample.hip / hsr_tile.hip on this thread (hsr_aux_last_launch):
+// an index of this table (AuxInstance, hsr_common.h), turned into its name only when read.  -1 = none since the last read.
+static const char* const kAuxNames[kAuxInstances] = {
+    "select_hist_kernel<1, 0>", "select_hist_kernel<1, 1>", "select_hist_kernel<2, 0>", "select_hist_kernel<2, 1>",
+    "select_hist_kernel<3, 0>", "select_hist_kernel<3, 1>",
+    "select_hist_rows4_kernel<1>", "select_hist_rows4_kernel<2>", "select_hist_rows4_kernel<3>",
+    "select_scan_kernel<1>", "select_scan_kernel<2>", "select_scan_kernel<3>",
+    "select_tiny_kernel",
+    "block_mean_tile_kernel<float>", "block_mean_tile_kernel<uint8_t>", "block_mean_tile_kernel<uint16_t>",
+    "block_mean_kernel<float>", "block_mean_kernel<uint8_t>", "block_mean_kernel<uint16_t>",
+    "bilinear_up_kernel<false, false>", "bilinear_up_kernel<true, false>", "bilinear_up_kernel<true, true>",
+    "bilinear_up_hist_kernel<false>", "bilinear_up_hist_kernel<true>",
+    "tile_encode_kernel scalar", "tile_encode_kernel vec",
+    "tile_decode_kernel scalar", "tile_decode_kernel vec",
+    "transpose_rc_kernel<float, float>", "transpose_rc_kernel<uint16_t, uint16_t>", "transpose_rc_kernel<uint16_t, float>",
+    "transpose_rc_kernel<int16_t, float>",
+};
+static thread_local int g_aux_last = -1;
+
+int aux_launched(const char* what, int instance) {
+  const int rc = check_hip(hipGetLastError(), what);
+  if (rc == HSR_OK) g_aux_last = instance;
+  return rc;
+}
+
 }  // namespace hsr
+
+extern "C" int hsr_aux_last_launch(char* name, int32_t capacity) {
+  const int r = hsr::g_aux_last;
+  hsr::g_aux_last = -1;
+  if (!name || capacity < 1) return r >= 0 ? 1 : 0;
+  name[0] = 0;
+  if (r < 0) return 0;
+  snprintf(name, (size_t)capacity, "%s", hsr::kAuxNames[r]);
+  return 1;
+}
+
+extern "C" int hsr_aux_instance_count(void) { return hsr::kAuxInstances; }
+
+extern "C" const char* hsr_aux_instance_name(int32_t i) {
+  if (i < 0 || i >= hsr::kAuxInstances) {
+    hsr::set_error("hsr_aux_instance_name: i=%d outside [0,%d)", i, (int)hsr::kAuxInstances);
+    return nullptr;
+  }
+  return hsr::kAuxNames[i];
+}
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

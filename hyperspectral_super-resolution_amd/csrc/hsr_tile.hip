@@ -29,10 +29,9 @@ __device__ __forceinline__ uint16_t encode_sample(float x, float scale, bool has
 
 __global__ __launch_bounds__(256) void tile_encode_kernel(const float* __restrict__ x, int64_t n, float scale,
                                                           int has_src_nodata, float src_nodata, int32_t nodata_u16,
-                                                          uint16_t* __restrict__ out) {
+                                                          uint16_t* __restrict__ out, bool vec) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = n >> 2;
-  const bool vec = ((((uintptr_t)x) & 15) == 0) && ((((uintptr_t)out) & 7) == 0);
   if (vec) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
       const float4 v = ld_stream(reinterpret_cast<const float4*>(x) + i);
@@ -56,10 +55,9 @@ __device__ __forceinline__ float decode_sample(uint32_t u, float scale, uint32_t
 }
 
 __global__ __launch_bounds__(256) void tile_decode_kernel(const uint16_t* __restrict__ u, int64_t n, float scale,
-                                                          uint32_t nodata, float* __restrict__ out) {
+                                                          uint32_t nodata, float* __restrict__ out, bool vec) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t n4 = n >> 2;
-  const bool vec = ((((uintptr_t)u) & 7) == 0) && ((((uintptr_t)out) & 15) == 0);
   if (vec) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
       const uint2 v = reinterpret_cast<const uint2*>(u)[i];
@@ -108,13 +106,12 @@ __global__ __launch_bounds__(256) void transpose_rc_kernel(const TI* __restrict_
 }
 
 template <typename TI, typename TO>
-static int launch_transpose(const void* in, void* out, int64_t batch, int64_t R, int64_t C, hipStream_t s) {
+static int launch_transpose(const void* in, void* out, int64_t batch, int64_t R, int64_t C, hipStream_t s, int pair) {
   const int64_t tiles_c = (C + 63) / 64, tiles_r = (R + 63) / 64;
   HSR_REQUIRE(tiles_c * tiles_r < ((int64_t)1 << 31) && batch <= 65535, HSR_ERR_UNSUPPORTED, "hsr_interleave_to_bip: shape too large");
   hipLaunchKernelGGL((transpose_rc_kernel<TI, TO>), dim3((unsigned)(tiles_c * tiles_r), (unsigned)batch), dim3(256), 0, s,
                      (const TI*)in, (TO*)out, R, C, tiles_c);
-  HSR_LAUNCH_CHECK("transpose_rc_kernel");
-  return HSR_OK;
+  return aux_launched("transpose_rc_kernel launch", kAuxTranspose + pair);
 }
 
 static unsigned stream_grid(int64_t n) {
@@ -132,10 +129,11 @@ extern "C" int hsr_tile_encode_u16(const float* x_dev, int64_t n, float scale, i
   HSR_REQUIRE(nodata_u16 >= 1 && nodata_u16 <= 0xffff, HSR_ERR_INVALID, "hsr_tile_encode_u16: nodata_u16=%d outside [1,65535]", nodata_u16);
   if (n == 0) return HSR_OK;
   HSR_REQUIRE(x_dev && out_dev, HSR_ERR_INVALID, "hsr_tile_encode_u16: NULL pointer");
+  // the 16-byte path of the kernel: four samples per load and one 8-byte store, so both ends must be aligned for it
+  const bool vec = ((((uintptr_t)x_dev) & 15) == 0) && ((((uintptr_t)out_dev) & 7) == 0);
   hipLaunchKernelGGL(hsr::tile_encode_kernel, dim3(hsr::stream_grid(n)), dim3(256), 0, (hipStream_t)stream, x_dev, n,
-                     scale, has_src_nodata, src_nodata, nodata_u16, out_dev);
-  HSR_LAUNCH_CHECK("tile_encode_kernel");
-  return HSR_OK;
+                     scale, has_src_nodata, src_nodata, nodata_u16, out_dev, vec);
+  return hsr::aux_launched("tile_encode_kernel launch", hsr::kAuxTileEncode + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_tile_decode_u16(const uint16_t* u_dev, int64_t n, float scale, int32_t nodata, float* out_dev,
@@ -144,10 +142,10 @@ extern "C" int hsr_tile_decode_u16(const uint16_t* u_dev, int64_t n, float scale
   HSR_REQUIRE(nodata <= 0xffff, HSR_ERR_INVALID, "hsr_tile_decode_u16: nodata=%d is not a uint16 value (negative = none)", nodata);
   if (n == 0) return HSR_OK;
   HSR_REQUIRE(u_dev && out_dev, HSR_ERR_INVALID, "hsr_tile_decode_u16: NULL pointer");
+  const bool vec = ((((uintptr_t)u_dev) & 7) == 0) && ((((uintptr_t)out_dev) & 15) == 0);   // as in hsr_tile_encode_u16
   hipLaunchKernelGGL(hsr::tile_decode_kernel, dim3(hsr::stream_grid(n)), dim3(256), 0, (hipStream_t)stream, u_dev, n,
-                     scale, nodata < 0 ? 0x10000u : (uint32_t)nodata, out_dev);
-  HSR_LAUNCH_CHECK("tile_decode_kernel");
-  return HSR_OK;
+                     scale, nodata < 0 ? 0x10000u : (uint32_t)nodata, out_dev, vec);
+  return hsr::aux_launched("tile_decode_kernel launch", hsr::kAuxTileDecode + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_interleave_to_bip(const void* in_dev, int32_t in_dtype, int32_t interleave, int64_t lines, int64_t samples,
@@ -167,10 +165,10 @@ extern "C" int hsr_interleave_to_bip(const void* in_dev, int32_t in_dtype, int32
     const char* ip = (const char*)in_dev + (size_t)b0 * R * C * isz;
     char* op = (char*)out_dev + (size_t)b0 * R * C * osz;
     int rc;
-    if (in_dtype == 0 && out_dtype == 0) rc = hsr::launch_transpose<float, float>(ip, op, nb, R, C, s);
-    else if (in_dtype == 2 && out_dtype == 2) rc = hsr::launch_transpose<uint16_t, uint16_t>(ip, op, nb, R, C, s);
-    else if (in_dtype == 2 && out_dtype == 0) rc = hsr::launch_transpose<uint16_t, float>(ip, op, nb, R, C, s);
-    else if (in_dtype == 3 && out_dtype == 0) rc = hsr::launch_transpose<int16_t, float>(ip, op, nb, R, C, s);
+    if (in_dtype == 0 && out_dtype == 0) rc = hsr::launch_transpose<float, float>(ip, op, nb, R, C, s, 0);
+    else if (in_dtype == 2 && out_dtype == 2) rc = hsr::launch_transpose<uint16_t, uint16_t>(ip, op, nb, R, C, s, 1);
+    else if (in_dtype == 2 && out_dtype == 0) rc = hsr::launch_transpose<uint16_t, float>(ip, op, nb, R, C, s, 2);
+    else if (in_dtype == 3 && out_dtype == 0) rc = hsr::launch_transpose<int16_t, float>(ip, op, nb, R, C, s, 3);
     else {
       hsr::set_error("hsr_interleave_to_bip: unsupported dtype pair (%d -> %d)", in_dtype, out_dtype);
       return HSR_ERR_UNSUPPORTED;

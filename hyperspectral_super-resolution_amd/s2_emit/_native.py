@@ -183,6 +183,9 @@ SIGNATURES = {
     "hsr_srf_last_launch": (C.c_int, [_pi32, _pi32, C.POINTER(_i64)]),
     "hsr_srf_kernel_instance": (C.c_int, [_i32, _i32]),
     "hsr_poly_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_aux_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_aux_instance_count": (C.c_int, []),
+    "hsr_aux_instance_name": (C.c_char_p, [_i32]),
     "hsr_polyfeat_predict_kernel": (C.c_int, [_i32, _i32, _i32, _i32]),
     "hsr_step_plan_create": (C.c_int, [C.POINTER(StepDesc), C.POINTER(_vp)]),
     "hsr_step_plan_destroy": (None, [_vp]),

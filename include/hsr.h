@@ -772,6 +772,21 @@ int hsr_srf_kernel_instance(int32_t deg, int32_t variant);
  * "moments_kernel<4>", "reduce_kernel" - truncated to `capacity` bytes, then clears the record; 0 (and "") if there was no
  * launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same. */
 int hsr_poly_last_launch(char* name, int32_t capacity);
+/* The same for the operators around them: the percentile select (csrc/hsr_select.hip), the resamplers (csrc/hsr_resample.hip),
+ * the uint16 tile codec and the ENVI transposer (csrc/hsr_tile.hip).  Host only, same contract, so HSR_ABI_VERSION stays.
+ * hsr_aux_last_launch returns 1 and writes the name of the calling thread's last successful launch from those three files -
+ * kernel and template arguments as in the source, e.g. "select_hist_kernel<2, 1>", "select_tiny_kernel",
+ * "block_mean_tile_kernel<uint8_t>", "bilinear_up_kernel<true, false>", "transpose_rc_kernel<uint16_t, float>"; the codec
+ * kernels, which take their 16-byte path as an argument computed on the host from the two pointers, as "tile_encode_kernel vec" /
+ * "tile_encode_kernel scalar" (decode alike) - truncated to `capacity` bytes, then clears the record; 0 (and "") if there was
+ * no such launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same.
+ * An entry point that launches several kernels (hsr_percentile_limits above 32768 pixels, a BIL cube of more than 65535
+ * lines) leaves the last one.
+ * hsr_aux_instance_count / hsr_aux_instance_name(i), 0 <= i < count: every name the record can return (NULL and the error
+ * text outside that range). */
+int hsr_aux_last_launch(char* name, int32_t capacity);
+int hsr_aux_instance_count(void);
+const char* hsr_aux_instance_name(int32_t i);
 /* Which predict kernel hsr_polyfeat_predict / _predict_cube / _predict_cube_batched launch for (n_in, degree, T): 0
  * predict103_x16_kernel, 1 .. 3 predict103_slice_kernel<1 .. 3>, 4 .. 6 predict_kernel<1 / 2 / 4>; -1 (and the error text) for a
  * shape no kernel takes.  The MFMA kernels (0 .. 3) need the orbit rows that the first hsr_polyfeat_prepare uploads:

@@ -498,6 +498,68 @@ def test_poly_launch_record_host_side():
     assert lib.hsr_poly_last_launch(None, 0) == 0
 
 
+def test_aux_launch_record_host_side():
+    """hsr_aux_last_launch: empty at the start, no record after calls refused (or with nothing to do) before their launch,
+    capacity handling, cleared on read."""
+    lib = nat.load()
+    lib.hsr_aux_last_launch(None, 0)                             # whatever an earlier test left
+    buf = ctypes.create_string_buffer(64)
+    buf.value = b"junk"
+    assert lib.hsr_aux_last_launch(buf, 64) == 0 and buf.value == b""
+    buf.value = b"junk"
+    assert lib.hsr_aux_last_launch(buf, 0) == 0 and buf.value == b"junk"      # capacity < 1: the buffer is not touched
+    assert lib.hsr_aux_last_launch(buf, -5) == 0 and buf.value == b"junk"
+    assert lib.hsr_aux_last_launch(buf, 1) == 0 and buf.raw[0] == 0            # room for the terminator alone
+    f = ctypes.c_void_p(16)
+    assert lib.hsr_percentile_limits(None, 10, 1, None, 10, 1, 2.0, 98.0, f, f, None) == 1
+    assert lib.hsr_percentile_limits(f, 10, 1, None, 10, 1, 2.0, 101.0, f, f, None) == 1
+    assert lib.hsr_percentile_limits(f, 10, 1, None, 10, 17, 2.0, 98.0, f, f, None) == 2
+    assert lib.hsr_percentile_hist(4, f, 10, 1, None, 10, 1, f, None) == 1
+    assert lib.hsr_percentile_hist(1, f, 5, 1, None, 10, 1, f, None) == 1         # neither band-major nor pixel-major
+    assert lib.hsr_percentile_hist(1, f, 10, 1, None, 0, 1, f, None) == 0         # npix 0: nothing launched
+    assert lib.hsr_percentile_scan(0, 1, 2.0, 98.0, f, f, None) == 1
+    assert lib.hsr_block_mean(None, 0, 1, 1, 1, 1, 1, 1, 1.0, f, 1, 1, None) == 1
+    assert lib.hsr_block_mean(f, 0, 1, 1, 1, 1, 1, 65, 1.0, f, 1, 1, None) == 1
+    assert lib.hsr_bilinear_upsample(f, 1, 1, 1, 0, 1, 1, f, 1, 1, None) == 1
+    assert lib.hsr_bilinear_upsample_mask_hist(f, 1, 4, 5, 1, 1, 1, f, f, f, None) == 2
+    assert lib.hsr_tile_encode_u16(f, -1, 1e4, 0, 0.0, 65535, f, None) == 1
+    assert lib.hsr_tile_encode_u16(None, 0, 1e4, 0, 0.0, 65535, None, None) == 0  # n 0: nothing launched
+    assert lib.hsr_tile_decode_u16(None, 0, 1e-4, 65535, None, None) == 0
+    assert lib.hsr_tile_decode_u16(f, 4, 1e-4, 70000, f, None) == 1
+    assert lib.hsr_interleave_to_bip(f, 0, 3, 1, 1, 1, f, 0, None) == 1
+    assert lib.hsr_interleave_to_bip(f, 0, 1, 0, 1, 1, f, 0, None) == 1
+    assert lib.hsr_aux_last_launch(buf, 64) == 0 and buf.value == b""
+    assert lib.hsr_aux_last_launch(None, 0) == 0
+
+
+def test_aux_instance_enumeration():
+    """hsr_aux_instance_name: every name the record can return - unique, stable, the template spellings of the sources."""
+    lib = nat.load()
+    n = lib.hsr_aux_instance_count()
+    assert n == 32 and lib.hsr_aux_instance_count() == n
+    names = [lib.hsr_aux_instance_name(i) for i in range(n)]
+    assert all(isinstance(s, bytes) and s for s in names) and len(set(names)) == n
+    assert names == [lib.hsr_aux_instance_name(i) for i in range(n)]
+    for bad in (-1, n, 1 << 20):
+        assert lib.hsr_aux_instance_name(bad) is None and b"hsr_aux_instance_name" in lib.hsr_last_error()
+    want = ({f"select_hist_kernel<{p}, {m}>" for p in (1, 2, 3) for m in (0, 1)}
+            | {f"select_hist_rows4_kernel<{p}>" for p in (1, 2, 3)} | {f"select_scan_kernel<{p}>" for p in (1, 2, 3)}
+            | {"select_tiny_kernel"}
+            | {f"{k}<{t}>" for k in ("block_mean_tile_kernel", "block_mean_kernel") for t in ("float", "uint8_t", "uint16_t")}
+            | {"bilinear_up_kernel<false, false>", "bilinear_up_kernel<true, false>", "bilinear_up_kernel<true, true>",
+               "bilinear_up_hist_kernel<true>", "bilinear_up_hist_kernel<false>"}
+            | {f"tile_{c}_kernel {v}" for c in ("encode", "decode") for v in ("vec", "scalar")}
+            | {f"transpose_rc_kernel<{a}, {b}>" for a, b in (("float", "float"), ("uint16_t", "uint16_t"), ("uint16_t", "float"),
+                                                             ("int16_t", "float"))})
+    assert {s.decode() for s in names} == want
+    # every template instance the three sources name in a launch is in the table (kernel names with explicit arguments)
+    csrc = os.path.join(ROOT, "hyperspectral_super-resolution_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in ("hsr_select.hip", "hsr_resample.hip", "hsr_tile.hip"))
+    launched = set(re.findall(r"hipLaunchKernelGGL\(\(?((?:select|block_mean|bilinear|transpose)\w*<[\w, ]+>)", text))
+    assert len(launched) >= 17 and {s for s in launched if not re.search(r"<(PASS|T|TI, TO)>", s)} <= want
+    assert max(len(s) for s in names) < 64
+
+
 # ---------------------------------------------------------------------------------------------
 # SRF weight table
 # ---------------------------------------------------------------------------------------------
