@@ -59,6 +59,12 @@ inline void raise_lds_limit(const void* kernel, size_t bytes, size_t& configured
   configured = bytes;
 }
 
+// Internal entry of hsr_srf.hip for the step executor (hsr_exec.hip); not part of the C ABI.
+// srf_bind_launch_events: the next K1 launch of this thread (hsr_srf_integrate_moments* and their _apply forms) goes out with
+// these timing events bound to its dispatch (hipExtLaunchKernelGGL) instead of two marker packets round it; either may be NULL.
+// The record is consumed by that launch; a caller whose launch call failed early clears it with (NULL, NULL).
+void srf_bind_launch_events(hipEvent_t start, hipEvent_t stop);
+
 constexpr int kWave = 64;
 
 // Number of moments for a degree.

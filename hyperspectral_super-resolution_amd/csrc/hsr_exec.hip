@@ -14,6 +14,7 @@
 #include "hsr_common.h"
 #include "hsr_solve.h"
 #include "hsr_sync_dev.h"
+#include "hsr_fused_dev.h"
 
 // The prepared launches of one tile and nothing else: creating a plan makes no HIP call.
 struct hsr_step_plan {
@@ -23,6 +24,7 @@ struct hsr_step_plan {
 };
 
 enum { kTwoSlot = 0, kFused = 1, kExchange = 2, kGroup = 3 };
+enum { kSyncDrainTickets = 8, kSyncWords = 12 };   // hsr_pipeline.sync
 
 // One slot of a pipeline: the plan it launches and the state of the tile it holds.
 struct pipe_slot {
@@ -50,8 +52,10 @@ struct hsr_pipeline {
   int exchange = 0;               // two slots, 1: the caller runs the fit (reduce -> collective -> solve) itself between
                                   //    hsr_pipeline_submit and hsr_pipeline_fit_done
   unsigned int* sync = nullptr;   // fused forms, device words: [0] ticket counter of the tail fits, [1] bands whose moments are published,
-                                  //   [2] error code, [4 + k] "coefficients ready" word of slot k (holds the sequence number of its tile)
+                                  //   [2] error code, [4 + k] "coefficients ready" word of slot k (holds the sequence number of its tile),
+                                  //   [8] ticket counter of the drain launches (three slots)
   unsigned int tickets = 0;       // value sync[0] reaches once every launch enqueued so far has run
+  unsigned int drain_tickets = 0; // the same for sync[8]
   // ---- four slots: the exchange is issued from here ----
   hsr_exchange x{};
   unsigned int published = 0;     // value sync[1] reaches once every reduction enqueued so far has run (nb per tile)
@@ -110,6 +114,85 @@ __global__ __launch_bounds__(64) void solve_publish_kernel(const double* __restr
   }
 }
 
+// ---- drain of the three-slot fused pipeline ----------------------------------------------------------------------------
+// When no further K1 launch comes, the two ends of a carrying launch still go out as ONE kernel: K3 of the older pending tile as the
+// body (apply_prephase: the bits of apply_rows_kernel), the fit of the newest tile as the tail (lazy_fit: the bits of
+// hsr_moments_reduce_solve), by tickets of a counter of its own.  Both read what EARLIER launches wrote, so nothing crosses between
+// running workgroups and nothing is waited for; the newest tile's own K3 stays behind the launch boundary.  Needs gridDim.x >= nb
+// like every launch with a tail fit.  No exchange, no group fit: those members are fixed, the branches behind them compiled out.
+// (In this file, not next to the K1 kernels: a further caller of solve_band_t in their translation unit changed their register
+// allocation - the degree-3 instances went from 48 to 96 bytes of private segment.)
+struct DrainArgs {
+  int32_t nb;
+  int64_t out_ps;
+  const float* apply_x;
+  float* apply_out;
+  const double* apply_coeffs;
+  const uint8_t* apply_mask;
+  int64_t apply_npix;
+  int32_t apply_clip;
+  const double* lazy_partials;
+  int32_t lazy_slots;
+  long long lazy_min_count;
+  double* lazy_moments;
+  double* lazy_coeffs;
+  unsigned int* lazy_counter;
+  unsigned int lazy_base;
+  unsigned int* lazy_ready;         // always NULL here (a compile-time NULL trips -Wnonnull in the atomic of the dead branch)
+  static constexpr const unsigned int* apply_ready = nullptr;
+  static constexpr unsigned int apply_ready_value = 0;
+  static constexpr unsigned int* sync_error = nullptr;
+  static constexpr int32_t lazy_group_T = 0, lazy_group_index = 0;
+  static constexpr const double* lazy_group_moments = nullptr;
+  static constexpr double* lazy_group_total = nullptr;
+};
+constexpr int kDrainThreads = 512;
+constexpr int kDrainLds = 64 + 64 * 16 * 8 + (16 + hsr::kSolveWork + 16) * 8;   // lazy_fit: ticket, lane sums, moments, solve work area
+template <int DEG>
+__global__ __launch_bounds__(kDrainThreads, 4) void drain_apply_fit_kernel(const DrainArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kDrainLds];
+  const int t = threadIdx.x;
+  hsr::apply_prephase<DEG + 1, kDrainThreads>(a, smem, t);
+  hsr::lazy_fit<DEG, kDrainThreads>(a, smem, t);
+}
+
+int run_drain(const hsr_apply_job& job, const hsr_step_desc& d, int grid, hipStream_t stream) {
+  const char* who = "hsr_pipeline_flush (drain)";
+  HSR_REQUIRE(job.x_dev && job.out_dev && job.coeffs_dev && job.npix >= 1 && job.fit_partials_dev && job.fit_moments_dev &&
+                  job.fit_coeffs_dev && job.fit_counter_dev && job.fit_slots >= 1 && job.fit_min_count >= 0,
+              HSR_ERR_INVALID, "%s: NULL pointer, npix < 1 or an incomplete tail fit", who);
+  // (hsr_pipeline_create_fused has checked the rows: 16-byte aligned, pixel-major, 4 / 8 / 12 / 16 floats)
+  HSR_REQUIRE(job.npix * (d.out_ps >> 2) < ((int64_t)1 << 31), HSR_ERR_UNSUPPORTED, "%s: %lld pixels of %lld floats exceed 2^31 float4",
+              who, (long long)job.npix, (long long)d.out_ps);
+  // one ticket per workgroup, one band per ticket
+  HSR_REQUIRE(grid >= d.nb && grid <= 512, HSR_ERR_UNSUPPORTED, "%s: %d workgroups cannot fit %d bands", who, grid, d.nb);
+  DrainArgs a{};
+  a.nb = d.nb;
+  a.out_ps = d.out_ps;
+  a.apply_x = job.x_dev;
+  a.apply_out = job.out_dev;
+  a.apply_coeffs = job.coeffs_dev;
+  a.apply_mask = job.mask_dev;
+  a.apply_npix = job.npix;
+  a.apply_clip = job.clip;
+  a.lazy_partials = job.fit_partials_dev;
+  a.lazy_slots = job.fit_slots;
+  a.lazy_min_count = (long long)job.fit_min_count;
+  a.lazy_moments = job.fit_moments_dev;
+  a.lazy_coeffs = job.fit_coeffs_dev;
+  a.lazy_counter = job.fit_counter_dev;
+  a.lazy_base = job.fit_ticket_base;
+  switch (d.deg) {
+    case 1: hipLaunchKernelGGL(drain_apply_fit_kernel<1>, dim3(grid), dim3(kDrainThreads), 0, stream, a); break;
+    case 2: hipLaunchKernelGGL(drain_apply_fit_kernel<2>, dim3(grid), dim3(kDrainThreads), 0, stream, a); break;
+    case 3: hipLaunchKernelGGL(drain_apply_fit_kernel<3>, dim3(grid), dim3(kDrainThreads), 0, stream, a); break;
+    case 4: hipLaunchKernelGGL(drain_apply_fit_kernel<4>, dim3(grid), dim3(kDrainThreads), 0, stream, a); break;
+    default: HSR_REQUIRE(false, HSR_ERR_UNSUPPORTED, "%s: deg=%d", who, d.deg);
+  }
+  HSR_LAUNCH_CHECK("drain_apply_fit_kernel");
+  return HSR_OK;
+}
+
 int run_k1(hsr_step_plan* p, const void* cube, const float* real, const uint8_t* mask, hipStream_t s,
            const hsr_apply_job* job = nullptr) {
   const hsr_step_desc& d = p->d;
@@ -128,6 +211,16 @@ int run_k1(hsr_step_plan* p, const void* cube, const float* real, const uint8_t*
   return hsr_srf_integrate_moments(static_cast<const float*>(cube), d.npix, d.B, d.wn_dev, p->k0, p->klen, d.nb, d.pseudo_dev,
                                    d.out_bs, d.out_ps, real, d.real_bs, d.real_ps, mask, d.min_x, d.min_y, d.deg,
                                    d.partials_dev, &p->slots, &d.opts, s);
+}
+
+// K1 with the caller's timing events (either may be NULL) bound to the dispatch: they bracket exactly this launch and put no marker
+// packet on the stream (two hipEventRecord calls round a launch cost ~12 us of launch gap).
+int run_k1_timed(hsr_step_plan* p, const void* cube, const float* real, const uint8_t* mask, hipStream_t s, const hsr_apply_job* job,
+                 void* begin_event, void* end_event) {
+  hsr::srf_bind_launch_events((hipEvent_t)begin_event, (hipEvent_t)end_event);
+  const int rc = run_k1(p, cube, real, mask, s, job);
+  hsr::srf_bind_launch_events(nullptr, nullptr);      // (a call that failed before its launch leaves the record behind)
+  return rc;
 }
 
 int run_apply(const hsr_step_plan* p, const double* coeffs, const uint8_t* mask, hipStream_t s) {
@@ -229,7 +322,7 @@ static int pipeline_new(hsr_step_plan* const* sl, int nslots, int kind, hsr_stre
   pl->side = (hipStream_t)side_stream;
   bool ok = true;
   if (kind != kTwoSlot)           // not a launch-path call
-    ok = hipMalloc(&pl->sync, 8 * sizeof(unsigned int)) == hipSuccess && hipMemset(pl->sync, 0, 8 * sizeof(unsigned int)) == hipSuccess &&
+    ok = hipMalloc(&pl->sync, kSyncWords * sizeof(unsigned int)) == hipSuccess && hipMemset(pl->sync, 0, kSyncWords * sizeof(unsigned int)) == hipSuccess &&
          hipDeviceSynchronize() == hipSuccess;
   if (kind == kTwoSlot || kind == kExchange)
     for (pipe_slot& s : pl->slot)
@@ -530,8 +623,7 @@ static int submit_fused(hsr_pipeline* pl, const void* cube_dev, const float* rea
   int rc = HSR_OK;
   if (ride) job_fit(pl, last, &job);
   else if (fit_last) rc = fit_standalone(pl, last, main);
-  if (rc == HSR_OK && k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-  if (rc == HSR_OK) rc = run_k1(cur.p, cube_dev, real_dev, mask_dev, main, (carry || ride) ? &job : nullptr);
+  if (rc == HSR_OK) rc = run_k1_timed(cur.p, cube_dev, real_dev, mask_dev, main, (carry || ride) ? &job : nullptr, k1_begin_event, k1_end_event);
   if (rc != HSR_OK) return rc;
   if (ride) {
     // the ticket base advances by the workgroups the launch REALLY had (run_k1 reports them), and that must be the number the
@@ -541,7 +633,6 @@ static int submit_fused(hsr_pipeline* pl, const void* cube_dev, const float* rea
     if (pl->kind == kExchange) pl->published += (unsigned int)cur.p->d.nb;
     slot_of(pl, last).fitted = true;
   }
-  if (k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
   // exchange: the moments of tile n - 1 are (or will be, when this launch's tail runs) published - its collective
   if (rc == HSR_OK && fit_last && pl->kind == kExchange) rc = enqueue_exchange(pl, (int)(last % S));
   if (rc != HSR_OK) return rc;
@@ -564,6 +655,26 @@ static int finish_fused(hsr_pipeline* pl, int64_t i, const uint8_t* mask, hipStr
   HSR_REQUIRE(pl->kind != kGroup || pl->n % pl->group_T == 0, HSR_ERR_INVALID,
               "hsr_pipeline_flush: %lld tiles submitted, not a whole number of groups of %d - the last group has no fit yet", (long long)pl->n, pl->group_T);
   int rc = HSR_OK;
+  if (pl->kind == kFused && i + 1 < pl->n && slot_of(pl, i).fitted && slot_of(pl, i + 1).pending && !slot_of(pl, i + 1).fitted) {
+    // Two tiles left: this one's K3 and the newest one's fit are the two ends of a carrying launch - one kernel instead of K3 here and
+    // reduce + solve in front of the last K3.  Same rule as `ride` in submit_fused: at least nb workgroups, else the launches below.
+    pipe_slot& s = slot_of(pl, i);
+    const hsr_step_desc& d = s.p->d;
+    const int grid = hsr_partial_slots(d.npix, &d.opts);
+    if (grid >= d.nb) {
+      hsr_apply_job job{};
+      job_apply(pl, i, mask, &job);
+      job_fit(pl, i + 1, &job);
+      job.fit_counter_dev = pl->sync + kSyncDrainTickets;
+      job.fit_ticket_base = pl->drain_tickets;
+      rc = run_drain(job, d, grid, main);
+      if (rc != HSR_OK) return rc;
+      pl->drain_tickets += (unsigned int)grid;
+      slot_of(pl, i + 1).fitted = true;
+      s.pending = false;
+      return HSR_OK;
+    }
+  }
   for (int64_t k = i; k < (pl->kind == kGroup ? pl->n : i + 1) && rc == HSR_OK; ++k)
     if (slot_of(pl, k).pending && !slot_of(pl, k).fitted) rc = fit_standalone(pl, k, main);
   pipe_slot& s = slot_of(pl, i);
@@ -598,9 +709,7 @@ static int submit_two_slot(hsr_pipeline* pl, const void* cube_dev, const float* 
   const int cur = (int)(pl->n % 2);
   pipe_slot &s = pl->slot[cur], &prev = pl->slot[cur ^ 1];
   int rc = HSR_OK;
-  if (k1_begin_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_begin_event, main), "hsr_pipeline: record K1 begin");
-  if (rc == HSR_OK) rc = run_k1(s.p, cube_dev, real_dev, mask_dev, main);
-  if (rc == HSR_OK && k1_end_event) rc = hsr::check_hip(hipEventRecord((hipEvent_t)k1_end_event, main), "hsr_pipeline: record K1 end");
+  rc = run_k1_timed(s.p, cube_dev, real_dev, mask_dev, main, nullptr, k1_begin_event, k1_end_event);
   if (rc != HSR_OK) return rc;
   if (prev.pending) {
     rc = finish_two_slot(prev, prev_mask_dev, main);

@@ -977,7 +977,8 @@ class SpectralFusion:
 
     @staticmethod
     def _event_handle(ev, stream):
-        """Raw hipEvent_t of a torch event (torch creates it lazily, on the first record)."""
+        """Raw hipEvent_t of a torch event (torch creates it lazily, on the first record: ``stream`` is the pipeline's side stream, so
+        that this record puts no marker on the caller's stream - the native pipeline binds the event to the K1 dispatch itself)."""
         if not ev.cuda_event:
             ev.record(stream)
         import ctypes as C
@@ -1010,8 +1011,7 @@ class SpectralFusion:
         with eng._launch(cube) as stream:
             e0 = e1 = None
             if k1_events is not None:
-                ts = torch.cuda.current_stream(self.device)
-                e0, e1 = self._event_handle(k1_events[0], ts), self._event_handle(k1_events[1], ts)
+                e0, e1 = self._event_handle(k1_events[0], st["side"]), self._event_handle(k1_events[1], st["side"])
             nat.check(lib.hsr_pipeline_submit(st["h"], cube.data_ptr(), real.data_ptr(), None if mask is None else mask.data_ptr(),
                                               None if prev_mask is None else prev_mask.data_ptr(), stream, C.byref(fin), e0, e1),
                       "hsr_pipeline_submit")

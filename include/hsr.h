@@ -651,14 +651,18 @@ int hsr_pipeline_create(hsr_step_plan* slot0, hsr_step_plan* slot1, hsr_stream_t
                         hsr_pipeline** pipeline_out);
 /* Fused form over THREE plans: K3 of tile i-2 rides in the launch of K1 of tile i (hsr_srf_integrate_moments[_u16]_apply) - one kernel
  * per tile on the caller's stream.  submit(i) finishes tile i-2 (prev_mask_dev = ITS mask); hsr_pipeline_flush finishes the
- * OLDEST unfinished tile per call (call it until *finished_slot == -1).  HSR_ERR_UNSUPPORTED unless all plans describe the same
+ * OLDEST unfinished tile per call (call it until *finished_slot == -1); with two tiles left the first call enqueues ONE kernel - K3
+ * of the older tile with the fit of the newest one in its tail - and the second call the newest tile's K3 (tiles of fewer
+ * 64-pixel groups than bands: K3, reduce + solve, K3 as launches of their own).  HSR_ERR_UNSUPPORTED unless all plans describe the same
  * geometry and cube type (float32 or uint16) with 16-byte aligned pixel-major rows of 4 / 8 / 12 / 16 floats. */
 int hsr_pipeline_create_fused(hsr_step_plan* slot0, hsr_step_plan* slot1, hsr_step_plan* slot2, hsr_stream_t side_stream,
                               int32_t exchange, hsr_pipeline** pipeline_out);
 void hsr_pipeline_destroy(hsr_pipeline* pipeline);
 int hsr_pipeline_submit(hsr_pipeline* pipeline, const void* cube_dev, const float* real_dev, const uint8_t* mask_dev,
                         const uint8_t* prev_mask_dev, hsr_stream_t main_stream, int32_t* finished_slot,
-                        void* k1_begin_event, void* k1_end_event);   /* optional hipEvent_t pair recorded around K1 (or NULL) */
+                        void* k1_begin_event, void* k1_end_event);   /* optional hipEvent_t pair (created, timing enabled) or NULL:  */
+                        /* bound to the K1 dispatch itself (hipExtLaunchKernelGGL), so they bracket exactly that launch and put no     */
+                        /* marker packet on main_stream                                                                                */
 int hsr_pipeline_fit_done(hsr_pipeline* pipeline);
 int hsr_pipeline_flush(hsr_pipeline* pipeline, const uint8_t* mask_dev, hsr_stream_t main_stream, int32_t* finished_slot);
 int64_t hsr_pipeline_count(const hsr_pipeline* pipeline);
