@@ -496,13 +496,16 @@ def tile_decode_u16(u16, scale=None, nodata=65535) -> np.ndarray:
 
 
 def match_pair_reference(R, emit_w, srf_dict, good_mask, s2_rgb_hi, factor=6, deg=4, use_ot=True,
-                         n_samples=5000, reg=0.05, numItermax=300, stopThr=1e-6, seed=0, src_scale=1.0 / 255.0):
+                         n_samples=5000, reg=0.05, numItermax=300, stopThr=1e-6, seed=0, src_scale=1.0 / 255.0,
+                         rgb_bands=("B4", "B3", "B2"), positive_band="B2"):
     """poly_regression.py:96-172 on in-memory aligned arrays, statement by statement; the two GDAL warps
-    are the aligned-grid restatements above (unpinned)."""
+    are the aligned-grid restatements above (unpinned).  ``rgb_bands`` (red, green, blue) and ``positive_band``
+    generalise the driver's hard-coded B4 / B3 / B2 and its ``B2 > 0``; the defaults are the driver's."""
     pseudo = pseudo_s2_srf_integral(R, emit_w, srf_dict, good_mask)                                   # :101
-    emit_sim_60m = np.stack([pseudo[b] for b in ("B2", "B3", "B4")], axis=0).astype(np.float32)       # :103-104
+    stack_order = tuple(rgb_bands)[::-1]                                                              # the driver stacks B2, B3, B4
+    emit_sim_60m = np.stack([pseudo[b] for b in stack_order], axis=0).astype(np.float32)              # :103-104
     with np.errstate(invalid="ignore"):
-        valid60 = np.isfinite(emit_sim_60m).all(axis=0) & (emit_sim_60m[0] > 0)                       # :106
+        valid60 = np.isfinite(emit_sim_60m).all(axis=0) & (emit_sim_60m[stack_order.index(positive_band)] > 0)   # :106
     s2_planes = np.ascontiguousarray(np.moveaxis(np.asarray(s2_rgb_hi), -1, 0))
     s2_real_60m = block_mean(s2_planes, factor)                                                        # :110-116
     s2_real_60m *= float(src_scale)
