@@ -50,6 +50,30 @@ enum AuxInstance : int {
 // HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_aux_last_launch).
 int aux_launched(const char* what, int instance);
 
+// Kernel instances of hsr_ridge.hip, hsr_gram.hip and hsr_chol.hip (K4), the index of the name table behind hsr_k4_last_launch /
+// hsr_k4_instance_name (csrc/hsr_lib.hip).  A family's instances are consecutive: base + offset.
+enum K4Instance : int {
+  kK4Expand = 0,
+  kK4PairExpand,
+  kK4StatsPartial,
+  kK4StatsFinish,
+  kK4Assemble,
+  kK4Finish,
+  kK4Predict,                              // + 0 <1>, 1 <2>, 2 <4>
+  kK4PredictX16 = kK4Predict + 3,          // + arm of pred_load10 (0 x2, 1 scalar)
+  kK4PredictSlice = kK4PredictX16 + 2,     // + (TT - 1) * 2 + arm
+  kK4GramLds = kK4PredictSlice + 6,        // + kinds - 1 (bit 0 wide, bit 1 diag, bit 2 narrow)
+  kK4GramReg = kK4GramLds + 7,             // + 0 sym, 1 full
+  kK4GramReduce = kK4GramReg + 2,
+  kK4CholFactorRes,
+  kK4CholFactor,
+  kK4CholSolve,                            // + 0 block inverses in LDS, 1 in global memory
+  kK4Instances = kK4CholSolve + 2
+};
+// HSR_LAUNCH_CHECK of an entry point's one or two launches that also appends their instances, in launch order, to the calling
+// thread's record on success (hsr_k4_last_launch); second < 0: one launch.
+int k4_launched(const char* what, int first, int second = -1);
+
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
 // records, and clears the error a refused request leaves: the launch itself then reports it.
 inline void raise_lds_limit(const void* kernel, size_t bytes, size_t& configured) {

@@ -716,7 +716,7 @@ extern "C" size_t hsr_gram_work_bytes(int32_t na, int32_t nb, int64_t n) {
 // per-pair element strides of A, of the partials and of C.  False when the panels cannot be loaded by DMA or the plan does not fit.
 static bool launch_gram_lds(const double* a_dev, int64_t lda, int32_t na, const double* b_dev, int64_t ldb, int32_t nb, int64_t n,
                             int sym, double* work_dev, double* c_dev, int64_t ldc, int64_t pair_a, int64_t pair_p,
-                            int64_t pair_c, int32_t npairs, hipStream_t s) {
+                            int64_t pair_c, int32_t npairs, hipStream_t s, int* instance) {
   const bool dma_ok = (lda % 2 == 0) && (ldb % 2 == 0) && (((uintptr_t)a_dev | (uintptr_t)b_dev) & 15) == 0 &&
                       (npairs == 1 || pair_a % 2 == 0);
   GramLdsArgs g{};
@@ -743,6 +743,7 @@ static bool launch_gram_lds(const double* a_dev, int64_t lda, int32_t na, const 
                               (int)lds_bytes);
   });
   const int ti = na / 16, tj = nb / 16;
+  *instance = kK4GramLds + ((g.c.nwide ? 1 : 0) | (g.c.ndiag ? 2 : 0) | (g.c.nnarrow ? 4 : 0)) - 1;   // a plan has at least one block
   hipLaunchKernelGGL(gram_f64_lds_kernel, dim3(8 * (unsigned)g.c.per_xcd, (unsigned)npairs), dim3(kGramThreads), lds_bytes, s, g);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj, (unsigned)npairs), dim3(256), 0, s, work_dev, ti * tj, g.c.chunks_wide, tj,
                      sym, kGpCols / 16, g.c.narrow_col / 16, g.c.chunks_narrow, g.c.chunks_diag, c_dev, ldc, pair_p, pair_c);
@@ -760,10 +761,9 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
   // result are symmetric, compute the upper block triangle only
   const int sym = (a_dev == b_dev && lda == ldb && nb >= na) ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
-  if (launch_gram_lds(a_dev, lda, na, b_dev, ldb, nb, n, sym, work_dev, c_dev, ldc, 0, 0, 0, 1, s)) {
-    HSR_LAUNCH_CHECK("gram_f64_lds_kernel");
-    return HSR_OK;
-  }
+  int lds_instance = -1;
+  if (launch_gram_lds(a_dev, lda, na, b_dev, ldb, nb, n, sym, work_dev, c_dev, ldc, 0, 0, 0, 1, s, &lds_instance))
+    return k4_launched("gram_f64_lds_kernel launch", lds_instance, kK4GramReduce);
   int64_t rows = 0;
   const int64_t chunks = gram_reg_chunks(n, &rows);
   constexpr int R = hsr::kGramR;
@@ -771,8 +771,7 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
                      a_dev, lda, ti, b_dev, ldb, tj, n, rows, sym, work_dev);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj), dim3(256), 0, s, work_dev, ti * tj, (int)chunks, tj, sym, R, tj,
                      (int)chunks, 0, c_dev, ldc, (int64_t)0, (int64_t)0);
-  HSR_LAUNCH_CHECK("gram_f64_kernel");
-  return HSR_OK;
+  return k4_launched("gram_f64_kernel launch", kK4GramReg + (sym ? 0 : 1), kK4GramReduce);
 }
 
 extern "C" int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na, int32_t nb, int64_t n, int64_t pair_a,
@@ -786,9 +785,9 @@ extern "C" int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na
                               (size_t)pair_work * sizeof(double) >= hsr_gram_work_bytes(na, nb, n)),
               HSR_ERR_INVALID, "hsr_gram_f64_batched: pair strides overlap");
   // every pair takes the plan of a single launch of its shape: its chunks, and so its bits, do not depend on the batch
+  int lds_instance = -1;
   HSR_REQUIRE(launch_gram_lds(a_dev, lda, na, a_dev, lda, nb, n, 1, work_dev, c_dev, ldc, pair_a, pair_work, pair_c, npairs,
-                              (hipStream_t)stream),
+                              (hipStream_t)stream, &lds_instance),
               HSR_ERR_UNSUPPORTED, "hsr_gram_f64_batched: needs 16-byte aligned rows of an even leading dimension");
-  HSR_LAUNCH_CHECK("gram_f64_lds_kernel (batched)");
-  return HSR_OK;
+  return k4_launched("gram_f64_lds_kernel (batched) launch", lds_instance, kK4GramReduce);
 }

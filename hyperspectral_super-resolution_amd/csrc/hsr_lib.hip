@@ -107,7 +107,69 @@ int aux_launched(const char* what, int instance) {
   return rc;
 }
 
+// The kernels of hsr_ridge.hip / hsr_gram.hip / hsr_chol.hip this thread launched successfully since the last read
+// (hsr_k4_last_launch): indices of this table (K4Instance, hsr_common.h) in launch order, the oldest dropped when the list is full.
+static const char* const kK4Names[kK4Instances] = {
+    "expand_f64_kernel", "pair_expand_f64_kernel", "ridge_stats_partial_kernel", "ridge_stats_finish_kernel",
+    "ridge_assemble_kernel", "ridge_finish_kernel",
+    "predict_kernel<1>", "predict_kernel<2>", "predict_kernel<4>",
+    "predict103_x16_kernel x2", "predict103_x16_kernel scalar",
+    "predict103_slice_kernel<1> x2", "predict103_slice_kernel<1> scalar",
+    "predict103_slice_kernel<2> x2", "predict103_slice_kernel<2> scalar",
+    "predict103_slice_kernel<3> x2", "predict103_slice_kernel<3> scalar",
+    "gram_f64_lds_kernel wide", "gram_f64_lds_kernel diag", "gram_f64_lds_kernel wide+diag", "gram_f64_lds_kernel narrow",
+    "gram_f64_lds_kernel wide+narrow", "gram_f64_lds_kernel diag+narrow", "gram_f64_lds_kernel wide+diag+narrow",
+    "gram_f64_kernel sym", "gram_f64_kernel full",
+    "gram_reduce_kernel",
+    "chol_factor_res_kernel", "chol_factor_kernel",
+    "chol_solve_kernel lds", "chol_solve_kernel global",
+};
+constexpr int kK4RecordCap = 32;
+static thread_local int g_k4_seq[kK4RecordCap];
+static thread_local int g_k4_count = 0;
+
+static void k4_append(int instance) {
+  if (g_k4_count == kK4RecordCap) {
+    for (int i = 1; i < kK4RecordCap; ++i) g_k4_seq[i - 1] = g_k4_seq[i];
+    --g_k4_count;
+  }
+  g_k4_seq[g_k4_count++] = instance;
+}
+
+int k4_launched(const char* what, int first, int second) {
+  const int rc = check_hip(hipGetLastError(), what);
+  if (rc == HSR_OK) {
+    k4_append(first);
+    if (second >= 0) k4_append(second);
+  }
+  return rc;
+}
+
 }  // namespace hsr
+
+extern "C" int hsr_k4_last_launch(char* names, int32_t capacity) {
+  const int count = hsr::g_k4_count;
+  hsr::g_k4_count = 0;
+  if (!names || capacity < 1) return count > 0 ? 1 : 0;
+  names[0] = 0;
+  size_t used = 0;
+  for (int i = 0; i < count && used + 1 < (size_t)capacity; ++i) {
+    const int w = snprintf(names + used, (size_t)capacity - used, "%s%s", i ? "; " : "", hsr::kK4Names[hsr::g_k4_seq[i]]);
+    if (w < 0) break;
+    used += (size_t)w < (size_t)capacity - used ? (size_t)w : (size_t)capacity - used - 1;
+  }
+  return count > 0 ? 1 : 0;
+}
+
+extern "C" int hsr_k4_instance_count(void) { return hsr::kK4Instances; }
+
+extern "C" const char* hsr_k4_instance_name(int32_t i) {
+  if (i < 0 || i >= hsr::kK4Instances) {
+    hsr::set_error("hsr_k4_instance_name: i=%d outside [0,%d)", i, (int)hsr::kK4Instances);
+    return nullptr;
+  }
+  return hsr::kK4Names[i];
+}
 
 extern "C" int hsr_aux_last_launch(char* name, int32_t capacity) {
   const int r = hsr::g_aux_last;

@@ -330,6 +330,11 @@ __device__ __forceinline__ void pred_load10(const PredArgs& a, int64_t pc, float
   }
 }
 
+// pred_load10's predicate on the host, for the launch record (the suffix " x2" / " scalar" of hsr_k4_last_launch): keep the two alike
+static bool pred_x2_arm(const float* x, int64_t x_ps, int64_t x_cs) {
+  return x_cs == 1 && (x_ps & 1) == 0 && (((uintptr_t)x) & 7) == 0;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---- the K axis in ORBIT order (r04) ------------------------------------------------------------------------------------------
 // An MFMA's K index is spread over lane groups (two for v_mfma_f32_32x32x2_f32, four for v_mfma_f32_16x16x4_f32), so the lane
@@ -644,7 +649,7 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
   PredGenericKernel generic = nullptr;
   const void* kern;
   const char* what;
-  int gx, slices = 1, threads;
+  int gx, slices = 1, threads, instance;
   size_t lds;
   const int16_t* rows = nullptr;
   const int tt = a.ttiles;
@@ -658,6 +663,7 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
       wgs_per_cu = kX16Wgs;
       lds = (size_t)4 * kStepsOrb * 16 * 4;
       rows = g_orb_rows_dev;                            // kOrb103.src
+      instance = kK4PredictX16;
     } else {
       // T <= 32: one 16-wave workgroup per CU, W (36.6 KB) staged once per CU (0.209 -> 0.199 ms);
       // T <= 512: slices of 64 or 96 targets, as few and as narrow as T allows
@@ -668,7 +674,9 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
       waves = slice_waves(per);
       lds = (size_t)2 * kStepsOrb2 * per * 32 * 4;
       rows = g_orb_rows_dev + 4 * kStepsOrb;            // kOrb2.src
+      instance = kK4PredictSlice + (per - 1) * 2;
     }
+    instance += pred_x2_arm(a.x, a.x_ps, a.x_cs) ? 0 : 1;   // the arm of pred_load10, pair 0's
     const int pix = 32 * waves;
     const int64_t tiles = (a.npix + pix - 1) / pix;
     gx = 256 * wgs_per_cu / slices;                     // one workgroup per CU in all (73 / 110 KB of LDS each), two for x16
@@ -685,6 +693,7 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
     generic = slot == 4 ? predict_kernel<1> : (slot == 5 ? predict_kernel<2> : predict_kernel<4>);
     what = "predict_kernel launch";
     kern = reinterpret_cast<const void*>(generic);
+    instance = kK4Predict + slot - 4;
   }
   // a batch shares the chip's workgroups among its pairs: fewer per pair, each walking more of its pair's tiles with W staged once
   // (which workgroup computes a tile does not change its bits)
@@ -692,7 +701,7 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
   raise_lds_limit(kern, lds, configured[slot]);
   if (orb) hipLaunchKernelGGL(orb, dim3(gx, slices, npairs), dim3(threads), lds, s, a, rows);
   else hipLaunchKernelGGL(generic, dim3(gx, 1, npairs), dim3(threads), lds, s, a);
-  return check_hip(hipGetLastError(), what);
+  return k4_launched(what, instance);
 }
 
 static int ensure_table(int n_in, int degree) {
@@ -772,8 +781,7 @@ extern "C" int hsr_polyfeat_expand_f64(const float* x_dev, int64_t x_rs, int64_t
               "hsr_polyfeat_expand_f64: ncols=%d ldp=%lld (need ncols >= %d)", ncols, (long long)ldp, g_table_nfeat + 1);
   hipLaunchKernelGGL(expand_f64_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, x_rs,
                      x_cs, mean_dev, scale_dev, n, n_in, g_table_nfeat, g_table_dev, p_dev, ldp, ncols);
-  HSR_LAUNCH_CHECK("expand_f64_kernel");
-  return HSR_OK;
+  return k4_launched("expand_f64_kernel launch", kK4Expand);
 }
 
 extern "C" int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const double* mean_dev, const double* scale_dev,
@@ -791,8 +799,7 @@ extern "C" int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const dou
                    n_in, g_table_nfeat, T, na, eps, g_table_dev};
   hipLaunchKernelGGL(pair_expand_f64_kernel, dim3((unsigned)((npix + 31) / 32), (unsigned)npairs), dim3(256), 0,
                      (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("pair_expand_f64_kernel");
-  return HSR_OK;
+  return k4_launched("pair_expand_f64_kernel launch", kK4PairExpand);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -991,8 +998,7 @@ extern "C" int hsr_ridge_stats(const float* x_dev, int64_t x_rs, int64_t x_cs, i
   static_assert(kStatsBlocks <= 64, "one lane per block");
   hipLaunchKernelGGL(ridge_stats_finish_kernel, dim3(1), dim3(64 * n_in), 0, (hipStream_t)stream, x_dev, x_cs, n, n_in, nblocks,
                      work_dev, stats_dev, mean_dev, scale_dev);
-  HSR_LAUNCH_CHECK("ridge_stats_kernel");
-  return HSR_OK;
+  return k4_launched("ridge_stats_kernel launch", kK4StatsPartial, kK4StatsFinish);
 }
 
 // One launch of ridge_assemble_kernel behind hsr_ridge_assemble (npairs = 1, strides 0, empty_identity = 0) and its batched form:
@@ -1007,7 +1013,7 @@ static int launch_assemble(const char* who, const double* g_dev, int64_t ldg, in
   const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
   hipLaunchKernelGGL(ridge_assemble_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, s, g_dev, ldg, na, nf, T, alpha, a_dev,
                      npad, b_dev, ldb, info_dev, pair_g, pair_a, pair_b, empty_identity);
-  return check_hip(hipGetLastError(), "ridge_assemble_kernel launch");
+  return k4_launched("ridge_assemble_kernel launch", kK4Assemble);
 }
 
 // One launch of ridge_finish_kernel behind hsr_ridge_finish (npairs = 1, an empty FinishPairs: no status word, no NaN intercepts)
@@ -1027,7 +1033,7 @@ static int launch_finish(const char* who, const double* g_dev, int32_t na, int32
   if (cpy > grid) grid = (int)(cpy < 64 ? cpy : 64);
   hipLaunchKernelGGL(ridge_finish_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, s, g_dev, na, nf, T, w_dev, ldw, mean_dev,
                      scale_dev, n_in, kpad, b64_dev, b32_dev, w32_dev, mean32_dev, inv32_dev, pp);
-  return check_hip(hipGetLastError(), "ridge_finish_kernel launch");
+  return k4_launched("ridge_finish_kernel launch", kK4Finish);
 }
 
 extern "C" int hsr_ridge_assemble(const double* g_dev, int64_t ldg, int32_t na, int32_t nf, int32_t T, double alpha,

@@ -126,6 +126,7 @@ class PolyRidge:
         self._dev = {}
         self._fit64 = None     # float64 device tensors of the last fit: (mean, scale, W (nf, T), intercept)
         self._host = None      # their host copies, made on first access of mean_ / scale_ / coef_ / intercept_
+        self._status = None    # the fit's status word: a device tensor until status_ is first read, then an int
 
     # scikit-learn's attribute names, float64 NumPy arrays.  They are copied from the device on first use, so that
     # fit() itself never synchronises with the host (it is ~0.4 ms of enqueued GPU work).
@@ -141,6 +142,15 @@ class PolyRidge:
     scale_ = property(lambda self: self._host_copy()[1])
     coef_ = property(lambda self: self._host_copy()[2])
     intercept_ = property(lambda self: self._host_copy()[3])
+
+    @property
+    def status_(self):
+        """0: fitted; 1: the fit had no row; 2: the ridge system was not positive definite (a non-positive Cholesky pivot, e.g.
+        alpha = 0 on rank-deficient features).  A model whose status is not 0 has NaN intercepts, so every prediction of it is
+        NaN - the statuses of fuse_tile_pairs.  None before a fit; copied from the device on first access, like coef_."""
+        if self._status is not None and not isinstance(self._status, int):
+            self._status = int(self._status.item())
+        return self._status
 
     # ---- fit --------------------------------------------------------------------------------------
     # The fit is a sum over pixels twice over (scaler statistics, then the Gram matrix), so it shards by
@@ -232,7 +242,9 @@ class PolyRidge:
         nf, na, npad, kpad = dims.nf, dims.na, dims.npad, dims.kpad
         # (Phi_c^T Phi_c + alpha I) W = Phi_c^T (Y - ybar) by the library's Cholesky (csrc/hsr_chol.hip), the system padded to
         # a multiple of 32 with an identity block and zero right-hand-side rows, which leaves the solution untouched;
-        # assembly and model read-out are one launch each (hsr_ridge_assemble / hsr_ridge_finish)
+        # assembly and model read-out are one launch each (hsr_ridge_assemble / hsr_ridge_finish_batched with one pair: the
+        # read-out kernel of hsr_ridge_finish, which in this form also turns the Cholesky status into the model's status word
+        # and writes NaN intercepts for a failed fit)
         dev = G.device
         Gp = torch.empty((npad, npad), dtype=torch.float64, device=dev)
         Bp = torch.empty((npad, T), dtype=torch.float64, device=dev)
@@ -248,10 +260,12 @@ class PolyRidge:
         f32 = torch.empty(kpad * T + T + 2 * n_in, dtype=torch.float32, device=dev)
         Wf, b32 = f32[:kpad * T].view(kpad, T), f32[kpad * T:kpad * T + T]
         mean32, inv32 = f32[kpad * T + T:kpad * T + T + n_in], f32[kpad * T + T + n_in:]
-        nat.check(lib.hsr_ridge_finish(_ptr(G), na, nf, T, _ptr(Wm), Bp.stride(0), _ptr(mean), _ptr(scale), n_in, kpad,
-                                       _ptr(b), _ptr(b32), _ptr(Wf), _ptr(mean32), _ptr(inv32), st), "hsr_ridge_finish")
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        nat.check(lib.hsr_ridge_finish_batched(_ptr(G), 0, na, nf, T, _ptr(Wm), Bp.stride(0), 0, _ptr(mean), _ptr(scale), 0, n_in,
+                                               kpad, _ptr(b), _ptr(b32), 0, _ptr(Wf), 0, _ptr(mean32), _ptr(inv32), 0,
+                                               _ptr(self._chol_info), _ptr(status), 1, st), "hsr_ridge_finish_batched")
         self.n_in, self.n_feat, self.n_targets = n_in, nf, T
-        self._fit64, self._host = (mean, scale, Wm, b), None
+        self._fit64, self._host, self._status = (mean, scale, Wm, b), None, status
         self._dev = dict(W=Wf, b=b32, mean=mean32, inv=inv32)
         return self
 
@@ -299,6 +313,7 @@ class PolyRidge:
         dev = torch.device("cuda", torch.cuda.current_device())
         to = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)
         m.n_in, m.n_feat, m.n_targets = n_in, nf, T
+        m._status = 0
         m._fit64 = (to(mean, torch.float64), to(scale, torch.float64), to(coef.T, torch.float64), to(b, torch.float64))
         m._dev = dict(W=to(W, torch.float32), b=to(b, torch.float32), mean=to(mean, torch.float32), inv=to(1.0 / scale, torch.float32))
         return m

@@ -448,7 +448,14 @@ int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const double* b_d
  * a_dev (n, lda) float64 symmetric positive definite - its lower triangle is overwritten by the factor L -,
  * b_dev (n, ldb) holds nrhs right-hand sides in its columns and is overwritten by the solution.  n must be a
  * multiple of 32 in [32, 512]: pad with an identity block and zero right-hand-side rows.  *info_dev = 0, or the
- * 1-based index of the first non-positive pivot (LAPACK potrf convention); asynchronous like everything else. */
+ * 1-based index of the first non-positive pivot (LAPACK potrf convention); asynchronous like everything else.
+ * Which elements of a_dev a call touches (pinned by tests/test_gpu_k4_instances.py): only the lower triangle (i >= j) is
+ * input - no element strictly above the diagonal influences L, the solution or *info_dev, so it may hold anything, NaN
+ * included - and every element of the lower triangle is written (L).  Both factor kernels update the trailing matrix in whole
+ * 16 x 16 tiles, so they load the strictly upper elements of the 16 x 16 diagonal tiles from row 32 on - (i, j) with i < j,
+ * i / 16 == j / 16, i >= 32 - without using them: n <= 288 (chol_factor_res_kernel) writes nothing above the diagonal,
+ * n > 288 (chol_factor_kernel) rewrites exactly those elements and leaves unspecified values there.  Every other element above the diagonal, and the columns
+ * n .. lda - 1 of every row, are neither read nor written.  The same per system for the batched form. */
 size_t hsr_chol_work_bytes(int32_t n);   /* workspace: the inverses of the 32 x 32 diagonal blocks of L */
 int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double* b_dev, int64_t ldb, int32_t nrhs,
                        double* work_dev, int32_t* info_dev, hsr_stream_t stream);
@@ -797,6 +804,30 @@ const char* hsr_aux_instance_name(int32_t i);
  * orbit_rows < 0 answers for the library as it stands, 0 / 1 as if the rows were absent / on the device.  Host only; it
  * adds no record and changes no entry point, so HSR_ABI_VERSION stays. */
 int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t orbit_rows);
+/* Which kernel instances of the polynomial-ridge family (K4: csrc/hsr_ridge.hip, csrc/hsr_gram.hip, csrc/hsr_chol.hip) ran.  Host
+ * only, per thread, same contract as the three records above: no entry point gains an argument, so HSR_ABI_VERSION stays.
+ * One difference: a K4 entry point launches up to two kernels whose selection differs (Gram: main + reduce; Cholesky: factor +
+ * solve; statistics: partial + finish), so the record keeps EVERY kernel the calling thread launched successfully since the last
+ * read (the 32 most recent), in launch order.  hsr_k4_last_launch returns 1 and writes their names joined by "; " - e.g.
+ * "gram_f64_lds_kernel wide+diag+narrow; gram_reduce_kernel" - NUL-terminated and truncated to `capacity` bytes, then clears
+ * the record; 0 (and "") if there was no launch since the last read.  name NULL or capacity < 1: only the return value, the
+ * record is cleared all the same.  A call refused by its argument checks adds nothing.
+ * Names are the kernel and its template arguments as in the source; a path that the host computes and that is uniform over
+ * the launch is a suffix:
+ *   expand_f64_kernel, pair_expand_f64_kernel, ridge_stats_partial_kernel, ridge_stats_finish_kernel, ridge_assemble_kernel,
+ *   ridge_finish_kernel, predict_kernel<1 / 2 / 4>;
+ *   predict103_x16_kernel and predict103_slice_kernel<1 / 2 / 3> with " x2" (the inputs of a pixel read as five float2: x_cs == 1,
+ *   even x_ps, 8-byte aligned base) or " scalar" - the kernel's own predicate, evaluated on the host for pair 0 of a batch (a
+ *   later pair of an odd pair_x may take the other arm);
+ *   gram_f64_lds_kernel with the block kinds of its plan joined by "+" in the order wide, diag, narrow; gram_f64_kernel sym /
+ *   gram_f64_kernel full (with / without the symmetric skip); gram_reduce_kernel;
+ *   chol_factor_res_kernel (n <= 288), chol_factor_kernel, chol_solve_kernel lds / chol_solve_kernel global (block inverses
+ *   staged in LDS or read from the workspace).
+ * hsr_k4_instance_count / hsr_k4_instance_name(i), 0 <= i < count: every name the record can hold (NULL and the error text
+ * outside that range). */
+int hsr_k4_last_launch(char* names, int32_t capacity);
+int hsr_k4_instance_count(void);
+const char* hsr_k4_instance_name(int32_t i);
 
 #ifdef __cplusplus
 }

@@ -532,6 +532,61 @@ def test_aux_launch_record_host_side():
     assert lib.hsr_aux_last_launch(None, 0) == 0
 
 
+def test_k4_launch_record_host_side():
+    """hsr_k4_last_launch: empty without a launch, nothing added by calls refused by their argument checks (NULL pointer,
+    n % 32 != 0, ldw < T, ...), capacity handling, cleared on read; hsr_k4_instance_name: unique, stable, the spellings of the
+    sources with every host-computed path as a suffix."""
+    lib = nat.load()
+    lib.hsr_k4_last_launch(None, 0)                              # whatever an earlier test left
+    buf = ctypes.create_string_buffer(64)
+    buf.value = b"junk"
+    assert lib.hsr_k4_last_launch(buf, 64) == 0 and buf.value == b""
+    buf.value = b"junk"
+    assert lib.hsr_k4_last_launch(buf, 0) == 0 and buf.value == b"junk"       # capacity < 1: the buffer is not touched
+    assert lib.hsr_k4_last_launch(buf, -5) == 0 and buf.value == b"junk"
+    assert lib.hsr_k4_last_launch(buf, 1) == 0 and buf.raw[0] == 0             # room for the terminator alone
+    f = ctypes.c_void_p(16)
+    assert lib.hsr_ridge_stats(None, 1, 1, 10, 1, f, f, f, f, None) == 1 and b"NULL" in lib.hsr_last_error()
+    assert lib.hsr_ridge_stats(f, 1, 1, 0, 1, f, f, f, f, None) == 1
+    assert lib.hsr_ridge_stats(f, 1, 1, 10, 17, f, f, f, f, None) == 1
+    assert lib.hsr_polyfeat_expand_f64(None, 1, 1, f, f, 10, 1, 1, f, 2, 2, None) == 1
+    assert lib.hsr_pair_expand_f64(f, 0, f, f, 0, f, 0, None, 0, 10, 1, 1, 1, 1e-4, f, 32, 0, 16, 1, None) == 1
+    assert lib.hsr_gram_f64(f, 16, 16, None, 16, 16, 10, f, f, 16, None) == 1
+    assert lib.hsr_gram_f64(f, 16, 24, f, 16, 16, 10, f, f, 16, None) == 1           # na % 16 != 0
+    assert lib.hsr_gram_f64_batched(f, 16, 32, 16, 10, 0, f, 0, f, 16, 0, 1, None) == 1   # nb < na
+    assert lib.hsr_chol_solve_f64(f, 48, 48, f, 1, 1, f, f, None) == 2 and b"multiple of 32" in lib.hsr_last_error()
+    assert lib.hsr_chol_solve_f64(f, 32, 32, f, 1, 1, f, None, None) == 1
+    assert lib.hsr_chol_solve_f64(f, 31, 32, f, 1, 1, f, f, None) == 1                # lda < n
+    assert lib.hsr_chol_solve_f64_batched(f, 544, 544, 0, f, 1, 1, 0, f, f, 1, None) == 2
+    assert lib.hsr_ridge_assemble(f, 20, 16, 4, 8, 1.0, f, 32, f, 7, f, None) == 1    # ldb < T
+    assert lib.hsr_ridge_assemble_batched(f, 24, 0, 16, 4, 8, 1.0, f, 32, 0, f, 8, 0, f, 0, None) == 1
+    assert lib.hsr_ridge_finish(f, 16, 4, 8, f, 7, f, f, 4, 4, f, f, f, f, f, None) == 1   # ldw < T
+    assert lib.hsr_ridge_finish_batched(f, 0, 16, 4, 8, f, 8, 0, f, f, 0, 4, 4, f, f, 0, f, 0, f, f, 0, f, None, 1, None) == 1
+    assert lib.hsr_polyfeat_predict(f, 4, 1, f, f, 10, 4, 1, f, 7, f, 8, 0, f, 10, None) == 1       # ldw < T
+    assert lib.hsr_polyfeat_predict_cube(f, 4, 1, f, f, 10, 4, 1, f, 8, f, 8, 0, 0, 0.0, 0, f, 9, None) == 1   # out_stride < npix
+    assert lib.hsr_polyfeat_predict_cube_batched(f, 4, 1, 0, f, f, 0, 10, 4, 1, f, 8, 0, f, 0, 8, 0, 0, 0.0, 0, f, 10, 0, 0,
+                                                 None) == 1
+    assert lib.hsr_k4_last_launch(buf, 64) == 0 and buf.value == b""
+    assert lib.hsr_k4_last_launch(None, 0) == 0
+    n = lib.hsr_k4_instance_count()
+    assert n == 31 and lib.hsr_k4_instance_count() == n
+    names = [lib.hsr_k4_instance_name(i) for i in range(n)]
+    assert all(isinstance(s, bytes) and s for s in names) and len(set(names)) == n
+    assert names == [lib.hsr_k4_instance_name(i) for i in range(n)]
+    for bad in (-1, n, 1 << 20):
+        assert lib.hsr_k4_instance_name(bad) is None and b"hsr_k4_instance_name" in lib.hsr_last_error()
+    want = ({"expand_f64_kernel", "pair_expand_f64_kernel", "ridge_stats_partial_kernel", "ridge_stats_finish_kernel",
+             "ridge_assemble_kernel", "ridge_finish_kernel", "predict_kernel<1>", "predict_kernel<2>", "predict_kernel<4>"}
+            | {f"{k} {arm}" for k in ("predict103_x16_kernel", "predict103_slice_kernel<1>", "predict103_slice_kernel<2>",
+                                      "predict103_slice_kernel<3>") for arm in ("x2", "scalar")}
+            | {f"gram_f64_lds_kernel {k}" for k in ("wide", "diag", "narrow", "wide+diag", "wide+narrow", "diag+narrow",
+                                                    "wide+diag+narrow")}
+            | {"gram_f64_kernel sym", "gram_f64_kernel full", "gram_reduce_kernel", "chol_factor_res_kernel", "chol_factor_kernel",
+               "chol_solve_kernel lds", "chol_solve_kernel global"})
+    assert {s.decode() for s in names} == want
+    assert max(len(a) + 2 + len(b) for a in names for b in names) < 96     # any two names joined fit a 96-byte buffer
+
+
 def test_aux_instance_enumeration():
     """hsr_aux_instance_name: every name the record can return - unique, stable, the template spellings of the sources."""
     lib = nat.load()
