@@ -636,6 +636,174 @@ __global__ __launch_bounds__(kScoreFinishThreads) void pair_score_finish_kernel(
   }
 }
 
+// Pooled models (fuse_tile_pairs(pool=...)): M groups of pairs share one model each.  Membership is two small arrays the host
+// builds: order (P) = the pairs sorted by (group, pair index), start (M + 1) = each group's slice of order; group_of (P) is the
+// inverse map.  Every merge walks a group's members in pair-index order, skips a member whose stats[0] (its training pixels) is 0
+// and COPIES the first non-empty member, so a singleton group, and a group with empty members, carries the bits of the group
+// without them.  A pair index outside [0, P), a group id outside [0, M) or a slice outside [0, P] is skipped, never dereferenced.
+//   pool stats   one wave per group, lane c owns band c: [n, mean.., M2..] of the members merged by Chan's update (as
+//                PolyRidge.combine_stats / rep_merge write it); the group's mean and scale go to the group (M, nb) arrays and to
+//                every member's row of the pair (P, nb) arrays, which hsr_pair_expand_f64 then reads as it reads hsr_pair_stats'.
+//   pool gram    grid (chunks of elements, M): a thread owns its elements for the whole walk and adds the members' values in
+//                order (float64), four members' loads in flight ahead of the adds; 16-byte loads in the vector instance.
+//   pool models  grid (chunks, P): pair p gets its group's fitted model - Bp rows [0, nf) (zero rows up to npad), b64, W32, b32,
+//                mean32, inv32 - its status word and the report's (non-zero for a failed group or a pair without training pixels).
+constexpr int kPoolAhead = 4;                      // members whose loads are issued before their adds
+constexpr int kPoolGramThreads = 256;
+
+__device__ __forceinline__ void pool_slice(const int32_t* __restrict__ start, int g, int P, int& k0, int& k1) {
+  k0 = start[g];
+  k1 = start[g + 1];
+  k0 = k0 < 0 ? 0 : (k0 > P ? P : k0);
+  k1 = k1 < k0 ? k0 : (k1 > P ? P : k1);
+}
+
+__global__ __launch_bounds__(64) void pool_stats_kernel(const double* __restrict__ stats, int nb, int P,
+                                                        const int32_t* __restrict__ order, const int32_t* __restrict__ start,
+                                                        double* __restrict__ gstats, int64_t* __restrict__ n_pool,
+                                                        double* __restrict__ gmean, double* __restrict__ gscale,
+                                                        double* __restrict__ mean_out, double* __restrict__ scale_out) {
+  const int g = blockIdx.x, c = threadIdx.x;
+  if (c >= nb) return;
+  const int ls = 1 + 2 * nb;
+  int k0, k1;
+  pool_slice(start, g, P, k0, k1);
+  double n = 0.0, mean = 0.0, m2 = 0.0;
+  for (int k = k0; k < k1; ++k) {
+    const int p = order[k];
+    if (p < 0 || p >= P) continue;
+    const double* s = stats + (int64_t)p * ls;
+    const double nb_ = s[0];
+    if (nb_ == 0.0) continue;
+    const double mb = s[1 + c], m2b = s[1 + nb + c];
+    if (n == 0.0) {
+      n = nb_, mean = mb, m2 = m2b;
+      continue;
+    }
+    const double tot = n + nb_, delta = mb - mean;
+    mean += delta * (nb_ / tot);
+    m2 = m2 + m2b + delta * delta * (n * nb_ / tot);
+    n = tot;
+  }
+  const double sc = n > 0.0 ? sqrt(m2 / n) : 0.0;
+  const double scale = sc == 0.0 ? 1.0 : sc;
+  gstats[(int64_t)g * ls + 1 + c] = mean;
+  gstats[(int64_t)g * ls + 1 + nb + c] = m2;
+  gmean[(int64_t)g * nb + c] = mean;
+  gscale[(int64_t)g * nb + c] = scale;
+  if (c == 0) {
+    gstats[(int64_t)g * ls] = n;
+    n_pool[g] = (int64_t)n;
+  }
+  for (int k = k0; k < k1; ++k) {
+    const int p = order[k];
+    if (p < 0 || p >= P) continue;
+    mean_out[(int64_t)p * nb + c] = mean;
+    scale_out[(int64_t)p * nb + c] = scale;
+  }
+}
+
+template <bool kVec>
+__global__ __launch_bounds__(kPoolGramThreads) void pool_gram_kernel(const double* __restrict__ gsrc, int64_t pair_g, int64_t n_elems,
+                                                                     const double* __restrict__ cnt, int64_t pair_n, int P,
+                                                                     const int32_t* __restrict__ order,
+                                                                     const int32_t* __restrict__ start, double* __restrict__ out,
+                                                                     int64_t group_out) {
+  const int g = blockIdx.y;
+  const int64_t e0 = ((int64_t)blockIdx.x * kPoolGramThreads + threadIdx.x) * 2;   // this thread's elements: e0, e0 + 1
+  if (e0 >= n_elems) return;
+  const bool two = e0 + 1 < n_elems;               // always, in the vector instance (n_elems is even there)
+  int k0, k1;
+  pool_slice(start, g, P, k0, k1);
+  double ax = 0.0, ay = 0.0;
+  bool first = true;
+  for (int k = k0; k < k1; k += kPoolAhead) {
+    double vx[kPoolAhead], vy[kPoolAhead];
+    bool use[kPoolAhead];
+#pragma unroll
+    for (int u = 0; u < kPoolAhead; ++u) {
+      use[u] = false;
+      vx[u] = vy[u] = 0.0;
+      if (k + u >= k1) continue;
+      const int p = order[k + u];
+      if (p < 0 || p >= P || cnt[(int64_t)p * pair_n] == 0.0) continue;
+      use[u] = true;
+      const double* src = gsrc + (int64_t)p * pair_g + e0;
+      if (kVec) {
+        const double2 v = *reinterpret_cast<const double2*>(src);
+        vx[u] = v.x, vy[u] = v.y;
+      } else {
+        vx[u] = src[0];
+        if (two) vy[u] = src[1];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kPoolAhead; ++u) {
+      if (!use[u]) continue;
+      ax = first ? vx[u] : ax + vx[u];
+      ay = first ? vy[u] : ay + vy[u];
+      first = false;
+    }
+  }
+  double* dst = out + (int64_t)g * group_out + e0;
+  if (kVec) {
+    *reinterpret_cast<double2*>(dst) = make_double2(ax, ay);
+  } else {
+    dst[0] = ax;
+    if (two) dst[1] = ay;
+  }
+}
+
+struct PoolModelArgs {
+  const double* g_bp;                  // (M, >= nf rows, T) group models; group strides below
+  const double* g_b64;                 // (M, T)
+  const float* g_w32;                  // (M, kpad, T)
+  const float* g_b32;                  // (M, T)
+  const float* g_mean32;               // (M, nb)
+  const float* g_inv32;                // (M, nb)
+  const int32_t* pool_status;          // (M)
+  const int64_t* n_train;              // (P)
+  const int32_t* group_of;             // (P)
+  double* bp;                          // (P, npad, T) and the rest per pair, contiguous
+  double* b64;
+  float* w32;
+  float* b32;
+  float* mean32;
+  float* inv32;
+  int32_t* status;                     // (P)
+  int32_t* report_status;              // (P)
+  int64_t group_bp, group_w32;         // element strides between groups of g_bp and g_w32
+  int32_t nf, npad, kpad, T, nb, M;
+};
+
+__global__ __launch_bounds__(256) void pool_models_kernel(const PoolModelArgs a) {
+  const int64_t pr = blockIdx.y;
+  const int g = a.group_of[pr];
+  if (g < 0 || g >= a.M) return;
+  const int64_t nbp = (int64_t)a.npad * a.T, nw = (int64_t)a.kpad * a.T;
+  const int64_t o_b64 = nbp, o_w = o_b64 + a.T, o_b32 = o_w + nw, o_mean = o_b32 + a.T, o_inv = o_mean + a.nb, total = o_inv + a.nb;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    if (e < o_b64) {
+      a.bp[pr * nbp + e] = e < (int64_t)a.nf * a.T ? a.g_bp[g * a.group_bp + e] : 0.0;
+    } else if (e < o_w) {
+      a.b64[pr * a.T + (e - o_b64)] = a.g_b64[(int64_t)g * a.T + (e - o_b64)];
+    } else if (e < o_b32) {
+      a.w32[pr * nw + (e - o_w)] = a.g_w32[g * a.group_w32 + (e - o_w)];
+    } else if (e < o_mean) {
+      a.b32[pr * a.T + (e - o_b32)] = a.g_b32[(int64_t)g * a.T + (e - o_b32)];
+    } else if (e < o_inv) {
+      a.mean32[pr * a.nb + (e - o_mean)] = a.g_mean32[(int64_t)g * a.nb + (e - o_mean)];
+    } else {
+      a.inv32[pr * a.nb + (e - o_inv)] = a.g_inv32[(int64_t)g * a.nb + (e - o_inv)];
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int32_t s = a.pool_status[g];
+    a.status[pr] = s;
+    a.report_status[pr] = s != 0 ? s : (a.n_train[pr] == 0 ? 1 : 0);
+  }
+}
+
 }  // namespace hsr
 
 using namespace hsr;
@@ -762,5 +930,67 @@ extern "C" int hsr_pair_score_f64(const float* pred_dev, int64_t pair_pred, cons
   hipLaunchKernelGGL(pair_score_finish_kernel, dim3((unsigned)npairs), dim3(kScoreFinishThreads), 0, (hipStream_t)stream, work_dev, pair_work,
                      (int)chunks, T, ergas_scale, o);
   HSR_LAUNCH_CHECK("pair_score_finish_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_pool_stats(const double* stats_dev, int32_t nb, int32_t npairs, const int32_t* order_dev, const int32_t* start_dev,
+                              int32_t ngroups, double* gstats_dev, int64_t* n_pool_dev, double* gmean_dev, double* gscale_dev,
+                              double* mean_dev, double* scale_dev, hsr_stream_t stream) {
+  HSR_REQUIRE(stats_dev && order_dev && start_dev && gstats_dev && n_pool_dev && gmean_dev && gscale_dev && mean_dev && scale_dev,
+              HSR_ERR_INVALID, "hsr_pool_stats: NULL pointer");
+  HSR_REQUIRE(nb >= 1 && nb <= kPairMaxIn && npairs >= 1 && npairs <= 65535 && ngroups >= 1 && ngroups <= npairs, HSR_ERR_INVALID,
+              "hsr_pool_stats: bad shape (nb=%d P=%d M=%d)", nb, npairs, ngroups);
+  hipLaunchKernelGGL(pool_stats_kernel, dim3((unsigned)ngroups), dim3(64), 0, (hipStream_t)stream, stats_dev, nb, npairs, order_dev,
+                     start_dev, gstats_dev, n_pool_dev, gmean_dev, gscale_dev, mean_dev, scale_dev);
+  HSR_LAUNCH_CHECK("pool_stats_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_pool_gram(const double* g_dev, int64_t pair_g, int64_t n_elems, const double* count_dev, int64_t pair_count,
+                             int32_t npairs, const int32_t* order_dev, const int32_t* start_dev, int32_t ngroups, double* out_dev,
+                             int64_t group_out, hsr_stream_t stream) {
+  HSR_REQUIRE(g_dev && count_dev && order_dev && start_dev && out_dev, HSR_ERR_INVALID, "hsr_pool_gram: NULL pointer");
+  HSR_REQUIRE(n_elems >= 1 && npairs >= 1 && npairs <= 65535 && ngroups >= 1 && ngroups <= npairs && pair_count >= 1,
+              HSR_ERR_INVALID, "hsr_pool_gram: bad shape (n_elems=%lld P=%d M=%d)", (long long)n_elems, npairs, ngroups);
+  HSR_REQUIRE((npairs == 1 || pair_g >= n_elems) && (ngroups == 1 || group_out >= n_elems), HSR_ERR_INVALID,
+              "hsr_pool_gram: strides overlap");
+  const int64_t chunks = (n_elems + 2 * kPoolGramThreads - 1) / (2 * kPoolGramThreads);
+  HSR_REQUIRE(chunks <= 0x7fffffff, HSR_ERR_UNSUPPORTED, "hsr_pool_gram: n_elems=%lld too large", (long long)n_elems);
+  // a 16-byte load per thread and member needs even sizes and strides and aligned bases; anything else takes the plain instance
+  const bool vec = n_elems % 2 == 0 && pair_g % 2 == 0 && group_out % 2 == 0 && ((uintptr_t)g_dev & 15) == 0 &&
+                   ((uintptr_t)out_dev & 15) == 0;
+  const dim3 grid((unsigned)chunks, (unsigned)ngroups);
+  if (vec)
+    hipLaunchKernelGGL(pool_gram_kernel<true>, grid, dim3(kPoolGramThreads), 0, (hipStream_t)stream, g_dev, pair_g, n_elems,
+                       count_dev, pair_count, npairs, order_dev, start_dev, out_dev, group_out);
+  else
+    hipLaunchKernelGGL(pool_gram_kernel<false>, grid, dim3(kPoolGramThreads), 0, (hipStream_t)stream, g_dev, pair_g, n_elems,
+                       count_dev, pair_count, npairs, order_dev, start_dev, out_dev, group_out);
+  HSR_LAUNCH_CHECK("pool_gram_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_pool_models(const double* gbp_dev, int64_t group_bp, const double* gb64_dev, const float* gw32_dev,
+                               int64_t group_w32, const float* gb32_dev, const float* gmean32_dev, const float* ginv32_dev,
+                               const int32_t* pool_status_dev, const int64_t* n_train_dev, const int32_t* group_of_dev, int32_t nf,
+                               int32_t npad, int32_t kpad, int32_t T, int32_t nb, double* bp_dev, double* b64_dev, float* w32_dev,
+                               float* b32_dev, float* mean32_dev, float* inv32_dev, int32_t* status_dev, int32_t* report_status_dev,
+                               int32_t npairs, int32_t ngroups, hsr_stream_t stream) {
+  HSR_REQUIRE(gbp_dev && gb64_dev && gw32_dev && gb32_dev && gmean32_dev && ginv32_dev && pool_status_dev && n_train_dev &&
+              group_of_dev && bp_dev && b64_dev && w32_dev && b32_dev && mean32_dev && inv32_dev && status_dev && report_status_dev,
+              HSR_ERR_INVALID, "hsr_pool_models: NULL pointer");
+  HSR_REQUIRE(nf >= 1 && npad >= nf && kpad >= nf && T >= 1 && nb >= 1 && nb <= kPairMaxIn && npairs >= 1 && npairs <= 65535 &&
+              ngroups >= 1 && ngroups <= npairs, HSR_ERR_INVALID,
+              "hsr_pool_models: bad shape (nf=%d npad=%d kpad=%d T=%d nb=%d P=%d M=%d)", nf, npad, kpad, T, nb, npairs, ngroups);
+  HSR_REQUIRE(ngroups == 1 || (group_bp >= (int64_t)nf * T && group_w32 >= (int64_t)kpad * T), HSR_ERR_INVALID,
+              "hsr_pool_models: group strides overlap");
+  const PoolModelArgs a{gbp_dev, gb64_dev, gw32_dev, gb32_dev, gmean32_dev, ginv32_dev, pool_status_dev, n_train_dev, group_of_dev,
+                        bp_dev, b64_dev, w32_dev, b32_dev, mean32_dev, inv32_dev, status_dev, report_status_dev, group_bp, group_w32,
+                        nf, npad, kpad, T, nb, ngroups};
+  const int64_t total = (int64_t)npad * T + (int64_t)kpad * T + 2 * (int64_t)T + 2 * nb;
+  const int64_t blocks = (total + 1023) / 1024;              // 4 elements per thread, at most 64 blocks per pair
+  hipLaunchKernelGGL(pool_models_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)npairs), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  HSR_LAUNCH_CHECK("pool_models_kernel");
   return HSR_OK;
 }

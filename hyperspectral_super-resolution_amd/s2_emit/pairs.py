@@ -15,6 +15,17 @@ launch) and ``validate=True`` scores the result against the EMIT tile on the fit
 to S2 on the EMIT grid and for the 10 m cube averaged back to it (see ``TilePairValidation``).  Nothing synchronises with the host and no pixel crosses PCIe for device inputs.  A pair's arithmetic
 does not depend on the batch: ``fuse_tile_pairs`` of a batch gives the bits of ``fuse_tile_pair`` of each of its pairs.
 
+``pool=`` shares one model among a group of pairs: M groups, each fitted on the training pixels of all its members and applied to
+every member, also to members that were kept out of the fit as a whole (``train_mask`` all False) - with ``validate=True`` that
+is generalisation to unseen tiles, where hold-out inside a tile measures interpolation.  Nothing is concatenated: a group's
+StandardScaler is a Chan merge of its members' ``[n, mean, M2]`` (``hsr_pool_stats``), every member's rows are expanded with the
+group's mean and scale, so the group's Gram is the sum of its members' Grams (``hsr_pool_gram``), M systems are assembled,
+factorised and read out instead of P, and one launch hands every pair a copy of its group's model in the per-pair layout that
+the report, predict and validate steps read (``hsr_pool_models``): three launches more than without pooling, whatever P and M
+are.  Merges walk a group's members in pair-index order, skip members without training pixels and copy the first one, so
+singleton groups give the bits of ``pool=None`` and a group does not depend on the other groups of its batch.
+``TilePairOutput.predict`` applies the fitted models to S2 tiles that have no EMIT partner.
+
 S2 -> EMIT grid: an f x f block mean (float64 sum of the f^2 samples, stored as float32: the bits of ``hsr_block_mean``);
 a coarse pixel whose block holds a non-finite or ``s2_nodata`` sample is NaN and so leaves the training set.  The
 notebook's GDAL bilinear ``reproject`` is NOT reproduced (rasterio is absent, that parity is unpinned); a caller who has
@@ -92,6 +103,8 @@ class _Plan:
     emit_dtype: str
     s2_dtype: str
     plane_slices: tuple = ()
+    pool: Optional[np.ndarray] = None          # (P,) int32 group ids 0 .. M-1, None without pooling
+    M: int = 0
 
 
 def _plane_slices(P: int, T: int, limit: int = _MAX_PLANES):
@@ -103,9 +116,48 @@ def _plane_slices(P: int, T: int, limit: int = _MAX_PLANES):
     return tuple((p0, min(p0 + step, P)) for p0 in range(0, P, step))
 
 
-def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False, train_mask=None, validate=False) -> _Plan:
+def _pool_ids(pool, P: int) -> np.ndarray:
+    """``pool`` -> the (P,) int32 group ids 0 .. M-1 (host data only; see ``fuse_tile_pairs``)."""
+    if isinstance(pool, str):
+        if pool != "all":
+            raise ValueError(f"pool={pool!r}: None, 'all' or a sequence of {P} group ids")
+        return np.zeros(P, dtype=np.int32)
+    if _is_torch(pool):
+        if pool.device.type != "cpu":
+            raise ValueError("pool: the group ids are host data (a list or a NumPy array); reading a device tensor would need a "
+                             "host sync")
+        pool = pool.numpy()
+    if isinstance(pool, (bool, np.bool_)):
+        raise ValueError("pool: a bool is not a list of group ids")
+    try:
+        ids = np.asarray(pool)
+    except Exception:
+        raise ValueError(f"pool={pool!r}: None, 'all' or a sequence of {P} group ids") from None
+    if ids.dtype.kind not in "iu":
+        raise ValueError(f"pool: the group ids must be integers, got {ids.dtype}")
+    if ids.shape != (P,):
+        raise ValueError(f"pool: expected {P} group ids, one per pair, got shape {ids.shape}")
+    if ids.min() < 0:
+        raise ValueError(f"pool: negative group id {int(ids.min())}")
+    used = np.unique(ids)
+    if int(used[-1]) != len(used) - 1:
+        raise ValueError(f"pool: the group ids must be exactly 0 .. M-1, each used at least once; got {len(used)} distinct ids "
+                         f"up to {int(used[-1])}")
+    return ids.astype(np.int32)
+
+
+def pool_layout(ids: np.ndarray):
+    """(order, start) of the group ids ``ids`` (P,), values 0 .. M-1: order (P,) int32 = the pairs sorted by (group, pair index),
+    start (M + 1,) int32 = each group's slice of order.  What the pooling kernels walk (include/hsr.h)."""
+    ids = np.asarray(ids, dtype=np.int64)
+    order = np.argsort(ids, kind="stable").astype(np.int32)
+    start = np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=int(ids.max()) + 1))]).astype(np.int32)
+    return order, start
+
+
+def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False, train_mask=None, validate=False, pool=None) -> _Plan:
     """Every check that needs no GPU: shapes, dtypes, the factor, the bands, the size of the ridge system, the report and
-    validate flags and the training mask."""
+    validate flags, the training mask and the pooling."""
     if not isinstance(report, bool):
         raise ValueError(f"report={report!r}: must be True or False")
     if not isinstance(validate, bool):
@@ -140,7 +192,9 @@ def _plan(emits, s2s, bands, degree, factor, s2_coarse, report=False, train_mask
         if mshape != (P, h, w) or mdt not in ("bool", "uint8"):
             raise ValueError(f"train_mask: expected bool or uint8 {(P, h, w)}, got {mdt} {mshape}")
     idx = _bands_index(bands, B)
-    return _Plan(P, B, h, w, nb, f, idx, edt, sdt, _plane_slices(P, len(idx)) if validate else ())
+    ids = _pool_ids(pool, P) if pool is not None else None
+    return _Plan(P, B, h, w, nb, f, idx, edt, sdt, _plane_slices(P, len(idx)) if validate else (), ids,
+                 int(ids.max()) + 1 if ids is not None else 0)
 
 
 def _stack_dev(x, torch, dev):
@@ -173,6 +227,30 @@ def _bands_dev(idx: np.ndarray, torch, dev):
     t = _BANDS_CACHE.get(key)
     if t is None:
         t = _BANDS_CACHE[key] = torch.from_numpy(idx.copy()).to(dev)
+    return t
+
+
+_POOL_CACHE: dict = {}
+
+
+def _pool_dev(ids: np.ndarray, torch, dev):
+    """(order, start, group_of) int32 device tensors of the group ids, uploaded once per id list and device."""
+    key = (ids.tobytes(), str(dev))
+    t = _POOL_CACHE.get(key)
+    if t is None:
+        order, start = pool_layout(ids)
+        t = _POOL_CACHE[key] = tuple(torch.from_numpy(a.copy()).to(dev) for a in (order, start, ids))
+    return t
+
+
+_INDEX_CACHE: dict = {}
+
+
+def _index_dev(idx: np.ndarray, torch, dev):
+    key = (idx.tobytes(), str(dev))
+    t = _INDEX_CACHE.get(key)
+    if t is None:
+        t = _INDEX_CACHE[key] = torch.from_numpy(idx.copy()).to(dev)
     return t
 
 
@@ -227,7 +305,13 @@ class TilePairOutput:
     r2, rmse (P, T) float64 with ``report=True`` (else None): the fit scored on its own training pixels as the notebook's cell 26
              does - yp = sigmoid(clip(float32(model(X_train)), +-50)) in float32, d = y - yp against the decoded targets,
              r2 = 1 - sum d^2 / (sum (y - mean y)^2 + 1e-8), rmse = sqrt(mean d^2), sums in float64; NaN where status != 0.
-    ``model(i)`` is pair i's model as a ``PolyRidge`` (its host attributes are copied on first access)."""
+    ``model(i)`` is pair i's model as a ``PolyRidge`` (its host attributes are copied on first access).
+
+    With ``pool=`` (else None): pool (P,) NumPy int32, each pair's group; n_pool (M,) int64, the training pixels of each group;
+    pool_status (M,) int32, the status of each group's fit.  ``status`` is then the group's status per pair, ``n_train`` stays each
+    pair's own count, ``model(i)`` is the model of pair i's group and ``pool_model(g)`` that of group g; ``r2`` / ``rmse`` score a
+    pair's own training pixels with its group's model and are NaN for a pair that supplied none.
+    ``predict(s2s, model_index)`` applies the fitted models to S2 tiles that have no EMIT partner."""
     cube: Any
     n_train: Any
     status: Any
@@ -242,14 +326,64 @@ class TilePairOutput:
     valid: Any = None
     held_out: Any = None
     validation: Optional[TilePairValidation] = None
+    pool: Optional[np.ndarray] = None
+    n_pool: Any = None
+    pool_status: Any = None
+    _pool_fit: Optional[dict] = field(repr=False, default=None)
 
-    def model(self, i: int) -> PolyRidge:
-        f = self._fit
+    def _model_of(self, f: dict, i: int) -> PolyRidge:
         m = PolyRidge(self.degree, self.alpha)
         m.n_in, m.n_feat, m.n_targets = f["n_in"], f["nf"], len(self.bands)
         m._fit64 = (f["mean"][i], f["scale"][i], f["Bp"][i, :f["nf"]], f["b64"][i])
         m._dev = dict(W=f["W32"][i], b=f["b32"][i], mean=f["mean32"][i], inv=f["inv32"][i])
         return m
+
+    def model(self, i: int) -> PolyRidge:
+        return self._model_of(self._fit, i)
+
+    def pool_model(self, g: int) -> PolyRidge:
+        """Group g's model (``pool=`` only): the one every member's cube comes from."""
+        if self._pool_fit is None:
+            raise ValueError("pool_model: this output was not fitted with pool=")
+        return self._model_of(self._pool_fit, g)
+
+    def predict(self, s2s, model_index=None, s2_nodata: Optional[float] = None):
+        """Apply fitted models to Q S2 tiles that have no EMIT partner: s2s (Q, nb, H, W) uint16 DN or float32 (a tensor, an
+        array or a list of cubes; any H and W), model_index a host array of Q pair indices (tile q takes ``model(model_index[q])``;
+        optional when there is one pair or one group: all zeros) -> (Q, T, H, W) float32 on the device with the bits of
+        ``model(model_index[q]).predict_cube(s2s[q], nodata=s2_nodata)``.  One predict launch over the gathered model rows on the
+        current stream; nothing synchronises with the host."""
+        f = self._fit
+        nb, P = f["n_in"], f["b64"].shape[0]
+        (Q, nbq, H, W), sdt = _describe(s2s, "s2", 3)
+        if nbq != nb or sdt not in _DTYPES:
+            raise ValueError(f"predict: s2 is {sdt} with {nbq} bands, the models take {nb} bands of uint16 or float32")
+        if model_index is None:
+            if P != 1 and (self.pool is None or int(self.pool.max()) != 0):
+                raise ValueError(f"predict: model_index is required with {P} pairs that do not share one model")
+            idx = np.zeros(Q, dtype=np.int64)
+        else:
+            if _is_torch(model_index) and model_index.device.type != "cpu":
+                raise ValueError("predict: model_index is host data; reading a device tensor would need a host sync")
+            idx = np.asarray(model_index)
+            if idx.dtype.kind not in "iu" or idx.shape != (Q,):
+                raise ValueError(f"predict: model_index must hold {Q} integer pair indices, got {idx.dtype} of shape {idx.shape}")
+            if idx.min() < 0 or idx.max() >= P:
+                raise ValueError(f"predict: model_index must lie in [0, {P}), got [{idx.min()}, {idx.max()}]")
+            idx = idx.astype(np.int64)
+        torch = nat.require_gpu()
+        lib = nat.load()
+        dev = f["b64"].device
+        S = _stack_dev(s2s, torch, dev)
+        Xf = (S.to(torch.int32) & 0xFFFF).to(torch.float32) if sdt == "uint16" else S      # as step 6 of fuse_tile_pairs
+        rows = _index_dev(idx, torch, dev)
+        model = dict(W=f["W32"].index_select(0, rows), b=f["b32"].index_select(0, rows), mean=f["mean32"].index_select(0, rows),
+                     inv=f["inv32"].index_select(0, rows))
+        nat.check(lib.hsr_polyfeat_prepare(nb, self.degree), "hsr_polyfeat_prepare")
+        T, npix = len(self.bands), H * W
+        out = torch.empty((Q, T, npix), dtype=torch.float32, device=dev)
+        _predict_batched(lib, _stream(torch), self.degree, model, _ptr(Xf), 1, npix, nb * npix, npix, Q, 1, True, s2_nodata, out)
+        return out.view(Q, T, H, W)
 
 
 # What the fit of fuse_tile_pairs (steps 1 - 5) hands to the steps that read it: fit = TilePairOutput._fit; model = the predict
@@ -260,7 +394,7 @@ _FitState = namedtuple("_FitState", "fit model x y group degree")
 
 def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                     emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                    eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False) -> TilePairOutput:
+                    eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False, pool=None) -> TilePairOutput:
     """P tile pairs -> their fused 10 m cubes (see the module docstring).
 
     emits: (P, bands, h, w) uint16 (decoded as ``u == 65535 ? NaN : float32(u) * 1e-4f``) or float32 reflectance (with an
@@ -272,8 +406,13 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     train_mask: (P, h, w) bool / uint8 (array, tensor or list of (h, w) ones): the fit uses ``valid & train_mask``; ``n_train``,
     ``status`` and the report follow that mask, the other valid pixels are ``held_out``.
     validate: also score the prediction against the EMIT tile (``validation``, see ``TilePairValidation``); a fixed number of
-    launches more, no host sync, and every other output keeps its bits."""
-    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse, report, train_mask, validate)
+    launches more, no host sync, and every other output keeps its bits.
+    pool: None (a model per pair), ``"all"`` (one model from the training pixels of all P pairs) or P ints on the host (a list or a
+    NumPy array; a device tensor is refused, reading it would need a host sync): pair i belongs to group ``pool[i]``, the ids being
+    exactly 0 .. M-1.  A group is fitted on the union of its members' ``valid & train_mask`` pixels and every member's cube comes
+    from that model, also a member that supplied no training pixel (``train_mask`` all False: a wholly held-out pair, status 0); a
+    group without any training pixel has status 1 and all-NaN cubes.  See ``TilePairOutput`` for the outputs under pooling."""
+    plan = _plan(emits, s2s, bands, degree, factor, s2_coarse, report, train_mask, validate, pool)
     torch = nat.require_gpu()
     lib = nat.load()
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -311,6 +450,18 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     n_train = torch.empty(P, dtype=torch.int64, device=dev)
     nat.check(lib.hsr_pair_stats(_ptr(x), _ptr(mask), npix, nb, _ptr(stats), _ptr(mean), _ptr(scale), _ptr(n_train), P, st),
               "hsr_pair_stats")
+    pooled = plan.pool is not None
+    M = plan.M if pooled else P                        # the systems to solve: one per group, or one per pair
+    if pooled:                                         # the group's scaler for every member (Chan merge of the pairs' statistics)
+        order, start, group_of = _pool_dev(plan.pool, torch, dev)
+        gstats = torch.empty((M, 1 + 2 * nb), **f64)
+        n_pool = torch.empty(M, dtype=torch.int64, device=dev)
+        gmean = torch.empty((M, nb), **f64)
+        gscale = torch.empty((M, nb), **f64)
+        mean = torch.empty((P, nb), **f64)
+        scale = torch.empty((P, nb), **f64)
+        nat.check(lib.hsr_pool_stats(_ptr(stats), nb, P, _ptr(order), _ptr(start), M, _ptr(gstats), _ptr(n_pool), _ptr(gmean),
+                                     _ptr(gscale), _ptr(mean), _ptr(scale), st), "hsr_pool_stats")
     # 3. [1 | Phi | logit(y)] rows of the training pixels, zero rows for the others; 4. their Gram
     Q = torch.empty((P, npix, ldq), **f64)
     nat.check(lib.hsr_pair_expand_f64(_ptr(x), nb * npix, _ptr(mean), _ptr(scale), nb, _ptr(y), T * npix, _ptr(mask), npix, npix,
@@ -320,25 +471,28 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     G = torch.empty((P, na, ldq), **f64)
     nat.check(lib.hsr_gram_f64_batched(_ptr(Q), ldq, na, ldq, npix, npix * ldq, _ptr(work), wq, _ptr(G), ldq, na * ldq, P, st),
               "hsr_gram_f64_batched")
-    # 5. centred ridge systems, P Cholesky factorisations side by side, model read-out
-    Gp = torch.empty((P, npad, npad), **f64)
-    Bp = torch.empty((P, npad, T), **f64)
-    info = torch.empty(P, dtype=torch.int32, device=dev)
-    nat.check(lib.hsr_ridge_assemble_batched(_ptr(G), ldq, na * ldq, na, nf, T, float(alpha), _ptr(Gp), npad, npad * npad, _ptr(Bp),
-                                             T, npad * T, _ptr(info), P, st), "hsr_ridge_assemble_batched")
-    cw = lib.hsr_chol_work_bytes(npad) // 8
-    cwork = torch.empty((P, cw), **f64)
-    nat.check(lib.hsr_chol_solve_f64_batched(_ptr(Gp), npad, npad, npad * npad, _ptr(Bp), T, T, npad * T, _ptr(cwork), _ptr(info), P,
-                                             st), "hsr_chol_solve_f64_batched")
-    b64 = torch.empty((P, T), **f64)
-    W32 = torch.empty((P, kpad, T), **f32)
-    b32 = torch.empty((P, T), **f32)
-    mean32 = torch.empty((P, nb), **f32)
-    inv32 = torch.empty((P, nb), **f32)
-    status = torch.empty(P, dtype=torch.int32, device=dev)
-    nat.check(lib.hsr_ridge_finish_batched(_ptr(G), na * ldq, na, nf, T, _ptr(Bp), T, npad * T, _ptr(mean), _ptr(scale), nb, nb, kpad,
-                                           _ptr(b64), _ptr(b32), T, _ptr(W32), kpad * T, _ptr(mean32), _ptr(inv32), nb, _ptr(info),
-                                           _ptr(status), P, st), "hsr_ridge_finish_batched")
+    Gs, smean, sscale = G, mean, scale                 # the Gram, mean and scale of each system
+    if pooled:                                         # a group's Gram = the sum of its members' (rows expanded with one scaler)
+        Gs, smean, sscale = torch.empty((M, na, ldq), **f64), gmean, gscale
+        nat.check(lib.hsr_pool_gram(_ptr(G), na * ldq, na * ldq, _ptr(stats), 1 + 2 * nb, P, _ptr(order), _ptr(start), M, _ptr(Gs),
+                                    na * ldq, st), "hsr_pool_gram")
+    # 5. centred ridge systems, M Cholesky factorisations side by side (M = P without pooling), model read-out
+    fit, status, rstatus = _solve(lib, torch, st, dims, Gs, smean, sscale, nb, T, float(alpha), M)
+    pool_fit = pool_status = None
+    if pooled:                                         # every pair gets its group's model: the per-pair layout the later steps read
+        pool_fit, pool_status = fit, status
+        fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=torch.empty((P, npad, T), **f64), b64=torch.empty((P, T), **f64),
+                   W32=torch.empty((P, kpad, T), **f32), b32=torch.empty((P, T), **f32), mean32=torch.empty((P, nb), **f32),
+                   inv32=torch.empty((P, nb), **f32))
+        status = torch.empty(P, dtype=torch.int32, device=dev)
+        rstatus = torch.empty(P, dtype=torch.int32, device=dev)
+        g = pool_fit
+        nat.check(lib.hsr_pool_models(_ptr(g["Bp"]), npad * T, _ptr(g["b64"]), _ptr(g["W32"]), kpad * T, _ptr(g["b32"]),
+                                      _ptr(g["mean32"]), _ptr(g["inv32"]), _ptr(pool_status), _ptr(n_train), _ptr(group_of), nf, npad,
+                                      kpad, T, nb, _ptr(fit["Bp"]), _ptr(fit["b64"]), _ptr(fit["W32"]), _ptr(fit["b32"]),
+                                      _ptr(fit["mean32"]), _ptr(fit["inv32"]), _ptr(status), _ptr(rstatus), P, M, st),
+                  "hsr_pool_models")
+    Bp, b64, W32, b32, mean32, inv32 = (fit[k] for k in ("Bp", "b64", "W32", "b32", "mean32", "inv32"))
     r2 = rmse = None
     if report:                                         # the notebook's cell 26 on the rows Q the fit read
         rw = lib.hsr_pair_report_work_bytes(npix, T) // 8
@@ -346,7 +500,7 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
         r2 = torch.empty((P, T), **f64)
         rmse = torch.empty((P, T), **f64)
         nat.check(lib.hsr_pair_report_f64(_ptr(Q), ldq, npix * ldq, na, npix, _ptr(b64), T, _ptr(Bp), T, npad * T, nf, _ptr(y),
-                                          T * npix, _ptr(mask), npix, T, _ptr(status), _ptr(rwork), rw, _ptr(r2), _ptr(rmse), T, P,
+                                          T * npix, _ptr(mask), npix, T, _ptr(rstatus), _ptr(rwork), rw, _ptr(r2), _ptr(rmse), T, P,
                                           st), "hsr_pair_report_f64")
     # 6. the 10 m prediction: predict_cube_logit's rule for unusable pixels, per pair
     if plan.s2_dtype == "uint16":                      # DN as float32 (exact), from the int16 bits
@@ -354,7 +508,6 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     else:
         Xf = S
     Xf = Xf.reshape(P, nb, npix10)
-    fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
     state = _FitState(fit, dict(W=W32, b=b32, mean=mean32, inv=inv32), x, y, group, int(degree))
     cube = _predict_batched(lib, st, state.degree, state.model, _ptr(Xf), 1, npix10, nb * npix10, npix10, P, 1, True, s2_nodata,
                             torch.empty((P, T, npix10), **f32))
@@ -364,7 +517,37 @@ def fuse_tile_pairs(emits, s2s, *, bands=32, degree: int = 3, alpha: float = 1.0
     valid_b = mask_b if Tm is None else valid.view(P, h, w).bool()
     return TilePairOutput(cube=cube.view(P, T, h * f, w * f), n_train=n_train, status=status, mask=mask_b,
                           s2_coarse=x.view(P, nb, h, w), bands=plan.bands, degree=int(degree), alpha=float(alpha), _fit=fit,
-                          r2=r2, rmse=rmse, valid=valid_b, held_out=held.view(P, h, w), validation=validation)
+                          r2=r2, rmse=rmse, valid=valid_b, held_out=held.view(P, h, w), validation=validation,
+                          pool=plan.pool, n_pool=n_pool if pooled else None, pool_status=pool_status, _pool_fit=pool_fit)
+
+
+def _solve(lib, torch, st, dims, G, mean, scale, nb: int, T: int, alpha: float, M: int):
+    """Step 5 for M systems: G (M, na, ldq) Grams with their float64 mean / scale (M, nb) -> (the fit arrays with a leading M
+    axis, status (M,), the report's status = the same tensor): assembly, M Cholesky factorisations side by side, read-out."""
+    nf, na, ldq, npad, kpad = dims.nf, dims.na, dims.ldq, dims.npad, dims.kpad
+    dev = G.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    Gp = torch.empty((M, npad, npad), **f64)
+    Bp = torch.empty((M, npad, T), **f64)
+    info = torch.empty(M, dtype=torch.int32, device=dev)
+    nat.check(lib.hsr_ridge_assemble_batched(_ptr(G), ldq, na * ldq, na, nf, T, alpha, _ptr(Gp), npad, npad * npad, _ptr(Bp),
+                                             T, npad * T, _ptr(info), M, st), "hsr_ridge_assemble_batched")
+    cw = lib.hsr_chol_work_bytes(npad) // 8
+    cwork = torch.empty((M, cw), **f64)
+    nat.check(lib.hsr_chol_solve_f64_batched(_ptr(Gp), npad, npad, npad * npad, _ptr(Bp), T, T, npad * T, _ptr(cwork), _ptr(info), M,
+                                             st), "hsr_chol_solve_f64_batched")
+    b64 = torch.empty((M, T), **f64)
+    W32 = torch.empty((M, kpad, T), **f32)
+    b32 = torch.empty((M, T), **f32)
+    mean32 = torch.empty((M, nb), **f32)
+    inv32 = torch.empty((M, nb), **f32)
+    status = torch.empty(M, dtype=torch.int32, device=dev)
+    nat.check(lib.hsr_ridge_finish_batched(_ptr(G), na * ldq, na, nf, T, _ptr(Bp), T, npad * T, _ptr(mean), _ptr(scale), nb, nb, kpad,
+                                           _ptr(b64), _ptr(b32), T, _ptr(W32), kpad * T, _ptr(mean32), _ptr(inv32), nb, _ptr(info),
+                                           _ptr(status), M, st), "hsr_ridge_finish_batched")
+    fit = dict(n_in=nb, nf=nf, mean=mean, scale=scale, Bp=Bp, b64=b64, W32=W32, b32=b32, mean32=mean32, inv32=inv32)
+    return fit, status, status
 
 
 def _validate(lib, torch, st, plan, state, cube, s2_nodata) -> TilePairValidation:
@@ -404,10 +587,11 @@ def _validate(lib, torch, st, plan, state, cube, s2_nodata) -> TilePairValidatio
 
 def fuse_tile_pair(emit, s2, *, bands=32, degree: int = 3, alpha: float = 1.0, factor: int = 6,
                    emit_nodata: Optional[float] = None, s2_nodata: Optional[float] = None, s2_coarse=None,
-                   eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False) -> TilePairOutput:
+                   eps: float = 1e-4, report: bool = False, train_mask=None, validate: bool = False, pool=None) -> TilePairOutput:
     """One tile pair: emit (bands, h, w), s2 (nb, h f, w f) -> a TilePairOutput with P = 1 (``cube[0]`` is (T, h f, w f)).
-    The same launches as ``fuse_tile_pairs``, so a pair gives the same bits alone as in any batch."""
+    The same launches as ``fuse_tile_pairs``, so a pair gives the same bits alone as in any batch (``pool``: None, ``"all"`` or
+    ``[0]``, which all give those bits)."""
     batch = lambda a: None if a is None else ([a] if not _is_torch(a) and not isinstance(a, np.ndarray) else a[None])
     return fuse_tile_pairs(batch(emit), batch(s2), bands=bands, degree=degree, alpha=alpha, factor=factor,
                            emit_nodata=emit_nodata, s2_nodata=s2_nodata, s2_coarse=batch(s2_coarse), eps=eps, report=report,
-                           train_mask=batch(train_mask), validate=validate)
+                           train_mask=batch(train_mask), validate=validate, pool=pool)

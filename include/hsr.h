@@ -579,6 +579,38 @@ int hsr_pair_score_f64(const float* pred_dev, int64_t pair_pred, const float* y_
                        int64_t* n_sam_dev, double* ergas_dev, int64_t pair_sam, float* sam_map_dev, int64_t pair_map,
                        int32_t npairs, hsr_stream_t stream);
 
+/* ---- tile pairs: pooled models (s2_emit.fuse_tile_pairs(pool=...)): M groups of pairs, one model per group ------------------------
+ * Membership is host-built int32 device arrays: order (P) = the pairs sorted by (group, pair index), start (M + 1) = each group's
+ * slice of order, group_of (P) = each pair's group.  Every merge walks a group's members in pair-index order, skips a member
+ * whose count (stats[0]) is 0 and copies the first non-empty member instead of adding it to zero: a singleton group, and a group
+ * with empty members, carries the bits of the group without them.  Indices out of range are skipped, never dereferenced.  One
+ * launch each, whatever P and M are.
+ * hsr_pool_stats: stats (P, 1 + 2 nb) as hsr_pair_stats writes it -> gstats (M, 1 + 2 nb) = [n, mean.., M2..] of each group by
+ *   Chan's update (tot = n + nb; delta = mb - mean; mean += delta * (nb / tot); M2 += M2b + delta * delta * (n * nb / tot)),
+ *   n_pool (M) int64, gmean / gscale (M, nb) = the group's StandardScaler (scale = sqrt(M2 / n), 0 -> 1; a group without a pixel:
+ *   0 / 1) and the same values per member in mean / scale (P, nb), where hsr_pair_expand_f64 reads them with pair_ms = nb.
+ * hsr_pool_gram: g (P; pair stride pair_g; n_elems contiguous doubles) -> out (M; stride group_out): the element-wise float64 sum
+ *   of each group's non-empty members in pair order (member p is empty when count_dev[p * pair_count] == 0: stats with stride
+ *   1 + 2 nb); zeros for a group without one.  16-byte loads when n_elems and the strides are even and the bases aligned, else a
+ *   plain instance with the same bits.
+ * hsr_pool_models: the M fitted groups' Bp rows [0, nf) (rows of T doubles, group stride group_bp), b64 (M, T), W32 (M; kpad T
+ *   floats, group stride group_w32), b32 (M, T), mean32 / inv32 (M, nb), pool_status (M) -> the contiguous per-pair arrays Bp
+ *   (P, npad, T; rows from nf on are zero), b64 (P, T), W32 (P, kpad, T), b32 (P, T), mean32 / inv32 (P, nb), status (P) = the
+ *   group's, and report_status (P) = non-zero where the group's status is non-zero or n_train[p] == 0 (hsr_pair_report_f64's
+ *   status argument: a pair that supplied no training pixel has no fit report). */
+int hsr_pool_stats(const double* stats_dev, int32_t nb, int32_t npairs, const int32_t* order_dev, const int32_t* start_dev,
+                   int32_t ngroups, double* gstats_dev, int64_t* n_pool_dev, double* gmean_dev, double* gscale_dev,
+                   double* mean_dev, double* scale_dev, hsr_stream_t stream);
+int hsr_pool_gram(const double* g_dev, int64_t pair_g, int64_t n_elems, const double* count_dev, int64_t pair_count, int32_t npairs,
+                  const int32_t* order_dev, const int32_t* start_dev, int32_t ngroups, double* out_dev, int64_t group_out,
+                  hsr_stream_t stream);
+int hsr_pool_models(const double* gbp_dev, int64_t group_bp, const double* gb64_dev, const float* gw32_dev, int64_t group_w32,
+                    const float* gb32_dev, const float* gmean32_dev, const float* ginv32_dev, const int32_t* pool_status_dev,
+                    const int64_t* n_train_dev, const int32_t* group_of_dev, int32_t nf, int32_t npad, int32_t kpad, int32_t T,
+                    int32_t nb, double* bp_dev, double* b64_dev, float* w32_dev, float* b32_dev, float* mean32_dev,
+                    float* inv32_dev, int32_t* status_dev, int32_t* report_status_dev, int32_t npairs, int32_t ngroups,
+                    hsr_stream_t stream);
+
 /* ---- f1: grid-aligned resamplers between the phases -----------------------------------------------
  * downsample_s2_to_grid ('average') and reproject_stack_to_grid ('bilinear') of the notebook
  * (Pairs_EMIT_S2_demo-2.ipynb cell 73, raw lines 4538-4599) for exactly aligned integer-factor grids:

@@ -6,6 +6,8 @@
     python tools/bench_tile_pairs.py --report --profile DIR   # the report=True batch under rocprofv3 (the report kernels)
     python tools/bench_tile_pairs.py --validate            # validate=False vs validate=True at P = 64, T = 32 and T = 285
     python tools/bench_tile_pairs.py --validate --profile DIR # the validate=True batch under rocprofv3 (the score kernels)
+    python tools/bench_tile_pairs.py --pool                # pool=None vs pool="all" vs groups of 8 at P = 64, T = 32 and T = 285
+    python tools/bench_tile_pairs.py --pool --profile DIR  # the two pooled batches under rocprofv3 (the pooling kernels)
 
 Configurations: P = 1, 8, 64 pairs at T = 32 targets, and P = 64 at T = 285 (EMIT 285 x 100 x 100 uint16, S2 10 x 600 x 600
 uint16, factor 6).  One JSON line per configuration:
@@ -26,6 +28,10 @@ score_held_out_us_per_view (the same with a checkerboard of 10 x 10 blocks held 
 which moves the same 2 P T npix 4 bytes), their rates and score_over_clone.  With --profile as well, from the kernel trace:
 score_us_per_batch (both views), score_read_tbps (4 P T npix 4 bytes over the partial kernels' time), and the block mean's and
 the coarse predict's time per batch.
+With --pool: none_ms_per_batch, all_ms_per_batch and groups_ms_per_batch - the batch without pooling, with ``pool="all"`` and with
+P / 8 groups of 8 pairs (``pool=arange(P) // 8``), timed in turn in one process over device events (median) - and each pooled
+time over the unpooled one; with --profile as well, one record per pooled mode with pool_us_per_batch (the three pooling kernels)
+and the per-kernel times.
 """
 from __future__ import annotations
 
@@ -203,6 +209,46 @@ def _score_vs_clone(torch, s2_emit, E, S, kw, iters):
                 score_over_clone=round(sm / cm, 2), score_held_out_over_clone=round(hm / cm, 2))
 
 
+def _pool_arg(mode, P):
+    """--pool-mode -> the ``pool`` argument: none, all, or groups of 8 pairs."""
+    import numpy as np
+    return {"none": None, "all": "all", "groups": np.arange(P) // 8}[mode]
+
+
+def child_pool(P, T, iters, warmup):
+    """pool=None, pool="all" and groups of 8, in turn, over device events (median of each)."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "hyperspectral_super-resolution_amd"))
+    import torch
+    import s2_emit
+    E, S = _pairs(torch, P)
+    kw = dict(bands=32 if T == 32 else "all", s2_nodata=0.0)
+    modes = ("none", "all", "groups")
+    for _ in range(warmup):
+        for m in modes:
+            s2_emit.fuse_tile_pairs(E, S, pool=_pool_arg(m, P), **kw)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(modes) + 1)]
+    ms = {m: [] for m in modes}
+    for _ in range(iters):
+        for i, m in enumerate(modes):
+            ev[i].record()
+            out = s2_emit.fuse_tile_pairs(E, S, pool=_pool_arg(m, P), **kw)
+            del out
+        ev[len(modes)].record()
+        torch.cuda.synchronize()
+        for i, m in enumerate(modes):
+            ms[m].append(ev[i].elapsed_time(ev[i + 1]))
+    med = {m: sorted(v)[len(v) // 2] for m, v in ms.items()}
+    rec = dict(P=P, T=T, iters=iters, groups=(P + 7) // 8)
+    for m in modes:
+        rec[f"{m}_ms_per_batch"] = round(med[m], 4)
+        rec[f"{m}_min_max_ms"] = [round(min(ms[m]), 4), round(max(ms[m]), 4)]
+    rec["all_over_none"] = round(med["all"] / med["none"], 3)
+    rec["groups_over_none"] = round(med["groups"] / med["none"], 3)
+    print(json.dumps(rec), flush=True)
+
+
 def _kernel_stats(out_dir):
     rows = []
     for path in glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True):
@@ -211,14 +257,15 @@ def _kernel_stats(out_dir):
     return rows
 
 
-def profile_one(P, T, iters, out_dir, report=False, validate=False):
+def profile_one(P, T, iters, out_dir, report=False, validate=False, pool="none"):
     """One configuration under rocprofv3, twice (1 and 1 + iters batches after the input generation): the difference of the two
     traces is `iters` batches alone - launches per batch, kernel time per batch, and the Gram / predict FLOP rates over it."""
     def run(n):
-        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}" + ("_report" if report else "") + ("_validate" if validate else ""))
+        d = os.path.join(out_dir, f"P{P}_T{T}_n{n}" + ("_report" if report else "") + ("_validate" if validate else "") +
+                         (f"_pool_{pool}" if pool != "none" else ""))
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "run", "--", sys.executable,
                os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(n), "--batch-only"] + \
-              (["--report"] if report else []) + (["--validate"] if validate else [])
+              (["--report"] if report else []) + (["--validate"] if validate else []) + ["--pool-mode", pool]
         subprocess.run(cmd, check=True, cwd=ROOT)
         per = {}
         for r in _kernel_stats(d):
@@ -249,6 +296,7 @@ def profile_one(P, T, iters, out_dir, report=False, validate=False):
                predict_tflops_f32=round(2.0 * npix10 * nf * T * P / pred_ns / 1e3, 2) if pred_ns else None,
                **(report_fields(ns, P, npix, na, iters) if report else {}),
                **(validate_fields(ns, P, npix, T) if validate else {}),
+               **(dict(pool=pool, pool_us_per_batch=round(ns(lambda n: "pool_" in n) / 1e3, 1)) if pool != "none" else {}),
                kernel_us_per_batch={k.split("(")[0][-60:]: round(v[1] / iters / 1e3, 1) for k, v in sorted(diff.items(), key=lambda kv: -kv[1][1])})
     print(json.dumps(rec), flush=True)
 
@@ -281,6 +329,8 @@ def main():
     ap.add_argument("--report", action="store_true", help="time report=False against report=True")
     ap.add_argument("--validate", action="store_true", help="time validate=False against validate=True, and the score call "
                     "against a clone of the same bytes")
+    ap.add_argument("--pool", action="store_true", help="time pool=None against pool='all' and groups of 8 pairs")
+    ap.add_argument("--pool-mode", default="none", choices=("none", "all", "groups"), help="(profiling) the pooling of --batch-only")
     a = ap.parse_args()
     if a.child:
         P, T = map(int, a.child.split(","))
@@ -291,20 +341,29 @@ def main():
             import s2_emit
             E, S = _pairs(torch, P)
             for _ in range(a.iters):
-                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0, report=a.report, validate=a.validate)
+                kw = dict(pool=_pool_arg(a.pool_mode, P)) if a.pool_mode != "none" else {}
+                s2_emit.fuse_tile_pairs(E, S, bands=32 if T == 32 else "all", s2_nodata=0.0, report=a.report, validate=a.validate, **kw)
             torch.cuda.synchronize()
             return
-        if a.validate:
+        if a.pool:
+            child_pool(P, T, a.iters, a.warmup)
+        elif a.validate:
             child_report(P, T, a.iters, a.warmup, "validate")
         elif a.report:
             child_report(P, T, a.iters, a.warmup)
         else:
             child(P, T, a.iters, a.warmup, a.host_pairs)
         return
-    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else (REPORT_CONFIGS if a.report or a.validate else CONFIGS)
+    configs = [tuple(map(int, c.split(","))) for c in a.configs.split(";")] if a.configs else (REPORT_CONFIGS if a.report or a.validate or a.pool else CONFIGS)
     for P, T in configs:
-        if a.profile:
+        if a.profile and a.pool:
+            for mode in ("all", "groups"):
+                profile_one(P, T, a.iters, a.profile, pool=mode)
+        elif a.profile:
             profile_one(P, T, a.iters, a.profile, a.report, a.validate)
+        elif a.pool:
+            subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(max(a.iters, 9)),
+                            "--warmup", str(a.warmup), "--pool"], check=True)
         elif a.report or a.validate:
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", f"{P},{T}", "--iters", str(max(a.iters, 9)),
                             "--warmup", str(a.warmup), "--validate" if a.validate else "--report"], check=True)
