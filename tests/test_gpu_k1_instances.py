@@ -18,14 +18,47 @@ without launching.  For every row:
   * an apply job: the older tile's matched rows bit-exact to oracle_np.apply_poly_planes (clip / no clip, mask / no mask),
     pad columns passed through, rows past apply_npix untouched;
   * a batch: each tile's rows and moments equal the references of that tile alone;
-  * a second launch gives identical bits.
-The last test checks that the rows reach every instance the table query (hsr_srf_kernel_instance) reports.
+  * a second launch gives identical bits; between the launches the ticket counter goes back to the row's ticket base and the
+    ready words to their initial values.
+The last two tests check that the rows reach every instance the table query (hsr_srf_kernel_instance) reports, and that every
+job-carrying instance (variants 5, 6, 18, 19 at degrees 1..4) has run each job form below.
+
+Job forms of an apply launch (csrc/hsr_fused_dev.h: lazy_fit, apply_prephase).  'plain' is what the fused pipeline sends: an
+ungated K3 pre-phase, a tail that reduces and solves one tile.  The exchange and group pipelines (csrc/hsr_exec.hip: job_fit,
+job_apply) send three more, and every form keeps the checks above (launch record, planes, moments, apply, second launch):
+  * every tail, whatever its form: the tile's moments carry the bits of hsr_moments_reduce over the previous launch's partials and
+    pass the float64 comparison above; the ticket counter ends at base + workgroups (mod 2^32); sync_error_dev stays 0;
+  * exchange (fit_ready_dev): *fit_ready_dev grows by exactly nb from a non-zero start (one row: from 0xFFFFFFFF - 3, across the
+    wrap); fit_coeffs_dev keeps its sentinel in every element (no solve);
+  * gated pre-phase (coeffs_ready_dev), with the exchange tail and without any tail: the matched rows carry the bits of
+    oracle_np.apply_poly_planes as in the plain form; the word is unchanged.  Pairs (word, value): equal, word three past the value,
+    and value 0xFFFFFFFF with word 1 (a word that has wrapped past its target).  Every row's wait is satisfied BEFORE the launch is
+    enqueued (asserted on the host): a word behind its value would spin for HSR_SYNC_TIMEOUT_S.  The time-out branch of
+    wait_word_at_least is deliberately not exercised;
+  * group_mid (fit_group_index < T - 1): fit_moments_dev is entry `index` of [T][nb][M]; the other T - 1 entries,
+    fit_group_total_dev and fit_coeffs_dev keep their sentinels;
+  * group_last (index T - 1), T in {2, 3, 31, 32, 33, 63, 64} - both halves of the group sum (l < T, l + 32 < T) and their edges.  The
+    other T - 1 entries are float64 moment sets of small random pixel sets; the last tile's own entry is poisoned in memory before
+    every launch (the kernel takes it from LDS, then overwrites it); two rows point fit_moments_dev away from the array - the host
+    does not check it - so the array's last entry stays poisoned and a sum that read it back from memory would show.  fit_group_total_dev and fit_coeffs_dev carry the bits of
+    hsr_moments_reduce_solve over the T entries as T slots.  The total against math.fsum of the entries:
+    |got - exact| <= 16 * 2^-53 * fsum(|entries|) per element, counts exact - every entry passes through at most seven correctly
+    rounded adds (one pair add, the butterfly levels), which bounds the error by 8 * 2^-53 * sum|e|; derived, not measured.  The
+    coefficients against oracle_np.fit_per_band_poly over the UNION of the group's pixels at the bar of the plain tail (1e-7, 1e-6 at
+    degree 4, relative to the band's largest coefficient).  Band 1 has no valid pixel in any entry (identity fallback); one row
+    gives it pixels in the other entries only (fitted, not the identity); one row puts min_count between the last tile's count
+    and the group's;
+  * ticket base: a plain, an exchange and a group_last row run with base and counter 0xFFFFFFF8 on more than 8 workgroups - the
+    counter wraps inside the launch - and carry the bits of the same launch at base 0;
+  * refusals (HSR_ERR_INVALID with the message of hsr_srf.hip, nothing launched): fit_group_tiles 65, fit_group_index T, NULL
+    fit_group_total_dev, a group together with fit_ready_dev.
 
 Support layouts: 'std' = bands of 17..32 taps (32 LDS taps each after rounding to 16-tap chunks), the first starting at
 sample 0 and the last ending at sample B - 1, with a zero response and a bad (good_mask False) sample inside; 'w64' / 'w65' =
 16 bands of 64 / 65 taps (1024 LDS taps fit kWeightCap, 16 x 80 do not); B < 16: the 16-tap chunks do not fit the row.
 """
 import ctypes as C
+import math
 import zlib
 from dataclasses import dataclass
 
@@ -98,6 +131,18 @@ class Case:
     job_x: bool = True      # apply launch carries a K3 job
     apply_npix: int = 61
     minv: float = 0.0
+    # the job forms of the exchange and group pipelines (apply rows; every form but "plain" carries a tail)
+    form: str = "plain"     # plain | exchange | group_mid | group_last
+    group_T: int = 0        # fit_group_tiles
+    group_index: int = -1   # group_mid: fit_group_index (group_last: group_T - 1)
+    tbase: int = 0          # fit_ticket_base and the counter's value before the launch
+    ready: tuple = None     # gated pre-phase: (*coeffs_ready_dev, coeffs_ready_value); the word must have reached the value
+    ready0: int = 7         # exchange: *fit_ready_dev before the launch
+    band1: str = "none"     # group_last: band 1 has no valid pixel in any entry (none) / only in the last tile's (others)
+    min_count: int = MIN_COUNT
+    detached: bool = False  # group_last: fit_moments_dev points away from the group's array (the host does not check it)
+    bad: str = ""           # refusals: T65 | index | total | ready
+    err: int = 2            # what a refusal returns (HSR_ERR_UNSUPPORTED; the job checks: HSR_ERR_INVALID = 1)
 
     @property
     def id(self):
@@ -106,7 +151,12 @@ class Case:
             s += "-unal"
         s += "" if self.entry == "batch" or self.out == "pix" else f"-{self.out}"
         for flag, tag in ((self.taps != "std", self.taps), (self.rc, f"rc{self.rc}"), (self.single, "single"),
-                          (self.fastu, "fastu"), (self.tail, "tail"), (self.entry == "apply" and not self.job_x, "nojob")):
+                          (self.fastu, "fastu"), (self.tail, "tail"), (self.entry == "apply" and not self.job_x, "nojob"),
+                          (self.form != "plain", self.form), (self.group_T, f"T{self.group_T}"),
+                          (self.group_index >= 0, f"i{self.group_index}"), (self.tbase, f"tb{self.tbase:x}"),
+                          (self.ready is not None, "gate{:x}_{:x}".format(*(self.ready or (0, 0)))), (self.ready0 != 7, f"r{self.ready0:x}"),
+                          (self.band1 != "none", f"b1{self.band1}"), (self.min_count != MIN_COUNT, f"mc{self.min_count}"),
+                          (self.detached, "detached"), (self.bad, f"bad{self.bad}")):
             if flag:
                 s += f"-{tag}"
         return s
@@ -239,11 +289,61 @@ def _cases():
         add(18, "apply", "u16", 63, 13, 1 + (i + 3) % 4, n, rc=rc, tail=True, clip=i % 2 == 1, mask=i % 3 == 1, apply_npix=999)
         add(8, "batch", "f32", 63, 13, i % 5, n + (37,), rc=rc)
         add(20, "batch", "u16", 63, 13, (i + 2) % 5, (100,) + n, rc=rc)
+    # -- the job forms of the exchange and group pipelines: every job-carrying instance at every degree, ragged tiles of
+    #    >= nb and > 8 workgroups; nb 1 / 13 / 16 (rows of 4 and 16 floats), clip and the apply mask on and off
+    inst = ((5, "f32", False, False), (6, "f32", True, False), (18, "u16", True, False), (19, "u16", True, True))
+    shape = {1: 64 * 9 + 27, 13: 64 * 14 + 27, 16: 64 * 16 + 27}
+    mids = ((2, 0), (64, 62), (33, 0), (3, 1), (32, 30), (63, 31), (31, 15))
+    i = nx = nm = nl = 0
+    for d in range(1, 5):
+        for vi, (v, dt, al, fu) in enumerate(inst):
+            for form in ("exchange", "group_mid", "group_last"):
+                nb = (13, 16, 1)[(i + d) % 3]
+                k = dict(aligned=(al,), fastu=fu, tail=True, clip=i % 2 == 0, mask=(i // 2) % 2 == 0, apply_npix=(61, 333, 700)[i % 3],
+                         minv=0.0625 if d % 2 == 0 else 0.0, form=form)
+                if form == "exchange":              # every other row with a gated pre-phase, the three pairs in turn
+                    gated = (d + vi) % 2 == 0
+                    add(v, "apply", dt, 285, nb, d, (shape[nb],), ready=GATES[nx % 3] if gated else None, **k)
+                    nx += gated
+                elif form == "group_mid":
+                    add(v, "apply", dt, 285, nb, d, (shape[nb],), group_T=mids[nm % 7][0], group_index=mids[nm % 7][1], **k)
+                    nm += 1
+                else:
+                    add(v, "apply", dt, 285, nb, d, (shape[nb],), group_T=GROUP_T[nl % 7], **k)
+                    nl += 1
+                i += 1
+    # the gated pre-phase without any tail (fit_partials_dev NULL): small tiles, every pair on every instance
+    for i, (v, dt, al, fu) in enumerate(inst):
+        for g, gate in enumerate(GATES):
+            add(v, "apply", dt, 285, (1, 13, 16)[(i + g) % 3], 1 + (i + g) % 4, ((37, 63, 50, 5)[i],), aligned=(al,), fastu=fu,
+                clip=g % 2 == 0, mask=i % 2 == 0, ready=gate)
+    # a ready word that wraps inside the launch; ticket bases eight below the wrap (15 workgroups draw tickets)
+    add(6, "apply", "f32", 285, 13, 2, (923,), tail=True, form="exchange", ready0=0xFFFFFFFF - 3, ready=GATES[2])
+    add(5, "apply", "f32", 284, 13, 1, (923,), tail=True, clip=False, apply_npix=700, tbase=0xFFFFFFF8)
+    add(19, "apply", "u16", 285, 13, 3, (923,), fastu=True, tail=True, form="group_last", group_T=32, tbase=0xFFFFFFF8)
+    add(18, "apply", "u16", 285, 13, 4, (923,), tail=True, form="exchange", tbase=0xFFFFFFF8)
+    # band 1 valid in the other entries only: fitted, not the identity; min_count between the last tile's count and the group's
+    add(6, "apply", "f32", 285, 13, 2, (923,), tail=True, form="group_last", group_T=33, band1="others")
+    add(18, "apply", "u16", 285, 13, 3, (923,), tail=True, form="group_last", group_T=64, min_count=923 + 50)
+    # the last entry of the sum is what the launch has just reduced, not what memory holds: fit_moments_dev elsewhere, entry T - 1 stays poisoned
+    add(5, "apply", "f32", 285, 13, 3, (923,), aligned=(False,), tail=True, form="group_last", group_T=33, detached=True)
+    add(19, "apply", "u16", 285, 16, 2, (1051,), fastu=True, tail=True, form="group_last", group_T=32, detached=True, minv=0.0625)
+    # group jobs the entry refuses (HSR_ERR_INVALID)
+    k = dict(tail=True, err=1)
+    add(None, "apply", "f32", 285, 13, 1, (923,), form="group_last", group_T=65, bad="T65", **k)
+    add(None, "apply", "f32", 285, 13, 2, (923,), form="group_mid", group_T=4, group_index=4, bad="index", **k)
+    add(None, "apply", "u16", 285, 13, 3, (923,), form="group_last", group_T=4, bad="total", **k)
+    add(None, "apply", "u16", 285, 13, 4, (923,), form="group_mid", group_T=4, group_index=1, bad="ready", **k)
     return cs
 
 
+GROUP_T = (2, 3, 31, 32, 33, 63, 64)                      # either side of the two halves of the group sum (l < T, l + 32 < T)
+GATES = ((5, 5), (9, 6), (1, 0xFFFFFFFF))                 # (word, value): equal, three past, wrapped past its target
+APPLY_VARIANTS = (5, 6, 18, 19)                           # the instances that carry a job
+POISON = 1.0e30                                           # the last tile's own entry in memory before a group_last launch
 CASES = _cases()
 SEEN = set()
+FORMS_SEEN = set()                                        # (degree, variant, form) of every tail row that passed
 
 
 @pytest.fixture(scope="module")
@@ -382,21 +482,71 @@ def _check_moments(got, x, y, mask, minv, deg, what):
     np.testing.assert_allclose(got, want, rtol=1e-12, atol=0, err_msg=what)
 
 
-def _check_coeffs(got, x, y, mask, minv, deg, what):
-    want, counts = onp.fit_per_band_poly(x, y, mask, deg, minv, MIN_COUNT)
+def _check_coeffs(got, x, y, mask, minv, deg, what, min_count=MIN_COUNT, band1_empty=True):
+    want, counts = onp.fit_per_band_poly(x, y, mask, deg, minv, min_count)
     tol = 1e-6 if deg == 4 else 1e-7
     for b in range(want.shape[0]):
         err = float(np.max(np.abs(got[b] - want[b])))
         assert err <= tol * max(1.0, float(np.max(np.abs(want[b])))), f"{what}: band {b} ({counts[b]} pixels) coefficients off by {err:.3g}"
-    if x.shape[0] >= 2:
+    if x.shape[0] >= 2 and band1_empty:
         assert counts[1] == 0 and np.array_equal(got[1], want[1])        # under-populated band: identity fallback
+    return counts
+
+
+def _u32(torch, v):
+    """A device word holding the unsigned value v."""
+    return torch.from_numpy(np.array([v], np.uint32).view(np.int32)).cuda()
+
+
+def _set_u32(t, v):
+    t.fill_(v - (1 << 32) if v >= (1 << 31) else v)
+
+
+def _get_u32(t):
+    return int(t.cpu().numpy().view(np.uint32)[0])
+
+
+def _synthetic_entries(case, n, rng):
+    """The other n tiles of a group as float64 moment sets of small random pixel sets with the targets' relation to x (the sums of
+    _moments_ref, so that the union with the real tile determines one polynomial): (x (nb, N), y (nb, N), entries (n, nb, M))."""
+    nb, deg = case.nb, case.deg
+    xs, ys, ent = [], [], np.zeros((n, nb, 3 * deg + 2))
+    for j in range(n):
+        k = int(rng.integers(12, 24))
+        x = rng.uniform(0.1, 0.9, (nb, k)).astype(np.float32)
+        y = (0.9 * x.astype(np.float64) ** 0.9 + 0.02 + 0.01 * rng.standard_normal((nb, k))).astype(np.float32)
+        if nb >= 2 and case.band1 == "none":
+            y[1] = -1.0
+        ok = _valid(x, y, np.ones(k, bool), case.minv)
+        ent[j] = _moments_ref(x.astype(np.float64), y.astype(np.float64), ok, deg)
+        xs.append(x)
+        ys.append(y)
+    return np.concatenate(xs, axis=1), np.concatenate(ys, axis=1), ent
+
+
+def _check_group_sum(got, entries, what):
+    """got (nb, M) against the exact sum of the T entries (T, nb, M).  Every entry reaches the result through at most seven adds
+    (one pair add of entries l and l + 32, then the butterfly levels), each correctly rounded, so the result is within
+    ((1 + u)^7 - 1) sum|e| < 8 u sum|e| of the exact sum, u = 2^-53; the bound asserted is 16 u sum|e|.  It follows from the tree,
+    it is not measured.  Counts are integers far below 2^53: exact."""
+    T, nb, M = entries.shape
+    worst = 0.0
+    for b in range(nb):
+        for m in range(M):
+            col = [float(v) for v in entries[:, b, m]]
+            exact, mag = math.fsum(col), math.fsum(abs(v) for v in col)
+            bound = 16.0 * 2.0 ** -53 * mag
+            worst = max(worst, abs(got[b, m] - exact) / bound) if bound > 0 else worst
+            assert abs(got[b, m] - exact) <= bound, f"{what}: band {b} moment {m}: {got[b, m]!r} vs {exact!r} (sum|e| {mag!r})"
+    print(f"{what}: T = {T}, largest |got - exact| / bound = {worst:.3g}")
+    assert np.array_equal(got[:, 0], entries[:, :, 0].sum(axis=0)), f"{what}: counts"
 
 
 def _same_bits(a, b, what):
     import torch
     a, b = a.contiguous(), b.contiguous()
     iv = torch.int64 if a.dtype == torch.float64 else torch.int32
-    assert torch.equal(a.view(iv), b.view(iv)), f"{what}: a second launch changed bits"
+    assert torch.equal(a.view(iv), b.view(iv)), f"{what}: bits differ"
 
 
 # ---- one case ------------------------------------------------------------------------------------------------------------
@@ -407,7 +557,11 @@ def _launch_checked(case, call):
     rc = call()
     rec = _record()
     if case.expect is None:
-        assert rc == 2 and rec is None, (rc, rec, nat.load().hsr_last_error())
+        assert rc == case.err and rec is None, (rc, rec, nat.load().hsr_last_error())
+        if case.bad:                                            # the message of hsr_srf.hip, with the job's own numbers
+            T, idx = case.group_T, case.group_T - 1 if case.form == "group_last" else case.group_index
+            text = f"group fit of {T} tiles (at most 64), index {idx}, or NULL group buffers, or combined with fit_ready_dev"
+            assert text.encode() in nat.load().hsr_last_error(), nat.load().hsr_last_error()
         return None
     assert rc == 0, nat.load().hsr_last_error()
     assert rec is not None, "the call launched no K1 kernel"
@@ -462,7 +616,7 @@ def _run_single(torch, case, rng):
     fit = ws_fit.fused_fit(MIN_COUNT) if ws_fit is not None else None
 
     # apply job: the older tile (its rows, coefficients, mask) and the previous tile's partials for the tail fit
-    job = None
+    job = ready_w = gate_w = sync_w = garr = gtotal = None
     if case.entry == "apply":
         an = case.apply_npix
         xa = (rng.random((an, row)) * 1.7 - 0.3).astype(np.float32)
@@ -491,12 +645,55 @@ def _run_single(torch, case, rng):
             if case.expect is not None:
                 assert rc == 0, lib.hsr_last_error()
             prev.slots = slots.value
-            tail_mom = torch.zeros((nb, 3 * deg + 2), dtype=torch.float64, device="cuda")
-            tail_co = torch.zeros((nb, deg + 1), dtype=torch.float64, device="cuda")
-            counter = torch.zeros(1, dtype=torch.int32, device="cuda")
+            # what the tail must not write holds the sentinel (the plain rows keep their zeros: the tail writes all of both)
+            M, T = 3 * deg + 2, case.group_T
+            f64 = dict(dtype=torch.float64, device="cuda")
+            fill = 0.0 if case.form == "plain" else SENTINEL
+            if T:                                               # fit_moments_dev is entry gidx of [T][nb][M], as job_fit (hsr_exec.hip) sets it
+                gidx = T - 1 if case.form == "group_last" else case.group_index
+                garr = torch.full((max(T, gidx + 1), nb, M), SENTINEL, **f64)
+                gtotal = torch.full((nb, M), SENTINEL, **f64)
+                tail_mom = torch.full((nb, M), SENTINEL, **f64) if case.detached else garr[gidx]
+                if case.form == "group_last":
+                    syn_x, syn_y, syn_ent = _synthetic_entries(case, T - 1, rng)
+                    garr[:T - 1] = torch.from_numpy(syn_ent).cuda()
+            else:
+                tail_mom = torch.full((nb, M), fill, **f64)
+            tail_co = torch.full((nb, deg + 1), fill, **f64)
+            counter = _u32(torch, case.tbase)
             job.fit_slots, job.fit_partials_dev = prev.slots, prev.partials.data_ptr()
             job.fit_moments_dev, job.fit_coeffs_dev = tail_mom.data_ptr(), tail_co.data_ptr()
-            job.fit_min_count, job.fit_counter_dev, job.fit_ticket_base = MIN_COUNT, counter.data_ptr(), 0
+            job.fit_min_count, job.fit_counter_dev, job.fit_ticket_base = case.min_count, counter.data_ptr(), case.tbase
+            if case.form == "exchange" or case.bad == "ready":
+                ready_w = _u32(torch, case.ready0)
+                job.fit_ready_dev = ready_w.data_ptr()
+            if T:
+                job.fit_group_tiles, job.fit_group_index = T, gidx
+                job.fit_group_moments_dev = garr.data_ptr()
+                job.fit_group_total_dev = None if case.bad == "total" else gtotal.data_ptr()
+        if case.form != "plain" or case.ready is not None:
+            sync_w = _u32(torch, 0)
+            job.sync_error_dev = sync_w.data_ptr()
+        if case.ready is not None:
+            # the wait must be satisfied before the launch is enqueued: a word behind its value would spin for the time limit
+            assert case.job_x and ((case.ready[0] - case.ready[1]) & 0xFFFFFFFF) < 0x80000000, case.ready
+            gate_w = _u32(torch, case.ready[0])
+            job.coeffs_ready_dev, job.coeffs_ready_value = gate_w.data_ptr(), case.ready[1]
+
+    def restore(tbase):
+        """The words and entries a launch changes, back to what they held before the first launch."""
+        if case.tail:
+            _set_u32(counter, tbase)
+            job.fit_ticket_base = tbase
+        if ready_w is not None:
+            _set_u32(ready_w, case.ready0)
+        if gate_w is not None:
+            _set_u32(gate_w, case.ready[0])
+        if case.form == "group_last":
+            garr[case.group_T - 1] = POISON                     # the kernel takes this entry from what it has just reduced
+
+    def tail_state():
+        return (tail_mom.clone(), tail_co.clone()) + ((garr.clone(), gtotal.clone()) if case.group_T else ())
 
     def call():
         head = (P(cube), npix, B, sc, NODATA) if u16 else (P(cube), npix, B)
@@ -513,11 +710,19 @@ def _run_single(torch, case, rng):
 
     runs = []
     for rep in range(2):
-        if case.tail and rep == 1:
-            counter.zero_()
+        restore(case.tbase)
         if _launch_checked(case, call) is None:
             return
         torch.cuda.synchronize()
+        if case.tail:                                           # one ticket per workgroup: what the pipeline advances its base by
+            assert slots.value > 8 or not case.tbase, "the counter must wrap inside the launch"
+            assert _get_u32(counter) == (case.tbase + slots.value) & 0xFFFFFFFF, "ticket counter"
+        if ready_w is not None:
+            assert _get_u32(ready_w) == (case.ready0 + nb) & 0xFFFFFFFF, "*fit_ready_dev must grow by nb"
+        if gate_w is not None:
+            assert _get_u32(gate_w) == case.ready[0], "*coeffs_ready_dev written"
+        if sync_w is not None:
+            assert _get_u32(sync_w) == 0, "sync_error_dev"
         snap = {"out": ostore.clone()}
         if deg > 0:
             ws.slots = slots.value
@@ -529,8 +734,14 @@ def _run_single(torch, case, rng):
         if job is not None and case.job_x:
             snap["apply"] = aout.clone()
         if case.tail:
-            snap["tail"] = (tail_mom.clone(), tail_co.clone())
+            snap["tail"] = tail_state()
         runs.append(snap)
+    if case.tbase:                                              # the same launch at base 0: the same bits
+        restore(0)
+        assert call() == 0, lib.hsr_last_error()
+        torch.cuda.synchronize()
+        for a, b in zip(runs[0]["tail"], tail_state()):
+            _same_bits(a, b, f"ticket base {case.tbase:#x} against base 0")
     for key in runs[0]:
         for a, b in zip(*(r[key] if isinstance(r[key], tuple) else (r[key],) for r in runs)):
             _same_bits(a, b, key)
@@ -559,11 +770,49 @@ def _run_single(torch, case, rng):
         _same_bits(r["fit"][1], want[1], "fused fit coefficients vs hsr_moments_reduce_solve")
         _check_coeffs(r["fit"][1].cpu().numpy(), x, y, mask_np, case.minv, deg, "fused fit")
     if case.tail:
-        want = eng.reduce_solve_slots(prev.partials, prev.slots, prev, MIN_COUNT, torch.empty_like(tail_mom), torch.empty_like(tail_co))
-        _same_bits(r["tail"][0], want[0], "tail fit moments vs hsr_moments_reduce_solve")
-        _same_bits(r["tail"][1], want[1], "tail fit coefficients vs hsr_moments_reduce_solve")
-        _check_moments(r["tail"][0].cpu().numpy(), x, y, mask_np, case.minv, deg, "tail fit moments")
-        _check_coeffs(r["tail"][1].cpu().numpy(), x, y, mask_np, case.minv, deg, "tail fit")
+        tm, tc = r["tail"][0], r["tail"][1]
+        tc_np = tc.cpu().numpy()
+        # every form writes the tile's own moments: the bits of hsr_moments_reduce, and the float64 sums
+        _same_bits(tm, eng.reduce_slots(prev.partials, prev.slots, nb, deg), f"{case.form}: tile moments vs hsr_moments_reduce")
+        _check_moments(tm.cpu().numpy(), x, y, mask_np, case.minv, deg, f"{case.form}: tile moments")
+        if case.form == "plain":
+            want = eng.reduce_solve_slots(prev.partials, prev.slots, prev, MIN_COUNT, torch.empty_like(tail_mom), torch.empty_like(tail_co))
+            _same_bits(tm, want[0], "tail fit moments vs hsr_moments_reduce_solve")
+            _same_bits(tc, want[1], "tail fit coefficients vs hsr_moments_reduce_solve")
+            _check_coeffs(tc_np, x, y, mask_np, case.minv, deg, "tail fit")
+        else:
+            ga, gt = (r["tail"][2].cpu().numpy(), r["tail"][3].cpu().numpy()) if case.group_T else (None, None)
+            if case.form != "group_last":                        # no solve in this launch
+                assert np.all(tc_np == SENTINEL), f"{case.form}: fit_coeffs_dev written"
+            if case.form == "group_mid":
+                others = np.arange(case.group_T) != case.group_index
+                assert np.all(ga[others] == SENTINEL) and np.all(gt == SENTINEL), "group_mid: another entry or the group's total written"
+            if case.form == "group_last":
+                T = case.group_T
+                assert np.array_equal(ga[:T - 1].view(np.int64), syn_ent.view(np.int64)), "group_last: another tile's entry written"
+                if case.detached:
+                    assert np.all(ga[T - 1] == POISON), "group_last: the array's last entry written though fit_moments_dev points elsewhere"
+                ent = torch.cat([torch.from_numpy(syn_ent).cuda(), tm[None]])        # the T entries, the true last one in place
+                want = eng.reduce_solve_slots(ent, T, prev, case.min_count, torch.empty_like(gtotal), torch.empty_like(tail_co))
+                _same_bits(r["tail"][3], want[0], "group total vs hsr_moments_reduce_solve over the T entries")
+                _same_bits(tc, want[1], "group coefficients vs hsr_moments_reduce_solve over the T entries")
+                _check_group_sum(gt, ent.cpu().numpy(), "group total")
+                # the polynomial of the union of the group's pixels: the tile's valid ones and the synthetic sets
+                ux, uy = np.concatenate([x, syn_x], axis=1), np.concatenate([y, syn_y], axis=1)
+                um = np.concatenate([mask_np, np.ones(syn_x.shape[1], bool)])
+                counts = _check_coeffs(tc_np, ux, uy, um, case.minv, deg, "group fit", case.min_count, case.band1 == "none")
+                own = _valid(x, y, mask_np, case.minv).sum(axis=1)
+                fitted = [b for b in range(nb) if b != 1]
+                if case.band1 == "others":                       # no pixel of its own, fitted from the other entries
+                    ident = np.zeros(deg + 1)
+                    ident[-2] = 1.0
+                    assert own[1] == 0 and counts[1] >= case.min_count and not np.array_equal(tc_np[1], ident), (own[1], counts[1], tc_np[1])
+                if case.min_count != MIN_COUNT:                  # the group's count decides, not the last tile's
+                    assert all(own[b] < case.min_count <= counts[b] for b in fitted), (own, counts)
+                    ident = np.zeros(deg + 1)
+                    ident[-2] = 1.0
+                    assert all(not np.array_equal(tc_np[b], ident) for b in fitted)
+        FORMS_SEEN.add((deg, case.expect, case.form))
     if "apply" in r:
         ao = r["apply"].cpu().numpy()
         want = onp.apply_poly_planes(xa[:, :nb].T, co, amask if case.mask else None, clip=case.clip)
@@ -660,3 +909,17 @@ def test_k1_case_table_reaches_every_instance(torch_gpu):
     missing = sorted(table - SEEN)
     assert not missing, "instances no row launched: " + "; ".join(TEMPLATES[v].format(d=d) for d, v in missing)
     assert SEEN <= table
+
+
+def test_k1_case_table_runs_every_job_form_on_every_apply_instance(torch_gpu):
+    """Every job-carrying instance the table query reports has been launched - and has passed its row - in each of the forms
+    the exchange and group pipelines use, besides the plain one."""
+    from s2_emit import _native as nat
+    lib = nat.load()
+    carriers = {(d, v) for d in range(nat.HSR_MAX_DEG + 1) for v in APPLY_VARIANTS if lib.hsr_srf_kernel_instance(d, v) == 1}
+    assert len(carriers) == 16
+    missing = sorted((d, v, f) for d, v in carriers for f in ("plain", "exchange", "group_mid", "group_last") if (d, v, f) not in FORMS_SEEN)
+    assert not missing, "job forms no row launched: " + "; ".join(f"{TEMPLATES[v].format(d=d)} {f}" for d, v, f in missing)
+    for v in APPLY_VARIANTS:                                   # the gated pre-phase with the exchange tail and without any tail
+        for tail in (True, False):
+            assert any(c.expect == v and c.ready is not None and c.tail == tail for c in CASES), (v, tail)
