@@ -132,6 +132,20 @@ __device__ __forceinline__ bool finite_f32(float v) {
   return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u;
 }
 
+// One sample of the uint16 tile format, the reference writer's rule (tiles_helpers/utils.py:362-374; the statements are spelled
+// out in hsr_tile.hip): used by hsr_tile_encode_u16 and by the encoding gather of hsr_scene.hip, which must give the same bits.
+__device__ __forceinline__ uint16_t encode_sample(float x, float scale, bool has_src_nodata, float src_nodata,
+                                                  int32_t nodata_u16) {
+  const bool valid = finite_f32(x) && !(has_src_nodata && x == src_nodata);
+  if (!valid) return (uint16_t)nodata_u16;
+  const float r = rintf(x * scale);   // -ffp-contract=off: the product is rounded to float32 first
+  int32_t q;
+  if (!(r >= -2147483648.0f && r < 2147483648.0f)) q = INT32_MIN;   // x86 "integer indefinite"
+  else q = (int32_t)r;
+  q = q < 0 ? 0 : (q > nodata_u16 - 1 ? nodata_u16 - 1 : q);
+  return (uint16_t)q;
+}
+
 // float32(clip((v - lo) / (hi - lo + 1e-12), 0, 1)) in float64, as s2_emit/color.py:33 evaluates it
 // (np.percentile returns float64 limits, so the whole expression is float64 before the store).
 __device__ __forceinline__ float stretch_f64(float v, double lo, double hi) {

@@ -15,18 +15,7 @@
 
 namespace hsr {
 
-__device__ __forceinline__ uint16_t encode_sample(float x, float scale, bool has_src_nodata, float src_nodata,
-                                                  int32_t nodata_u16) {
-  const bool valid = finite_f32(x) && !(has_src_nodata && x == src_nodata);
-  if (!valid) return (uint16_t)nodata_u16;
-  const float r = rintf(x * scale);   // -ffp-contract=off: the product is rounded to float32 first
-  int32_t q;
-  if (!(r >= -2147483648.0f && r < 2147483648.0f)) q = INT32_MIN;   // x86 "integer indefinite"
-  else q = (int32_t)r;
-  q = q < 0 ? 0 : (q > nodata_u16 - 1 ? nodata_u16 - 1 : q);
-  return (uint16_t)q;
-}
-
+// encode_sample: hsr_common.h (shared with the scene gather of hsr_scene.hip)
 __global__ __launch_bounds__(256) void tile_encode_kernel(const float* __restrict__ x, int64_t n, float scale,
                                                           int has_src_nodata, float src_nodata, int32_t nodata_u16,
                                                           uint16_t* __restrict__ out, bool vec) {

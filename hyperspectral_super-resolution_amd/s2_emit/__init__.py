@@ -17,6 +17,8 @@ from .poly_regression import fit_ot_poly_rgb, apply_poly_rgb
 from .fusion import SpectralFusion, fuse_pair, match_pair, calibrate_pseudo_to_real_linear
 from .ridge import PolyRidge, predict_cube_logit, flatten_pixels, subsample_bands_evenly
 from .pairs import TilePairOutput, TilePairValidation, fuse_tile_pair, fuse_tile_pairs
+from .scenes import (Window, SceneOutput, scene_windows, select_tiles, find_valid_paired_tiles, extract_tile_pairs,
+                     mosaic_tiles, fuse_scene)
 from ._native import HsrUnavailable, HsrError
 
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
@@ -30,5 +32,7 @@ _REFERENCE_SURFACE = (
 _COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb"]
 _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real_linear",
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
-          "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation"]
+          "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
+          "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
+          "Window", "SceneOutput"]
 __all__ = _REFERENCE_SURFACE + _COPIED_BY_CALLERS + _FUSED

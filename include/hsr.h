@@ -790,6 +790,41 @@ int hsr_pipeline_create_group(hsr_step_plan* const* slots, int32_t nslots, int32
  * *sync_error_out = 0, or 1 (the gate of a tile's moments) / 2 (the coefficients of a K3 pre-phase) ran into the 20 s limit, + 16 = host_sum failed. */
 int hsr_pipeline_status(hsr_pipeline* pipeline, hsr_stream_t main_stream, uint32_t* sync_error_out);
 
+/* ---- scene pairs: black-window scan, tile gather, mosaic (s2_emit.scenes; csrc/hsr_scene.hip) ------------------------------------
+ * The front and the back of the tile-pair flow on whole co-registered scenes: the reference finds its tile pairs by walking a
+ * regular grid of windows over an EMIT scene and an S2 scene (tiles_helpers/utils.py:223-305, find_valid_paired_tiles), keeps the
+ * windows whose share of black pixels (is_black_mask, :201-220) is small on both sides and cuts them out (save_tile_pair,
+ * :308-440).  A scene is band-sequential (bands, H, W); dtype codes as hsr_pair_prep: 0 float32, 2 uint16.  Everything runs on the
+ * caller's stream; the entries add no launch record and change no entry point, so HSR_ABI_VERSION stays.
+ * hsr_scene_black_counts: counts (H / tile_h, W / tile_w) int32 (floor; zeroed by the call) = the black pixels of every window of
+ *   the regular grid; the pixels right of and below the last window belong to no window and are not read.  A pixel is black if
+ *   (use_nodata and ALL bands are close to nodata) or ALL bands are close to masked_val or ALL bands have |v| < zero_atol: three
+ *   separate conjunctions.  close(x, v) is np.isclose(x, v, atol=nodata_atol) with v a Python float as NumPy 2 evaluates it:
+ *   float32 scenes wholly in float32 - fabsf(x - (float)v) <= (float)(nodata_atol + 1e-5 * fabs(v)), the sum in double and rounded
+ *   once, and fabsf(x) < (float)zero_atol; uint16 scenes in double (integer arrays promote to float64).  NaN and +-inf are never
+ *   close and never zero; x == v is close also for an infinite v, as in NumPy.  A wave ends its band loop when none of its lanes
+ *   has a live predicate (a valid pixel is decided by its first band); black lanes are counted per wave and window (ballot,
+ *   popcount), a wave walks up to 64 rows and adds a window's count with one integer atomic when it leaves the window, so the
+ *   result does not depend on the order.
+ * hsr_scene_gather_tiles: out (ntiles, bands, th, tw) = the windows at origins_dev (ntiles, 2) int32 (row, col) - arbitrary,
+ *   duplicates allowed; a window that leaves the scene is skipped, never dereferenced.  encode == 0: the scene's dtype and bits.
+ *   encode != 0 (float32 scenes only): uint16 by save_tile_pair's rule (:362-374), the bits of hsr_tile_encode_u16 with the same
+ *   scale, has_src_nodata, src_nodata, nodata_u16.  16-byte (uint16: 8-byte) stores when tw % 4 == 0 and out_dev is aligned,
+ *   vector loads where a row segment's address allows them; the same bits either way.
+ * hsr_scene_mosaic: cubes (ncubes, T, th, tw) float32 -> out (T, H, W) in one pass over the output.  slot (ny, nx) int32, with
+ *   ny th <= H and nx tw <= W, says what window (wy, wx) = rows [wy th, (wy + 1) th) x columns [wx tw, (wx + 1) tw) gets:
+ *   s >= 0 the cube s (s >= ncubes: left untouched), -1 `fill`, -2 left untouched.  The strips right of and below the windows get
+ *   `fill` when fill_rest != 0 and are left untouched otherwise.  16-byte moves when W % 4 == 0, tw % 4 == 0 and both bases are
+ *   aligned. */
+int hsr_scene_black_counts(const void* scene_dev, int32_t dtype, int32_t bands, int32_t H, int32_t W, int32_t tile_h, int32_t tile_w,
+                           int32_t use_nodata, double nodata, double masked_val, double nodata_atol, double zero_atol,
+                           int32_t* counts_dev, hsr_stream_t stream);
+int hsr_scene_gather_tiles(const void* scene_dev, int32_t dtype, int32_t bands, int32_t H, int32_t W, const int32_t* origins_dev,
+                           int32_t ntiles, int32_t th, int32_t tw, int32_t encode, float scale, int32_t has_src_nodata,
+                           float src_nodata, int32_t nodata_u16, void* out_dev, hsr_stream_t stream);
+int hsr_scene_mosaic(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, float* out_dev, int32_t H, int32_t W,
+                     const int32_t* slot_dev, int32_t ny, int32_t nx, float fill, int32_t fill_rest, hsr_stream_t stream);
+
 /* ---- diagnostics -------------------------------------------------------------------------------
  * Pure streaming read of `bytes` bytes (a multiple of 16, 16-byte aligned base): the measured HBM read ceiling of
  * the box, reported by bench.py beside the vendor peak.  mode 0: K1's own load shape - non-temporal LDS-DMA
