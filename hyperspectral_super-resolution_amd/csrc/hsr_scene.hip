@@ -7,6 +7,8 @@
 //   gather        the windows of a scene -> the (P, bands, th, tw) stack that fuse_tile_pairs takes, optionally quantised by
 //                 save_tile_pair's rule (:362-374, encode_sample of hsr_common.h: the bits of hsr_tile_encode_u16).
 //   mosaic        (P, T, th, tw) tile cubes -> the (T, H, W) scene grid in one pass over the output: every byte is written once.
+//   blend         the same for windows that overlap on a lattice: a pixel is the tent-weighted mean of the cubes over it, still
+//                 one pass over the output (nothing in the reference: its tiles never go back onto the scene grid).
 // A scene is band-sequential (bands, H, W); dtype codes as hsr_pair_prep: 0 float32, 2 uint16.
 #include "hsr_common.h"
 
@@ -227,6 +229,110 @@ __global__ __launch_bounds__(256) void scene_mosaic_kernel(const SceneMosaicArgs
   }
 }
 
+// ---- feathered mosaic -------------------------------------------------------------------------------------------------------
+constexpr int kBlendMax = 16;          // contributors of one output pixel, at most
+
+struct SceneBlendArgs {
+  const float* cubes;                  // (P, T, th, tw)
+  float* out;                          // (T, H, W)
+  const int32_t* start;                // (ny, nx): the cube whose window starts at lattice cell (j, i), -1 none
+  int64_t plane, tile_plane;
+  int32_t P, T, H, W, th, tw, sy, sx, K, nx;
+  int32_t ly, lx;                      // rows and columns of `start` whose cells lie in the table AND whose window stays in (H, W)
+  float fill;
+  uint8_t dj[kBlendMax], di[kBlendMax];   // contributor k starts dj[k] cells above and di[k] cells left of the pixel's cell:
+};                                        // ascending start row, then ascending start column
+
+// The tent weight of local position p of a window of n samples: min(p + 1, n - p), an integer.
+__device__ __forceinline__ float tent(int p, int n) { return (float)min(p + 1, n - p); }
+
+// grid (ceil(W / E / 256), rows, T), as scene_mosaic_kernel: a thread keeps its column(s) and walks rows; the lattice row, the
+// local rows and wy are the same for the whole workgroup, the lattice column, the local columns and wx are fixed per thread.
+// kVec (W, tw and sx multiples of 4, aligned bases): four columns per thread - they share one lattice cell, hence one
+// contributor set - moved as 16-byte loads and stores.  KMAX >= K is the unrolled contributor count.  Every one of the KMAX
+// table reads and then every one of the KMAX cube loads is issued, unconditionally, before the arithmetic, so a row's loads are
+// in flight together and none sits behind a branch: a slot without a contributor reads entry 0 of the table, which it ignores,
+// and the first samples of the stack, which it masks out.
+template <bool kVec, int KMAX>
+__global__ __launch_bounds__(256) void scene_blend_kernel(const SceneBlendArgs a) {
+  constexpr int E = kVec ? 4 : 1;
+  const int x = (blockIdx.x * 256 + threadIdx.x) * E;
+  if (x >= a.W) return;
+  const int64_t t = blockIdx.z;
+  const int cx = (int)((uint32_t)x / (uint32_t)a.sx);
+  float* out = a.out + t * a.plane + x;
+  const float* cubes_t = a.cubes + t * a.tile_plane;
+  const int64_t cube_pitch = (int64_t)a.T * a.tile_plane;
+  for (int y = blockIdx.y; y < a.H; y += gridDim.y) {
+    const int cy = y / a.sy;
+    bool on[KMAX];
+    int ent[KMAX], row[KMAX], col[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      const int sj = cy - a.dj[k], si = cx - a.di[k];                  // the start cell
+      on[k] = k < a.K && (uint32_t)sj < (uint32_t)a.ly && (uint32_t)si < (uint32_t)a.lx;
+      ent[k] = a.start[on[k] ? sj * a.nx + si : 0];
+      row[k] = y - sj * a.sy;
+      col[k] = x - si * a.sx;
+    }
+    const float* src[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      on[k] = on[k] && ent[k] >= 0 && ent[k] < a.P;
+      src[k] = on[k] ? cubes_t + ent[k] * cube_pitch + ((int64_t)row[k] * a.tw + col[k]) : a.cubes;
+    }
+    float v[KMAX][E];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      if constexpr (kVec) {
+        const float4 q = *reinterpret_cast<const float4*>(src[k]);
+        v[k][0] = q.x, v[k][1] = q.y, v[k][2] = q.z, v[k][3] = q.w;
+      } else {
+        v[k][0] = src[k][0];
+      }
+    }
+    // `one` is what an element with n <= 1 gets: `fill` while no cube covers it; then, while nothing is taken, the value of the
+    // contributor visited last (a NaN, with its bits); then the first value taken.
+    float num[E], den[E], one[E];
+    int n[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) num[e] = 0.0f, den[e] = 0.0f, one[e] = a.fill, n[e] = 0;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) {
+      const float wy = tent(row[k], a.th);
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const float val = v[k][e], w = wy * tent(col[k] + e, a.tw);   // integers whose product is below 2^24: exact
+        const bool take = on[k] && val == val;
+        one[e] = (take || (on[k] && n[e] == 0)) ? val : one[e];
+        num[e] = take ? fmaf(w, val, num[e]) : num[e];
+        den[e] = take ? den[e] + w : den[e];
+        n[e] += take ? 1 : 0;
+      }
+    }
+    float* d = out + (int64_t)y * a.W;
+    if constexpr (kVec) {
+      float4 q;
+      q.x = n[0] <= 1 ? one[0] : __fdiv_rn(num[0], den[0]);
+      q.y = n[1] <= 1 ? one[1] : __fdiv_rn(num[1], den[1]);
+      q.z = n[2] <= 1 ? one[2] : __fdiv_rn(num[2], den[2]);
+      q.w = n[3] <= 1 ? one[3] : __fdiv_rn(num[3], den[3]);
+      *reinterpret_cast<float4*>(d) = q;
+    } else {
+      d[0] = n[0] <= 1 ? one[0] : __fdiv_rn(num[0], den[0]);
+    }
+  }
+}
+
+template <bool kVec>
+static void launch_blend(const SceneBlendArgs& a, dim3 grid, hipStream_t s) {
+  if (a.K <= 1) hipLaunchKernelGGL((scene_blend_kernel<kVec, 1>), grid, dim3(256), 0, s, a);
+  else if (a.K <= 2) hipLaunchKernelGGL((scene_blend_kernel<kVec, 2>), grid, dim3(256), 0, s, a);
+  else if (a.K <= 4) hipLaunchKernelGGL((scene_blend_kernel<kVec, 4>), grid, dim3(256), 0, s, a);
+  else if (a.K <= 8) hipLaunchKernelGGL((scene_blend_kernel<kVec, 8>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((scene_blend_kernel<kVec, kBlendMax>), grid, dim3(256), 0, s, a);
+}
+
 // atol + 1e-5 |v| in double, as Python adds it; -1 (never reached by |x - v|) for a non-finite v
 static double close_tol(double v, double atol) { return isfinite(v) ? atol + 1e-5 * fabs(v) : -1.0; }
 
@@ -304,5 +410,42 @@ extern "C" int hsr_scene_mosaic(const float* cubes_dev, int32_t ncubes, int32_t 
   else
     hipLaunchKernelGGL(scene_mosaic_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
   HSR_LAUNCH_CHECK("scene_mosaic_kernel");
+  return HSR_OK;
+}
+
+extern "C" int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, int32_t sy, int32_t sx,
+                                      const int32_t* start_dev, int32_t ny, int32_t nx, float* out_dev, int32_t H, int32_t W,
+                                      float fill, hsr_stream_t stream) {
+  HSR_REQUIRE(cubes_dev && start_dev && out_dev, HSR_ERR_INVALID, "hsr_scene_mosaic_blend: NULL pointer");
+  HSR_REQUIRE(ncubes >= 1 && T >= 1 && th >= 1 && tw >= 1 && sy >= 1 && sx >= 1 && ny >= 1 && nx >= 1 && H >= 1 && W >= 1,
+              HSR_ERR_INVALID, "hsr_scene_mosaic_blend: bad shape (P=%d T=%d H=%d W=%d tile=%d x %d pitch=%d x %d cells=%d x %d)",
+              ncubes, T, H, W, th, tw, sy, sx, ny, nx);
+  HSR_REQUIRE(th % sy == 0 && tw % sx == 0, HSR_ERR_INVALID,
+              "hsr_scene_mosaic_blend: the lattice pitch %d x %d does not divide the tile %d x %d", sy, sx, th, tw);
+  const int64_t ky = th / sy, kx = tw / sx, K = ky * kx;
+  HSR_REQUIRE(K <= kBlendMax, HSR_ERR_UNSUPPORTED, "hsr_scene_mosaic_blend: %lld x %lld = %lld windows over a pixel, at most %d",
+              (long long)ky, (long long)kx, (long long)K, kBlendMax);
+  const int64_t wsum = K * ((th + 1) / 2) * (int64_t)((tw + 1) / 2);   // what the weights of one pixel can add up to
+  HSR_REQUIRE(wsum <= (1 << 24), HSR_ERR_UNSUPPORTED,
+              "hsr_scene_mosaic_blend: weight sum %lld = %lld x ceil(%d / 2) x ceil(%d / 2) above 2^24 is no exact float32 integer",
+              (long long)wsum, (long long)K, th, tw);
+  HSR_REQUIRE(T <= 65535, HSR_ERR_UNSUPPORTED, "hsr_scene_mosaic_blend: T=%d above 65535", T);
+  HSR_REQUIRE((int64_t)ny * nx <= 0x7fffffff, HSR_ERR_UNSUPPORTED, "hsr_scene_mosaic_blend: %d x %d lattice cells", ny, nx);
+  // the start cells whose window stays inside the output: rows 0 .. (H - th) / sy, none when the tile is larger than the output
+  const int64_t fy = H >= th ? (int64_t)(H - th) / sy + 1 : 0, fx = W >= tw ? (int64_t)(W - tw) / sx + 1 : 0;
+  SceneBlendArgs a{cubes_dev, out_dev, start_dev, (int64_t)H * W, (int64_t)th * tw, ncubes, T, H, W, th, tw, sy, sx, (int32_t)K, nx,
+                   (int32_t)(fy < ny ? fy : ny), (int32_t)(fx < nx ? fx : nx), fill, {}, {}};
+  for (int k = 0; k < (int)K; ++k) {                  // ascending start row, then ascending start column
+    a.dj[k] = (uint8_t)(ky - 1 - k / kx);
+    a.di[k] = (uint8_t)(kx - 1 - k % kx);
+  }
+  const bool vec = W % 4 == 0 && tw % 4 == 0 && sx % 4 == 0 && ((uintptr_t)out_dev & 15) == 0 && ((uintptr_t)cubes_dev & 15) == 0;
+  const int64_t gx = ((vec ? W / 4 : W) + 255) / 256;
+  int64_t gy = 65536 / (gx * T);                     // about 64 Ki workgroups: the rows are strided over them
+  gy = gy < 1 ? 1 : (gy > H ? H : gy);
+  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)T);
+  if (vec) launch_blend<true>(a, grid, (hipStream_t)stream);
+  else launch_blend<false>(a, grid, (hipStream_t)stream);
+  HSR_LAUNCH_CHECK("scene_blend_kernel");
   return HSR_OK;
 }

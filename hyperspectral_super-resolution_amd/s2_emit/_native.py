@@ -183,6 +183,7 @@ SIGNATURES = {
     "hsr_scene_black_counts": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp]),
     "hsr_scene_gather_tiles": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _vp]),
     "hsr_scene_mosaic": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _i32, _vp]),
+    "hsr_scene_mosaic_blend": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp]),
     "hsr_block_mean": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample_mask_hist": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),

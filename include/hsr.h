@@ -815,7 +815,23 @@ int hsr_pipeline_status(hsr_pipeline* pipeline, hsr_stream_t main_stream, uint32
  *   ny th <= H and nx tw <= W, says what window (wy, wx) = rows [wy th, (wy + 1) th) x columns [wx tw, (wx + 1) tw) gets:
  *   s >= 0 the cube s (s >= ncubes: left untouched), -1 `fill`, -2 left untouched.  The strips right of and below the windows get
  *   `fill` when fill_rest != 0 and are left untouched otherwise.  16-byte moves when W % 4 == 0, tw % 4 == 0 and both bases are
- *   aligned. */
+ *   aligned.
+ * hsr_scene_mosaic_blend: the mosaic of windows that overlap, cross-faded: cubes (ncubes, T, th, tw) float32 -> out (T, H, W) in
+ *   one pass over the output, every byte written exactly once, no atomics, no scratch.  The windows start on a lattice of pitch
+ *   (sy, sx) with th % sy == 0 and tw % sx == 0; start (ny, nx) int32 names the cube whose window starts at lattice cell (j, i),
+ *   i.e. covers rows [j sy, j sy + th) x columns [i sx, i sx + tw), or -1.  With ky = th / sy, kx = tw / sx, K = ky kx: output pixel
+ *   (y, x) lies in cell (cy, cx) = (y / sy, x / sx) and its contributors are the cubes that start at the cells (cy - j, cx - i),
+ *   0 <= j < ky, 0 <= i < kx, visited in ascending start row, then ascending start column - whatever the order of the stack.  An
+ *   entry is no contributor, and is never used as an index, when it is < 0 or >= ncubes, when its cell lies outside the table or
+ *   when its window would leave the H x W output.  A cube's weight at its local position (r, c) is wy(r) wx(c) with
+ *   wy(r) = min(r + 1, th - r) and wx(c) = min(c + 1, tw - c), integers.  Per element (t, y, x), from num = 0, den = 0, n = 0: each
+ *   contributor value v that is not NaN gives num = fmaf(w, v, num), den += w, n += 1.  The result is `fill` where no cube covers
+ *   the pixel; NaN where cubes cover it but n == 0 (the bits of the contributor visited last); the bits of the one value where
+ *   n == 1 (copied, not w v / w); num / den in IEEE float32 division otherwise.  +-inf is not special-cased.
+ *   Refused before any launch: NULL pointers, non-positive sizes, a pitch that does not divide the tile (HSR_ERR_INVALID); K > 16,
+ *   K ceil(th / 2) ceil(tw / 2) > 2^24 (den must stay an exact float32 integer), T > 65535, ny nx > 0x7fffffff
+ *   (HSR_ERR_UNSUPPORTED).  16-byte moves when W, tw and sx are multiples of 4 and both bases are aligned; K is unrolled to the
+ *   next of 1, 2, 4, 8, 16 and all of a pixel's loads are issued before the arithmetic. */
 int hsr_scene_black_counts(const void* scene_dev, int32_t dtype, int32_t bands, int32_t H, int32_t W, int32_t tile_h, int32_t tile_w,
                            int32_t use_nodata, double nodata, double masked_val, double nodata_atol, double zero_atol,
                            int32_t* counts_dev, hsr_stream_t stream);
@@ -824,6 +840,9 @@ int hsr_scene_gather_tiles(const void* scene_dev, int32_t dtype, int32_t bands, 
                            float src_nodata, int32_t nodata_u16, void* out_dev, hsr_stream_t stream);
 int hsr_scene_mosaic(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, float* out_dev, int32_t H, int32_t W,
                      const int32_t* slot_dev, int32_t ny, int32_t nx, float fill, int32_t fill_rest, hsr_stream_t stream);
+int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, int32_t sy, int32_t sx,
+                           const int32_t* start_dev, int32_t ny, int32_t nx, float* out_dev, int32_t H, int32_t W, float fill,
+                           hsr_stream_t stream);
 
 /* ---- diagnostics -------------------------------------------------------------------------------
  * Pure streaming read of `bytes` bytes (a multiple of 16, 16-byte aligned base): the measured HBM read ceiling of

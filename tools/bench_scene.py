@@ -12,8 +12,12 @@ Scenes (synthetic, built on the device from a seed): EMIT 285 x 1242 x 1280 floa
   gather_emit / _encode      hsr_scene_gather_tiles of all 144 EMIT windows, as float32 and quantised to uint16;
   gather_s2                  the 144 S2 windows;
   mosaic_T32 / mosaic_T8     hsr_scene_mosaic of 144 cubes of T x 600 x 600 into T x 7452 x 7680;
+  blend_T32_half_stride      hsr_scene_mosaic_blend of the half-stride window set - 23 x 24 cubes of 32 x 600 x 600 (25.4 GB), four
+                             over every inner pixel - into 32 x 7452 x 7680; bytes: the output once plus every contributor read;
+                             blend_vs_mosaic is its rate over mosaic_T32's in the same process;
   fuse_scene                 find -> gather -> fuse_tile_pairs -> mosaic end to end (wall clock around a synchronise: it holds the
-                             one host synchronisation), 32 bands, batches of 64.
+                             one host synchronisation), 32 bands, batches of 64;
+  fuse_scene_stride50        the same with stride=50: windows at half stride, their cubes kept in one stack and blended at the end.
 Per step: us, the median over SAMPLES samples of REPS back-to-back launches between two device events, after warm-up, with the
 fastest and slowest sample; bytes, what the step has to move (scan: one band of every covered pixel that is not black and
 every band of every black one; gather and mosaic: read + written); tbps = bytes / us; floor_us = bytes at 8 TB/s; numpy_ms, the
@@ -218,6 +222,20 @@ def main():
         record(f"mosaic_T{T}", us3, 4 * (cubes.numel() + out.numel()), ms, tiles=nys * nxs)
         del cubes, out
 
+    # ---- the feathered mosaic: the half-stride window set, 23 x 24 windows of 600 x 600 (four over an inner pixel) -----------------
+    half = ts // 2
+    nyb, nxb = (Hs - ts) // half + 1, (Ws - ts) // half + 1
+    start = torch.arange(nyb * nxb, dtype=torch.int32, device=dev).reshape(nyb, nxb)
+    cubes = torch.rand((nyb * nxb, 32, ts, ts), generator=g, device=dev)
+    out = torch.empty((32, Hs, Ws), dtype=torch.float32, device=dev)
+    us3 = timed(torch, lambda: scenes._blend_into(lib, torch, st, cubes, out, start, half, half, ts, ts, float("nan")))
+    record("blend_T32_half_stride", us3, 4 * (cubes.numel() + out.numel()), None, tiles=nyb * nxb)
+    mosaic = next(r for r in rows if r["step"] == "mosaic_T32")
+    blend_verdict = dict(step="blend_vs_mosaic", blend_tbps=rows[-1]["tbps"], mosaic_tbps=mosaic["tbps"],
+                         ratio=round(rows[-1]["tbps"] / mosaic["tbps"], 3))
+    print(json.dumps(blend_verdict), flush=True)
+    del cubes, out
+
     # ---- end to end -----------------------------------------------------------------------------------------------------------
     s2u = s2.view(torch.uint16)
     kw = dict(tile=TILE, factor=SCALE, batch=64, bands=32, emit_nodata=NODATA, s2_nodata=0.0)
@@ -237,6 +255,24 @@ def main():
                ms_per_tile=round(ms[1] / max(nt, 1), 3), scene_step_bytes=int(moved), floor_us=round(moved / PEAK_TBPS / 1e6, 1),
                status_ok=int((res.status == 0).sum().item()))
     print(json.dumps(rec), flush=True)
+    # the same with windows at half stride, cross-faded: every kept window's cube stays in one stack until the one blend launch
+    kw["stride"] = TILE // 2
+    res = s2_emit.fuse_scene(emit, s2u, **kw)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(3):
+        del res
+        t = time.perf_counter()
+        res = s2_emit.fuse_scene(emit, s2u, **kw)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t) * 1e3)
+    ms.sort()
+    nb = len(res.tiles)
+    rec_b = dict(step="fuse_scene_stride50", ms=round(ms[1], 2), ms_min=round(ms[0], 2), ms_max=round(ms[2], 2), tiles=nb,
+                 ms_per_tile=round(ms[1] / max(nb, 1), 3), stack_bytes=scenes._blend_stack_bytes(nb, 32, ts, ts),
+                 status_ok=int((res.status == 0).sum().item()))
+    print(json.dumps(rec_b), flush=True)
+    del res
     verdict = dict(step="early_exit", scan_emit_0_us=round(t0, 1), scan_emit_100_us=round(t100, 1), ratio=round(t100 / t0, 1),
                    works=bool(t0 * 4 < t100))
     print(json.dumps(verdict), flush=True)
@@ -249,7 +285,8 @@ def main():
                 ratio = "" if r["numpy_ms"] is None else f"{r['numpy_ms'] * 1e3 / r['us']:.0f} x"
                 fh.write(f"| {r['step']} | {r['us']} | {r['us_min']} .. {r['us_max']} | {r['bytes'] / 1e6:.1f} MB | {r['tbps']} | "
                          f"{r['floor_us']} | {r['us'] / max(r['floor_us'], 1e-9):.1f} | {npy} | {ratio} |\n")
-            fh.write(f"\nfuse_scene: {json.dumps(rec)}\n\nearly exit: {json.dumps(verdict)}\n")
+            fh.write(f"\nfuse_scene: {json.dumps(rec)}\n\nfuse_scene, stride 50: {json.dumps(rec_b)}\n\n"
+                     f"blend against mosaic: {json.dumps(blend_verdict)}\n\nearly exit: {json.dumps(verdict)}\n")
 
 
 if __name__ == "__main__":
