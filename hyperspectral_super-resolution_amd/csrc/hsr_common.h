@@ -50,6 +50,18 @@ enum AuxInstance : int {
 // HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_aux_last_launch).
 int aux_launched(const char* what, int instance);
 
+// Kernel instances of hsr_scene.hip, the index of the name table behind hsr_scene_last_launch / hsr_scene_instance_name
+// (csrc/hsr_lib.hip): a table of its own, so the auxiliary one keeps its 32 names.  base + template-argument offset, as above.
+enum SceneInstance : int {
+  kSceneBlack = 0,                         // + 0 <float>, 1 <uint16_t>
+  kSceneGather = kSceneBlack + 2,          // + 2 * (0 <float, float, false>, 1 <uint16_t, uint16_t, false>, 2 <float, uint16_t, true>) + kVec
+  kSceneMosaic = kSceneGather + 6,         // + kVec
+  kSceneBlend = kSceneMosaic + 2,          // + 5 * kVec + log2(KMAX): KMAX 1, 2, 4, 8, 16
+  kSceneInstances = kSceneBlend + 10
+};
+// HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_scene_last_launch).
+int scene_launched(const char* what, int instance);
+
 // Kernel instances of hsr_ridge.hip, hsr_gram.hip and hsr_chol.hip (K4), the index of the name table behind hsr_k4_last_launch /
 // hsr_k4_instance_name (csrc/hsr_lib.hip).  A family's instances are consecutive: base + offset.
 enum K4Instance : int {

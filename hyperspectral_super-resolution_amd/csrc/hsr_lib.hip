@@ -107,6 +107,26 @@ int aux_launched(const char* what, int instance) {
   return rc;
 }
 
+// The same for the kernels of hsr_scene.hip (hsr_scene_last_launch): every entry point there launches one kernel, so one slot.
+static const char* const kSceneNames[kSceneInstances] = {
+    "scene_black_kernel<float>", "scene_black_kernel<uint16_t>",
+    "scene_gather_kernel<float, float, false, false>", "scene_gather_kernel<float, float, false, true>",
+    "scene_gather_kernel<uint16_t, uint16_t, false, false>", "scene_gather_kernel<uint16_t, uint16_t, false, true>",
+    "scene_gather_kernel<float, uint16_t, true, false>", "scene_gather_kernel<float, uint16_t, true, true>",
+    "scene_mosaic_kernel<false>", "scene_mosaic_kernel<true>",
+    "scene_blend_kernel<false, 1>", "scene_blend_kernel<false, 2>", "scene_blend_kernel<false, 4>", "scene_blend_kernel<false, 8>",
+    "scene_blend_kernel<false, 16>",
+    "scene_blend_kernel<true, 1>", "scene_blend_kernel<true, 2>", "scene_blend_kernel<true, 4>", "scene_blend_kernel<true, 8>",
+    "scene_blend_kernel<true, 16>",
+};
+static thread_local int g_scene_last = -1;
+
+int scene_launched(const char* what, int instance) {
+  const int rc = check_hip(hipGetLastError(), what);
+  if (rc == HSR_OK) g_scene_last = instance;
+  return rc;
+}
+
 // The kernels of hsr_ridge.hip / hsr_gram.hip / hsr_chol.hip this thread launched successfully since the last read
 // (hsr_k4_last_launch): indices of this table (K4Instance, hsr_common.h) in launch order, the oldest dropped when the list is full.
 static const char* const kK4Names[kK4Instances] = {
@@ -189,6 +209,26 @@ extern "C" const char* hsr_aux_instance_name(int32_t i) {
     return nullptr;
   }
   return hsr::kAuxNames[i];
+}
+
+extern "C" int hsr_scene_last_launch(char* name, int32_t capacity) {
+  const int r = hsr::g_scene_last;
+  hsr::g_scene_last = -1;
+  if (!name || capacity < 1) return r >= 0 ? 1 : 0;
+  name[0] = 0;
+  if (r < 0) return 0;
+  snprintf(name, (size_t)capacity, "%s", hsr::kSceneNames[r]);
+  return 1;
+}
+
+extern "C" int hsr_scene_instance_count(void) { return hsr::kSceneInstances; }
+
+extern "C" const char* hsr_scene_instance_name(int32_t i) {
+  if (i < 0 || i >= hsr::kSceneInstances) {
+    hsr::set_error("hsr_scene_instance_name: i=%d outside [0,%d)", i, (int)hsr::kSceneInstances);
+    return nullptr;
+  }
+  return hsr::kSceneNames[i];
 }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }

@@ -112,8 +112,7 @@ template <typename T>
 static int launch_scan(const SceneScanArgs<T>& a, hipStream_t s) {
   const int wc = a.nx * a.tile_w, hc = a.ny * a.tile_h;
   hipLaunchKernelGGL(scene_black_kernel<T>, dim3((unsigned)((wc + 255) / 256), (unsigned)((hc + a.rows - 1) / a.rows)), dim3(256), 0, s, a);
-  HSR_LAUNCH_CHECK("scene_black_kernel");
-  return HSR_OK;
+  return scene_launched("scene_black_kernel launch", kSceneBlack + (sizeof(T) == 2 ? 1 : 0));
 }
 
 // ---- gather ----------------------------------------------------------------------------------------------------------------
@@ -174,6 +173,7 @@ __global__ __launch_bounds__(256) void scene_gather_kernel(const SceneGatherArgs
 
 template <typename TI, typename TO, bool kEncode>
 static int launch_gather(const SceneGatherArgs& a, int ntiles, hipStream_t s) {
+  constexpr int pair = kEncode ? 2 : (sizeof(TI) == 2 ? 1 : 0);
   const int64_t n = (int64_t)a.th * a.tw;
   const bool vec = a.tw % 4 == 0 && ((uintptr_t)a.out & (4 * sizeof(TO) - 1)) == 0;
   const int64_t chunks = ((vec ? n / 4 : n) + 255) / 256;
@@ -182,8 +182,7 @@ static int launch_gather(const SceneGatherArgs& a, int ntiles, hipStream_t s) {
     hipLaunchKernelGGL((scene_gather_kernel<TI, TO, kEncode, true>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((scene_gather_kernel<TI, TO, kEncode, false>), grid, dim3(256), 0, s, a);
-  HSR_LAUNCH_CHECK("scene_gather_kernel");
-  return HSR_OK;
+  return scene_launched("scene_gather_kernel launch", kSceneGather + 2 * pair + (vec ? 1 : 0));
 }
 
 // ---- mosaic ----------------------------------------------------------------------------------------------------------------
@@ -409,8 +408,7 @@ extern "C" int hsr_scene_mosaic(const float* cubes_dev, int32_t ncubes, int32_t 
     hipLaunchKernelGGL(scene_mosaic_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(scene_mosaic_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("scene_mosaic_kernel");
-  return HSR_OK;
+  return scene_launched("scene_mosaic_kernel launch", kSceneMosaic + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, int32_t sy, int32_t sx,
@@ -446,6 +444,6 @@ extern "C" int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, in
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)T);
   if (vec) launch_blend<true>(a, grid, (hipStream_t)stream);
   else launch_blend<false>(a, grid, (hipStream_t)stream);
-  HSR_LAUNCH_CHECK("scene_blend_kernel");
-  return HSR_OK;
+  const int lg = K <= 1 ? 0 : K <= 2 ? 1 : K <= 4 ? 2 : K <= 8 ? 3 : 4;        // launch_blend's KMAX
+  return scene_launched("scene_blend_kernel launch", kSceneBlend + (vec ? 5 : 0) + lg);
 }

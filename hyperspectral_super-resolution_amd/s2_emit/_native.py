@@ -194,6 +194,9 @@ SIGNATURES = {
     "hsr_aux_last_launch": (C.c_int, [C.c_char_p, _i32]),
     "hsr_aux_instance_count": (C.c_int, []),
     "hsr_aux_instance_name": (C.c_char_p, [_i32]),
+    "hsr_scene_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_scene_instance_count": (C.c_int, []),
+    "hsr_scene_instance_name": (C.c_char_p, [_i32]),
     "hsr_polyfeat_predict_kernel": (C.c_int, [_i32, _i32, _i32, _i32]),
     "hsr_k4_last_launch": (C.c_int, [C.c_char_p, _i32]),
     "hsr_k4_instance_count": (C.c_int, []),

@@ -884,6 +884,18 @@ int hsr_poly_last_launch(char* name, int32_t capacity);
 int hsr_aux_last_launch(char* name, int32_t capacity);
 int hsr_aux_instance_count(void);
 const char* hsr_aux_instance_name(int32_t i);
+/* The same for the scene kernels (csrc/hsr_scene.hip), in a table of their own: hsr_aux_instance_count stays 32.  Host only, per
+ * thread, same contract, so HSR_ABI_VERSION stays.  Each of hsr_scene_black_counts, hsr_scene_gather_tiles, hsr_scene_mosaic and
+ * hsr_scene_mosaic_blend launches one kernel; hsr_scene_last_launch returns 1 and writes the name of the calling thread's last
+ * successful such launch - kernel and template arguments as in the source: "scene_black_kernel<uint16_t>",
+ * "scene_gather_kernel<float, uint16_t, true, false>" (<TI, TO, kEncode, kVec>), "scene_mosaic_kernel<true>" (<kVec>),
+ * "scene_blend_kernel<false, 8>" (<kVec, KMAX>) - truncated to `capacity` bytes, then clears the record; 0 (and "") if there
+ * was no such launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same.
+ * hsr_scene_instance_count (20) / hsr_scene_instance_name(i), 0 <= i < count: every name the record can return (NULL and the
+ * error text outside that range). */
+int hsr_scene_last_launch(char* name, int32_t capacity);
+int hsr_scene_instance_count(void);
+const char* hsr_scene_instance_name(int32_t i);
 /* Which predict kernel hsr_polyfeat_predict / _predict_cube / _predict_cube_batched launch for (n_in, degree, T): 0
  * predict103_x16_kernel, 1 .. 3 predict103_slice_kernel<1 .. 3>, 4 .. 6 predict_kernel<1 / 2 / 4>; -1 (and the error text) for a
  * shape no kernel takes.  The MFMA kernels (0 .. 3) need the orbit rows that the first hsr_polyfeat_prepare uploads:

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from scene_cases import assemble as _assemble            # hsr_scene_mosaic in NumPy, shared with the instance tests
 from test_scene_tiles_host import SCALE, TILE, black_rule, g15_mask, g15_settings, window_counts
 
 pytestmark = pytest.mark.gpu
@@ -211,23 +212,6 @@ def test_extract_tile_pairs_against_g15(torch_gpu, g15):
 
 
 # ---- 4. the mosaic -------------------------------------------------------------------------------------------------------------------
-def _assemble(cubes, slot, out, th, tw, fill, fill_rest):
-    """hsr_scene_mosaic in NumPy, on a copy of the prefilled output."""
-    out = out.copy()
-    ny, nx = slot.shape
-    if fill_rest:
-        out[:, ny * th:, :] = fill
-        out[:, :, nx * tw:] = fill
-    for wy in range(ny):
-        for wx in range(nx):
-            s, win = slot[wy, wx], (slice(None), slice(wy * th, (wy + 1) * th), slice(wx * tw, (wx + 1) * tw))
-            if 0 <= s < len(cubes):
-                out[win] = cubes[s]
-            elif s == -1:
-                out[win] = fill
-    return out
-
-
 @pytest.mark.parametrize("W,tw", [(36, 8), (31, 8), (36, 6), (30, 7)])
 def test_mosaic_bits_equal_numpy_assembly(torch_gpu, W, tw):
     """T = 3, H = 23, th = 6: 3 x 4 windows, a 5-row strip below and a strip right of them ((36, 8) is the 16-byte instance, the

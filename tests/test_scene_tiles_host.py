@@ -19,13 +19,14 @@ TILE, SCALE = 8, 3                     # g15's grid
 
 def black_rule(arr, nodata=None, masked_val=-0.01, nodata_atol=1e-3, zero_atol=1e-6):
     """is_black_mask's arithmetic spelled out, as NumPy 2 evaluates np.isclose(arr, v, atol=a) with v a Python float: float32 arrays
-    wholly in float32 (|x - (float)v| <= (float)(a + 1e-5 |v|), |x| < (float)zero_atol), integer arrays in float64."""
+    wholly in float32 (|x - (float)v| <= (float)(a + 1e-5 |v|) & isfinite(v) | x == (float)v, |x| < (float)zero_atol), integer
+    arrays in float64."""
     ft = np.float32 if arr.dtype == np.float32 else np.float64
     x = arr.astype(ft, copy=False)
 
     def close(v):
         with np.errstate(invalid="ignore"):
-            return np.abs(x - ft(v)) <= ft(nodata_atol + 1e-5 * abs(v))
+            return (np.abs(x - ft(v)) <= ft(nodata_atol + 1e-5 * abs(v))) & np.isfinite(v) | (x == ft(v))
 
     out = close(masked_val).all(0) | (np.abs(x) < ft(zero_atol)).all(0)
     return out | close(nodata).all(0) if nodata is not None else out
