@@ -86,6 +86,25 @@ enum K4Instance : int {
 // thread's record on success (hsr_k4_last_launch); second < 0: one launch.
 int k4_launched(const char* what, int first, int second = -1);
 
+// Kernel instances of hsr_pairs.hip, the index of the name table behind hsr_pairs_last_launch / hsr_pairs_instance_name
+// (csrc/hsr_lib.hip): a table of its own, so the K4 one keeps its 31 names (pair_expand_f64_kernel stays there).
+enum PairsInstance : int {
+  kPairsPrep = 0,
+  kPairsStats,
+  kPairsReportPartial,
+  kPairsReportFinish,
+  kPairsHoldout,
+  kPairsScorePartial,                      // + kVec
+  kPairsScoreFinish = kPairsScorePartial + 2,
+  kPairsPoolStats,
+  kPairsPoolGram,                          // + kVec
+  kPairsPoolModels = kPairsPoolGram + 2,
+  kPairsInstances
+};
+// HSR_LAUNCH_CHECK of one launch that also appends its instance to the calling thread's record on success
+// (hsr_pairs_last_launch: a list in launch order like the K4 record, since report and score launch two kernels per call).
+int pairs_launched(const char* what, int instance);
+
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
 // records, and clears the error a refused request leaves: the launch itself then reports it.
 inline void raise_lds_limit(const void* kernel, size_t bytes, size_t& configured) {

@@ -165,7 +165,54 @@ int k4_launched(const char* what, int first, int second) {
   return rc;
 }
 
+// The same for the kernels of hsr_pairs.hip (hsr_pairs_last_launch): hsr_pair_report_f64 and hsr_pair_score_f64 launch two kernels
+// per call, so a list in launch order like the K4 record, with a name table of its own.
+static const char* const kPairsNames[kPairsInstances] = {
+    "pair_prep_kernel", "pair_stats_kernel", "pair_report_partial_kernel", "pair_report_finish_kernel", "pair_holdout_kernel",
+    "pair_score_partial_kernel<false>", "pair_score_partial_kernel<true>", "pair_score_finish_kernel",
+    "pool_stats_kernel", "pool_gram_kernel<false>", "pool_gram_kernel<true>", "pool_models_kernel",
+};
+constexpr int kPairsRecordCap = 32;
+static thread_local int g_pairs_seq[kPairsRecordCap];
+static thread_local int g_pairs_count = 0;
+
+int pairs_launched(const char* what, int instance) {
+  const int rc = check_hip(hipGetLastError(), what);
+  if (rc == HSR_OK) {
+    if (g_pairs_count == kPairsRecordCap) {
+      for (int i = 1; i < kPairsRecordCap; ++i) g_pairs_seq[i - 1] = g_pairs_seq[i];
+      --g_pairs_count;
+    }
+    g_pairs_seq[g_pairs_count++] = instance;
+  }
+  return rc;
+}
+
 }  // namespace hsr
+
+extern "C" int hsr_pairs_last_launch(char* names, int32_t capacity) {
+  const int count = hsr::g_pairs_count;
+  hsr::g_pairs_count = 0;
+  if (!names || capacity < 1) return count > 0 ? 1 : 0;
+  names[0] = 0;
+  size_t used = 0;
+  for (int i = 0; i < count && used + 1 < (size_t)capacity; ++i) {
+    const int w = snprintf(names + used, (size_t)capacity - used, "%s%s", i ? "; " : "", hsr::kPairsNames[hsr::g_pairs_seq[i]]);
+    if (w < 0) break;
+    used += (size_t)w < (size_t)capacity - used ? (size_t)w : (size_t)capacity - used - 1;
+  }
+  return count > 0 ? 1 : 0;
+}
+
+extern "C" int hsr_pairs_instance_count(void) { return hsr::kPairsInstances; }
+
+extern "C" const char* hsr_pairs_instance_name(int32_t i) {
+  if (i < 0 || i >= hsr::kPairsInstances) {
+    hsr::set_error("hsr_pairs_instance_name: i=%d outside [0,%d)", i, (int)hsr::kPairsInstances);
+    return nullptr;
+  }
+  return hsr::kPairsNames[i];
+}
 
 extern "C" int hsr_k4_last_launch(char* names, int32_t capacity) {
   const int count = hsr::g_k4_count;

@@ -808,6 +808,13 @@ __global__ __launch_bounds__(256) void pool_models_kernel(const PoolModelArgs a)
 
 using namespace hsr;
 
+// HSR_LAUNCH_CHECK that also appends the instance to the calling thread's record (hsr_pairs_last_launch) on success
+#define HSR_PAIRS_LAUNCHED(name, instance)                           \
+  do {                                                               \
+    int rc_ = hsr::pairs_launched(name " launch", (instance));       \
+    if (rc_ != HSR_OK) return rc_;                                   \
+  } while (0)
+
 extern "C" int hsr_pair_prep(const void* emit_dev, int32_t emit_dtype, int64_t pair_emit, int32_t emit_bands,
                              const int32_t* bands_dev, int32_t T, const void* s2_dev, int32_t s2_dtype, int64_t pair_s2,
                              int32_t nb, int32_t H, int32_t W, int32_t factor, float emit_nodata, int32_t use_emit_nodata,
@@ -828,7 +835,7 @@ extern "C" int hsr_pair_prep(const void* emit_dev, int32_t emit_dtype, int64_t p
   PairPrepArgs a{emit_dev, s2_dev, bands_dev, x_dev, y_dev, mask_dev, pair_emit, pair_s2, emit_dtype, s2_dtype, nb, T, H, W,
                  factor, use_emit_nodata, use_s2_nodata, emit_nodata, s2_nodata};
   hipLaunchKernelGGL(pair_prep_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)npairs), dim3(256), 0, (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("pair_prep_kernel");
+  HSR_PAIRS_LAUNCHED("pair_prep_kernel", kPairsPrep);
   return HSR_OK;
 }
 
@@ -840,7 +847,7 @@ extern "C" int hsr_pair_stats(const float* x_dev, const uint8_t* mask_dev, int64
               "hsr_pair_stats: bad shape (npix=%lld nb=%d P=%d)", (long long)npix, nb, npairs);
   hipLaunchKernelGGL(pair_stats_kernel, dim3((unsigned)npairs), dim3(kPairStatsThreads), 0, (hipStream_t)stream, x_dev, mask_dev,
                      npix, nb, stats_dev, mean_dev, scale_dev, n_train_dev);
-  HSR_LAUNCH_CHECK("pair_stats_kernel");
+  HSR_PAIRS_LAUNCHED("pair_stats_kernel", kPairsStats);
   return HSR_OK;
 }
 
@@ -872,10 +879,10 @@ extern "C" int hsr_pair_report_f64(const double* q_dev, int64_t ldq, int64_t pai
                    pair_work, npix, na, nf, T};
   hipLaunchKernelGGL(pair_report_partial_kernel, dim3((unsigned)chunks, (unsigned)((T + 31) / 32), (unsigned)npairs), dim3(256), 0,
                      (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("pair_report_partial_kernel");
+  HSR_PAIRS_LAUNCHED("pair_report_partial_kernel", kPairsReportPartial);
   hipLaunchKernelGGL(pair_report_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, (hipStream_t)stream, work_dev,
                      pair_work, (int)chunks, T, status_dev, r2_dev, rmse_dev, pair_out);
-  HSR_LAUNCH_CHECK("pair_report_finish_kernel");
+  HSR_PAIRS_LAUNCHED("pair_report_finish_kernel", kPairsReportFinish);
   return HSR_OK;
 }
 
@@ -887,7 +894,7 @@ extern "C" int hsr_pair_holdout(const uint8_t* valid_dev, const uint8_t* train_d
               npairs);
   hipLaunchKernelGGL(pair_holdout_kernel, dim3((unsigned)((npix + 255) / 256), (unsigned)npairs), dim3(256), 0, (hipStream_t)stream,
                      valid_dev, train_dev, pair_train, npix, mask_dev, group_dev);
-  HSR_LAUNCH_CHECK("pair_holdout_kernel");
+  HSR_PAIRS_LAUNCHED("pair_holdout_kernel", kPairsHoldout);
   return HSR_OK;
 }
 
@@ -925,11 +932,11 @@ extern "C" int hsr_pair_score_f64(const float* pred_dev, int64_t pair_pred, cons
     hipLaunchKernelGGL(pair_score_partial_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(pair_score_partial_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("pair_score_partial_kernel");
+  HSR_PAIRS_LAUNCHED("pair_score_partial_kernel", kPairsScorePartial + (vec ? 1 : 0));
   const PairScoreOut o{n_dev, rmse_dev, r2_dev, mean_ref_dev, sam_dev, n_sam_dev, ergas_dev, pair_out, pair_sam};
   hipLaunchKernelGGL(pair_score_finish_kernel, dim3((unsigned)npairs), dim3(kScoreFinishThreads), 0, (hipStream_t)stream, work_dev, pair_work,
                      (int)chunks, T, ergas_scale, o);
-  HSR_LAUNCH_CHECK("pair_score_finish_kernel");
+  HSR_PAIRS_LAUNCHED("pair_score_finish_kernel", kPairsScoreFinish);
   return HSR_OK;
 }
 
@@ -942,7 +949,7 @@ extern "C" int hsr_pool_stats(const double* stats_dev, int32_t nb, int32_t npair
               "hsr_pool_stats: bad shape (nb=%d P=%d M=%d)", nb, npairs, ngroups);
   hipLaunchKernelGGL(pool_stats_kernel, dim3((unsigned)ngroups), dim3(64), 0, (hipStream_t)stream, stats_dev, nb, npairs, order_dev,
                      start_dev, gstats_dev, n_pool_dev, gmean_dev, gscale_dev, mean_dev, scale_dev);
-  HSR_LAUNCH_CHECK("pool_stats_kernel");
+  HSR_PAIRS_LAUNCHED("pool_stats_kernel", kPairsPoolStats);
   return HSR_OK;
 }
 
@@ -966,7 +973,7 @@ extern "C" int hsr_pool_gram(const double* g_dev, int64_t pair_g, int64_t n_elem
   else
     hipLaunchKernelGGL(pool_gram_kernel<false>, grid, dim3(kPoolGramThreads), 0, (hipStream_t)stream, g_dev, pair_g, n_elems,
                        count_dev, pair_count, npairs, order_dev, start_dev, out_dev, group_out);
-  HSR_LAUNCH_CHECK("pool_gram_kernel");
+  HSR_PAIRS_LAUNCHED("pool_gram_kernel", kPairsPoolGram + (vec ? 1 : 0));
   return HSR_OK;
 }
 
@@ -991,6 +998,6 @@ extern "C" int hsr_pool_models(const double* gbp_dev, int64_t group_bp, const do
   const int64_t blocks = (total + 1023) / 1024;              // 4 elements per thread, at most 64 blocks per pair
   hipLaunchKernelGGL(pool_models_kernel, dim3((unsigned)(blocks < 64 ? blocks : 64), (unsigned)npairs), dim3(256), 0,
                      (hipStream_t)stream, a);
-  HSR_LAUNCH_CHECK("pool_models_kernel");
+  HSR_PAIRS_LAUNCHED("pool_models_kernel", kPairsPoolModels);
   return HSR_OK;
 }

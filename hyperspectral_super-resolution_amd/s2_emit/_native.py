@@ -201,6 +201,9 @@ SIGNATURES = {
     "hsr_k4_last_launch": (C.c_int, [C.c_char_p, _i32]),
     "hsr_k4_instance_count": (C.c_int, []),
     "hsr_k4_instance_name": (C.c_char_p, [_i32]),
+    "hsr_pairs_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_pairs_instance_count": (C.c_int, []),
+    "hsr_pairs_instance_name": (C.c_char_p, [_i32]),
     "hsr_step_plan_create": (C.c_int, [C.POINTER(StepDesc), C.POINTER(_vp)]),
     "hsr_step_plan_destroy": (None, [_vp]),
     "hsr_step_plan_slots": (C.c_int, [_vp]),

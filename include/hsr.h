@@ -926,6 +926,22 @@ int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t
 int hsr_k4_last_launch(char* names, int32_t capacity);
 int hsr_k4_instance_count(void);
 const char* hsr_k4_instance_name(int32_t i);
+/* The same for the tile-pair kernels (csrc/hsr_pairs.hip), in a table of their own: hsr_k4_instance_count stays 31 and
+ * pair_expand_f64_kernel stays in the K4 record.  Host only, per thread, the K4 record's contract (hsr_pair_report_f64 and
+ * hsr_pair_score_f64 launch two kernels per call): every kernel the calling thread launched successfully since the last read
+ * (the 32 most recent), in launch order, joined by "; " - e.g. "pair_score_partial_kernel<true>; pair_score_finish_kernel" -
+ * NUL-terminated and truncated to `capacity` bytes; reading clears the record; 0 (and "") without a launch; names NULL or
+ * capacity < 1: only the return value, the record is cleared all the same.  A call refused by its argument checks adds nothing.
+ * Exports only are added, so HSR_ABI_VERSION stays.  The 12 names: pair_prep_kernel, pair_stats_kernel,
+ * pair_report_partial_kernel, pair_report_finish_kernel, pair_holdout_kernel, pair_score_partial_kernel<false> / <true> (<kVec>:
+ * hsr_pair_score_f64's alignment predicate), pair_score_finish_kernel, pool_stats_kernel, pool_gram_kernel<false> / <true>
+ * (<kVec>: hsr_pool_gram's), pool_models_kernel.  The one- or two-group walk of the score kernel is chosen on the device, per
+ * chunk, and is not part of the name.
+ * hsr_pairs_instance_count (12) / hsr_pairs_instance_name(i), 0 <= i < count: every name the record can hold (NULL and the error
+ * text outside that range). */
+int hsr_pairs_last_launch(char* names, int32_t capacity);
+int hsr_pairs_instance_count(void);
+const char* hsr_pairs_instance_name(int32_t i);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 """fuse_tile_pairs(pool=...) on an MI355X: fixture g14 (the pooled scikit-learn pipeline on g12's pairs), the single-model path
 (PolyRidge on the host-concatenated training pixels), the bit invariants of the pooling kernels' merge rules on a small batch,
 hsr_pool_stats and hsr_pool_gram alone through ctypes, and TilePairOutput.predict."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -334,8 +336,12 @@ def test_pool_gram_kernel_is_exact_on_integers(torch_gpu, n_elems, misalign):
     assert (gd.data_ptr() % 16 == 8) == misalign
     order, start, _, _ = _layout_dev(torch, ids)
     cd = torch.from_numpy(cnt).cuda()
+    lib.hsr_pairs_last_launch(None, 0)
     nat.check(lib.hsr_pool_gram(_ptr(gd), pair_g, n_elems, _ptr(cd), 2, P, _ptr(order), _ptr(start), M, _ptr(od), group_out, None),
               "hsr_pool_gram")
+    record = ctypes.create_string_buffer(64)                 # the instance the sizes and the alignment ask for is the one that ran
+    vec = "true" if n_elems % 2 == 0 and not misalign else "false"
+    assert lib.hsr_pairs_last_launch(record, 64) == 1 and record.value.decode() == f"pool_gram_kernel<{vec}>", record.value
     torch.cuda.synchronize()
     got = od.cpu().numpy().reshape(M, group_out)
     for g in range(M):

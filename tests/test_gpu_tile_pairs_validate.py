@@ -3,6 +3,8 @@ against a NumPy restatement from the device's own outputs (T = 32 and all 285 ba
 what the hold-out does to the fit, defaults that change nothing, batch bits == single-pair bits, a non-default stream and float32
 inputs.  Bounds: only summation order separates the device from the restatement, so they are derived, not measured (see each
 test); the observed maxima are printed (run with -s) and quoted in profiles/r07_tile_pairs_validate.md."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -118,9 +120,14 @@ def _score_alone(torch, pred, y, group, factor, misalign=False):
     n, rmse, r2, mean_ref = i64(P, 2, T), f64(P, 2, T), f64(P, 2, T), f64(P, 2, T)
     sam, n_sam, ergas = f64(P, 2), i64(P, 2), f64(P, 2)
     sam_map = torch.full((P, npix), -7.0, dtype=torch.float32, device="cuda")
+    lib.hsr_pairs_last_launch(None, 0)
     nat.check(lib.hsr_pair_score_f64(_ptr(pd), T * npix, _ptr(yd), T * npix, _ptr(gd), npix, npix, T, 100.0 / factor, _ptr(work), sw,
                                      _ptr(n), _ptr(rmse), _ptr(r2), _ptr(mean_ref), 2 * T, _ptr(sam), _ptr(n_sam), _ptr(ergas), 2,
                                      _ptr(sam_map), npix, P, None), "hsr_pair_score_f64")
+    record = ctypes.create_string_buffer(96)                 # the instance the alignment asks for is the one that ran
+    vec = "true" if npix % 4 == 0 and not misalign else "false"
+    assert lib.hsr_pairs_last_launch(record, 96) == 1
+    assert record.value.decode() == f"pair_score_partial_kernel<{vec}>; pair_score_finish_kernel", record.value
     torch.cuda.synchronize()
     return dict(n=n, rmse=rmse, r2=r2, mean_ref=mean_ref, sam=sam, n_sam=n_sam, ergas=ergas, sam_map=sam_map)
 

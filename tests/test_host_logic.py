@@ -587,6 +587,44 @@ def test_k4_launch_record_host_side():
     assert max(len(a) + 2 + len(b) for a in names for b in names) < 96     # any two names joined fit a 96-byte buffer
 
 
+def test_pairs_launch_record_host_side():
+    """hsr_pairs_last_launch: empty without a launch (reads as 0), nothing added by calls their argument checks refuse, capacity
+    handling; hsr_pairs_instance_name: the 12 names in the table's order, NULL and the error text outside [0, 12)."""
+    lib = nat.load()
+    lib.hsr_pairs_last_launch(None, 0)                           # whatever an earlier test left
+    buf = ctypes.create_string_buffer(64)
+    buf.value = b"junk"
+    assert lib.hsr_pairs_last_launch(buf, 64) == 0 and buf.value == b""
+    buf.value = b"junk"
+    assert lib.hsr_pairs_last_launch(buf, 0) == 0 and buf.value == b"junk"    # capacity < 1: the buffer is not touched
+    assert lib.hsr_pairs_last_launch(buf, -5) == 0 and buf.value == b"junk"
+    assert lib.hsr_pairs_last_launch(buf, 1) == 0 and buf.raw[0] == 0          # room for the terminator alone
+    f = ctypes.c_void_p(16)
+    assert lib.hsr_pair_prep(f, 2, 0, 4, f, 5, f, 2, 0, 1, 2, 2, 2, 0.0, 0, 0.0, 0, f, f, f, 1, None) == 1     # T > emit_bands
+    assert lib.hsr_pair_prep(f, 2, 0, 4, f, 1, f, 2, 0, 17, 2, 2, 2, 0.0, 0, 0.0, 0, f, f, f, 1, None) == 1    # nb = 17
+    assert lib.hsr_pair_prep(f, 2, 0, 4, f, 1, f, 2, 0, 1, 2, 2, 0, 0.0, 0, 0.0, 0, f, f, f, 1, None) == 2     # a uint16 coarse image
+    assert lib.hsr_pair_stats(f, f, 0, 1, f, f, f, f, 1, None) == 1
+    assert lib.hsr_pair_report_f64(f, 16, 0, 24, 10, f, 0, f, 1, 0, 3, f, 0, f, 0, 1, f, f, 4, f, f, 0, 1, None) == 1   # na % 16 != 0
+    assert lib.hsr_pair_holdout(f, None, 10, 10, f, f, 1, None) == 1
+    assert lib.hsr_pair_score_f64(f, 0, f, 0, f, 0, 10, 1, 1.0, f, 1, f, f, f, f, 0, f, f, f, 0, f, 0, 1, None) == 1    # pair_work
+    assert lib.hsr_pool_stats(f, 1, 2, f, f, 3, f, f, f, f, f, f, None) == 1                                            # M > P
+    assert lib.hsr_pool_gram(f, 4, 8, f, 1, 2, f, f, 1, f, 8, None) == 1                                                # pair_g < n_elems
+    assert lib.hsr_pool_models(f, 0, f, f, 0, f, f, f, f, f, f, 4, 3, 4, 1, 1, f, f, f, f, f, f, f, f, 1, 1, None) == 1  # npad < nf
+    assert lib.hsr_pairs_last_launch(buf, 64) == 0 and buf.value == b""
+    assert lib.hsr_pairs_last_launch(None, 0) == 0
+    n = lib.hsr_pairs_instance_count()
+    assert n == 12 and lib.hsr_pairs_instance_count() == n and lib.hsr_k4_instance_count() == 31
+    names = [lib.hsr_pairs_instance_name(i) for i in range(n)]
+    assert names == [lib.hsr_pairs_instance_name(i) for i in range(n)]
+    assert [s.decode() for s in names] == [
+        "pair_prep_kernel", "pair_stats_kernel", "pair_report_partial_kernel", "pair_report_finish_kernel", "pair_holdout_kernel",
+        "pair_score_partial_kernel<false>", "pair_score_partial_kernel<true>", "pair_score_finish_kernel", "pool_stats_kernel",
+        "pool_gram_kernel<false>", "pool_gram_kernel<true>", "pool_models_kernel"]
+    for bad in (-1, n, 1 << 20):
+        assert lib.hsr_pairs_instance_name(bad) is None and b"hsr_pairs_instance_name" in lib.hsr_last_error()
+    assert sum(len(s) + 2 for s in names) < 2048                 # the whole table joined fits the tests' 2048-byte buffer
+
+
 def test_aux_instance_enumeration():
     """hsr_aux_instance_name: every name the record can return - unique, stable, the template spellings of the sources."""
     lib = nat.load()
