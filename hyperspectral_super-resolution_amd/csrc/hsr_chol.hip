@@ -841,7 +841,7 @@ static int chol_launch(double* a_dev, int64_t lda, int32_t n, int64_t pair_a, do
   raise_lds_limit(reinterpret_cast<const void*>(chol_solve_kernel), lds_s, configured_s);
   hipLaunchKernelGGL(chol_solve_kernel, dim3((nrhs + kSw - 1) / kSw, (unsigned)npairs), dim3(1024), lds_s, s, a_dev, lda, n, work_dev,
                      b_dev, ldb, nrhs, dinv_in_lds, pair_a, pair_w, pair_b CHOL_STAMP_ARG);
-  return k4_launched("chol kernels launch", n <= kResMaxN ? kK4CholFactorRes : kK4CholFactor, kK4CholSolve + (dinv_in_lds ? 0 : 1));
+  return launched(kLaunchK4, "chol kernels launch", n <= kResMaxN ? kK4CholFactorRes : kK4CholFactor, kK4CholSolve + (dinv_in_lds ? 0 : 1));
 }
 
 extern "C" int hsr_chol_solve_f64(double* a_dev, int64_t lda, int32_t n, double* b_dev, int64_t ldb, int32_t nrhs,

@@ -47,8 +47,6 @@ enum AuxInstance : int {
   kAuxTranspose = kAuxTileDecode + 2,      // + 0 <float, float>, 1 <uint16_t, uint16_t>, 2 <uint16_t, float>, 3 <int16_t, float>
   kAuxInstances = kAuxTranspose + 4
 };
-// HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_aux_last_launch).
-int aux_launched(const char* what, int instance);
 
 // Kernel instances of hsr_scene.hip, the index of the name table behind hsr_scene_last_launch / hsr_scene_instance_name
 // (csrc/hsr_lib.hip): a table of its own, so the auxiliary one keeps its 32 names.  base + template-argument offset, as above.
@@ -59,8 +57,6 @@ enum SceneInstance : int {
   kSceneBlend = kSceneMosaic + 2,          // + 5 * kVec + log2(KMAX): KMAX 1, 2, 4, 8, 16
   kSceneInstances = kSceneBlend + 10
 };
-// HSR_LAUNCH_CHECK that also records the instance, per thread, on success (the record of hsr_scene_last_launch).
-int scene_launched(const char* what, int instance);
 
 // Kernel instances of hsr_ridge.hip, hsr_gram.hip and hsr_chol.hip (K4), the index of the name table behind hsr_k4_last_launch /
 // hsr_k4_instance_name (csrc/hsr_lib.hip).  A family's instances are consecutive: base + offset.
@@ -82,9 +78,6 @@ enum K4Instance : int {
   kK4CholSolve,                            // + 0 block inverses in LDS, 1 in global memory
   kK4Instances = kK4CholSolve + 2
 };
-// HSR_LAUNCH_CHECK of an entry point's one or two launches that also appends their instances, in launch order, to the calling
-// thread's record on success (hsr_k4_last_launch); second < 0: one launch.
-int k4_launched(const char* what, int first, int second = -1);
 
 // Kernel instances of hsr_pairs.hip, the index of the name table behind hsr_pairs_last_launch / hsr_pairs_instance_name
 // (csrc/hsr_lib.hip): a table of its own, so the K4 one keeps its 31 names (pair_expand_f64_kernel stays there).
@@ -101,9 +94,11 @@ enum PairsInstance : int {
   kPairsPoolModels = kPairsPoolGram + 2,
   kPairsInstances
 };
-// HSR_LAUNCH_CHECK of one launch that also appends its instance to the calling thread's record on success
-// (hsr_pairs_last_launch: a list in launch order like the K4 record, since report and score launch two kernels per call).
-int pairs_launched(const char* what, int instance);
+
+// HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs };
+int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
 // records, and clears the error a refused request leaves: the launch itself then reports it.

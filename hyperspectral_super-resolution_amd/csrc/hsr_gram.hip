@@ -763,7 +763,7 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
   hipStream_t s = (hipStream_t)stream;
   int lds_instance = -1;
   if (launch_gram_lds(a_dev, lda, na, b_dev, ldb, nb, n, sym, work_dev, c_dev, ldc, 0, 0, 0, 1, s, &lds_instance))
-    return k4_launched("gram_f64_lds_kernel launch", lds_instance, kK4GramReduce);
+    return launched(kLaunchK4, "gram_f64_lds_kernel launch", lds_instance, kK4GramReduce);
   int64_t rows = 0;
   const int64_t chunks = gram_reg_chunks(n, &rows);
   constexpr int R = hsr::kGramR;
@@ -771,7 +771,7 @@ extern "C" int hsr_gram_f64(const double* a_dev, int64_t lda, int32_t na, const 
                      a_dev, lda, ti, b_dev, ldb, tj, n, rows, sym, work_dev);
   hipLaunchKernelGGL(gram_reduce_kernel, dim3(ti * tj), dim3(256), 0, s, work_dev, ti * tj, (int)chunks, tj, sym, R, tj,
                      (int)chunks, 0, c_dev, ldc, (int64_t)0, (int64_t)0);
-  return k4_launched("gram_f64_kernel launch", kK4GramReg + (sym ? 0 : 1), kK4GramReduce);
+  return launched(kLaunchK4, "gram_f64_kernel launch", kK4GramReg + (sym ? 0 : 1), kK4GramReduce);
 }
 
 extern "C" int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na, int32_t nb, int64_t n, int64_t pair_a,
@@ -789,5 +789,5 @@ extern "C" int hsr_gram_f64_batched(const double* a_dev, int64_t lda, int32_t na
   HSR_REQUIRE(launch_gram_lds(a_dev, lda, na, a_dev, lda, nb, n, 1, work_dev, c_dev, ldc, pair_a, pair_work, pair_c, npairs,
                               (hipStream_t)stream, &lds_instance),
               HSR_ERR_UNSUPPORTED, "hsr_gram_f64_batched: needs 16-byte aligned rows of an even leading dimension");
-  return k4_launched("gram_f64_lds_kernel (batched) launch", lds_instance, kK4GramReduce);
+  return launched(kLaunchK4, "gram_f64_lds_kernel (batched) launch", lds_instance, kK4GramReduce);
 }

@@ -82,9 +82,10 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// The last successful launch of a kernel of hsr_select.hip / hsr_resample.hip / hsr_tile.hip on this thread (hsr_aux_last_launch):
-// an index of this table (AuxInstance, hsr_common.h), turned into its name only when read.  -1 = none since the last read.
-static const char* const kAuxNames[kAuxInstances] = {
+// Launch records (hsr_{aux,scene,k4,pairs}_last_launch): per family and thread, the kernels launched successfully since the last
+// read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
+// the list is full.  Indices turn into names only when read.
+static const char* const kAuxNames[] = {
     "select_hist_kernel<1, 0>", "select_hist_kernel<1, 1>", "select_hist_kernel<2, 0>", "select_hist_kernel<2, 1>",
     "select_hist_kernel<3, 0>", "select_hist_kernel<3, 1>",
     "select_hist_rows4_kernel<1>", "select_hist_rows4_kernel<2>", "select_hist_rows4_kernel<3>",
@@ -99,16 +100,7 @@ static const char* const kAuxNames[kAuxInstances] = {
     "transpose_rc_kernel<float, float>", "transpose_rc_kernel<uint16_t, uint16_t>", "transpose_rc_kernel<uint16_t, float>",
     "transpose_rc_kernel<int16_t, float>",
 };
-static thread_local int g_aux_last = -1;
-
-int aux_launched(const char* what, int instance) {
-  const int rc = check_hip(hipGetLastError(), what);
-  if (rc == HSR_OK) g_aux_last = instance;
-  return rc;
-}
-
-// The same for the kernels of hsr_scene.hip (hsr_scene_last_launch): every entry point there launches one kernel, so one slot.
-static const char* const kSceneNames[kSceneInstances] = {
+static const char* const kSceneNames[] = {
     "scene_black_kernel<float>", "scene_black_kernel<uint16_t>",
     "scene_gather_kernel<float, float, false, false>", "scene_gather_kernel<float, float, false, true>",
     "scene_gather_kernel<uint16_t, uint16_t, false, false>", "scene_gather_kernel<uint16_t, uint16_t, false, true>",
@@ -119,17 +111,7 @@ static const char* const kSceneNames[kSceneInstances] = {
     "scene_blend_kernel<true, 1>", "scene_blend_kernel<true, 2>", "scene_blend_kernel<true, 4>", "scene_blend_kernel<true, 8>",
     "scene_blend_kernel<true, 16>",
 };
-static thread_local int g_scene_last = -1;
-
-int scene_launched(const char* what, int instance) {
-  const int rc = check_hip(hipGetLastError(), what);
-  if (rc == HSR_OK) g_scene_last = instance;
-  return rc;
-}
-
-// The kernels of hsr_ridge.hip / hsr_gram.hip / hsr_chol.hip this thread launched successfully since the last read
-// (hsr_k4_last_launch): indices of this table (K4Instance, hsr_common.h) in launch order, the oldest dropped when the list is full.
-static const char* const kK4Names[kK4Instances] = {
+static const char* const kK4Names[] = {
     "expand_f64_kernel", "pair_expand_f64_kernel", "ridge_stats_partial_kernel", "ridge_stats_finish_kernel",
     "ridge_assemble_kernel", "ridge_finish_kernel",
     "predict_kernel<1>", "predict_kernel<2>", "predict_kernel<4>",
@@ -144,139 +126,95 @@ static const char* const kK4Names[kK4Instances] = {
     "chol_factor_res_kernel", "chol_factor_kernel",
     "chol_solve_kernel lds", "chol_solve_kernel global",
 };
-constexpr int kK4RecordCap = 32;
-static thread_local int g_k4_seq[kK4RecordCap];
-static thread_local int g_k4_count = 0;
-
-static void k4_append(int instance) {
-  if (g_k4_count == kK4RecordCap) {
-    for (int i = 1; i < kK4RecordCap; ++i) g_k4_seq[i - 1] = g_k4_seq[i];
-    --g_k4_count;
-  }
-  g_k4_seq[g_k4_count++] = instance;
-}
-
-int k4_launched(const char* what, int first, int second) {
-  const int rc = check_hip(hipGetLastError(), what);
-  if (rc == HSR_OK) {
-    k4_append(first);
-    if (second >= 0) k4_append(second);
-  }
-  return rc;
-}
-
-// The same for the kernels of hsr_pairs.hip (hsr_pairs_last_launch): hsr_pair_report_f64 and hsr_pair_score_f64 launch two kernels
-// per call, so a list in launch order like the K4 record, with a name table of its own.
-static const char* const kPairsNames[kPairsInstances] = {
+static const char* const kPairsNames[] = {
     "pair_prep_kernel", "pair_stats_kernel", "pair_report_partial_kernel", "pair_report_finish_kernel", "pair_holdout_kernel",
     "pair_score_partial_kernel<false>", "pair_score_partial_kernel<true>", "pair_score_finish_kernel",
     "pool_stats_kernel", "pool_gram_kernel<false>", "pool_gram_kernel<true>", "pool_models_kernel",
 };
-constexpr int kPairsRecordCap = 32;
-static thread_local int g_pairs_seq[kPairsRecordCap];
-static thread_local int g_pairs_count = 0;
+template <int N>
+constexpr int length(const char* const (&)[N]) { return N; }
+static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
+static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
+static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
+static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per PairsInstance");
 
-int pairs_launched(const char* what, int instance) {
+// Aux and scene entry points launch one kernel each, so their record keeps the last launch only; K4 and pairs entry points
+// launch up to two, and a caller may read after several calls.
+constexpr int kRecordCap = 32;
+struct Family {
+  const char* const* names;
+  int count;
+  int cap;              // launches the record keeps, <= kRecordCap
+  const char* name_fn;  // for the out-of-range error text
+};
+static const Family kFamilies[] = {
+    {kAuxNames, kAuxInstances, 1, "hsr_aux_instance_name"},        // kLaunchAux
+    {kSceneNames, kSceneInstances, 1, "hsr_scene_instance_name"},  // kLaunchScene
+    {kK4Names, kK4Instances, kRecordCap, "hsr_k4_instance_name"},  // kLaunchK4
+    {kPairsNames, kPairsInstances, kRecordCap, "hsr_pairs_instance_name"},  // kLaunchPairs
+};
+struct Record {
+  int seq[kRecordCap];
+  int count;
+};
+static thread_local Record g_records[4];
+
+static void record_append(LaunchFamily f, int instance) {
+  Record& r = g_records[f];
+  if (r.count == kFamilies[f].cap) {
+    for (int i = 1; i < r.count; ++i) r.seq[i - 1] = r.seq[i];
+    --r.count;
+  }
+  r.seq[r.count++] = instance;
+}
+
+int launched(LaunchFamily f, const char* what, int first, int second) {
   const int rc = check_hip(hipGetLastError(), what);
   if (rc == HSR_OK) {
-    if (g_pairs_count == kPairsRecordCap) {
-      for (int i = 1; i < kPairsRecordCap; ++i) g_pairs_seq[i - 1] = g_pairs_seq[i];
-      --g_pairs_count;
-    }
-    g_pairs_seq[g_pairs_count++] = instance;
+    record_append(f, first);
+    if (second >= 0) record_append(f, second);
   }
   return rc;
 }
 
+// Always clears the record; writes the names joined by "; ", cut to capacity - 1 characters, unless there is no buffer.
+static int record_read(LaunchFamily f, char* names, int32_t capacity) {
+  Record& r = g_records[f];
+  const int count = r.count;
+  r.count = 0;
+  if (!names || capacity < 1) return count > 0 ? 1 : 0;
+  names[0] = 0;
+  size_t used = 0;
+  for (int i = 0; i < count && used + 1 < (size_t)capacity; ++i) {
+    const int w = snprintf(names + used, (size_t)capacity - used, "%s%s", i ? "; " : "", kFamilies[f].names[r.seq[i]]);
+    if (w < 0) break;
+    used += (size_t)w < (size_t)capacity - used ? (size_t)w : (size_t)capacity - used - 1;
+  }
+  return count > 0 ? 1 : 0;
+}
+
+static const char* instance_name(LaunchFamily f, int32_t i) {
+  if (i < 0 || i >= kFamilies[f].count) {
+    set_error("%s: i=%d outside [0,%d)", kFamilies[f].name_fn, i, kFamilies[f].count);
+    return nullptr;
+  }
+  return kFamilies[f].names[i];
+}
+
 }  // namespace hsr
 
-extern "C" int hsr_pairs_last_launch(char* names, int32_t capacity) {
-  const int count = hsr::g_pairs_count;
-  hsr::g_pairs_count = 0;
-  if (!names || capacity < 1) return count > 0 ? 1 : 0;
-  names[0] = 0;
-  size_t used = 0;
-  for (int i = 0; i < count && used + 1 < (size_t)capacity; ++i) {
-    const int w = snprintf(names + used, (size_t)capacity - used, "%s%s", i ? "; " : "", hsr::kPairsNames[hsr::g_pairs_seq[i]]);
-    if (w < 0) break;
-    used += (size_t)w < (size_t)capacity - used ? (size_t)w : (size_t)capacity - used - 1;
-  }
-  return count > 0 ? 1 : 0;
-}
-
-extern "C" int hsr_pairs_instance_count(void) { return hsr::kPairsInstances; }
-
-extern "C" const char* hsr_pairs_instance_name(int32_t i) {
-  if (i < 0 || i >= hsr::kPairsInstances) {
-    hsr::set_error("hsr_pairs_instance_name: i=%d outside [0,%d)", i, (int)hsr::kPairsInstances);
-    return nullptr;
-  }
-  return hsr::kPairsNames[i];
-}
-
-extern "C" int hsr_k4_last_launch(char* names, int32_t capacity) {
-  const int count = hsr::g_k4_count;
-  hsr::g_k4_count = 0;
-  if (!names || capacity < 1) return count > 0 ? 1 : 0;
-  names[0] = 0;
-  size_t used = 0;
-  for (int i = 0; i < count && used + 1 < (size_t)capacity; ++i) {
-    const int w = snprintf(names + used, (size_t)capacity - used, "%s%s", i ? "; " : "", hsr::kK4Names[hsr::g_k4_seq[i]]);
-    if (w < 0) break;
-    used += (size_t)w < (size_t)capacity - used ? (size_t)w : (size_t)capacity - used - 1;
-  }
-  return count > 0 ? 1 : 0;
-}
-
-extern "C" int hsr_k4_instance_count(void) { return hsr::kK4Instances; }
-
-extern "C" const char* hsr_k4_instance_name(int32_t i) {
-  if (i < 0 || i >= hsr::kK4Instances) {
-    hsr::set_error("hsr_k4_instance_name: i=%d outside [0,%d)", i, (int)hsr::kK4Instances);
-    return nullptr;
-  }
-  return hsr::kK4Names[i];
-}
-
-extern "C" int hsr_aux_last_launch(char* name, int32_t capacity) {
-  const int r = hsr::g_aux_last;
-  hsr::g_aux_last = -1;
-  if (!name || capacity < 1) return r >= 0 ? 1 : 0;
-  name[0] = 0;
-  if (r < 0) return 0;
-  snprintf(name, (size_t)capacity, "%s", hsr::kAuxNames[r]);
-  return 1;
-}
-
+extern "C" int hsr_aux_last_launch(char* name, int32_t capacity) { return hsr::record_read(hsr::kLaunchAux, name, capacity); }
 extern "C" int hsr_aux_instance_count(void) { return hsr::kAuxInstances; }
-
-extern "C" const char* hsr_aux_instance_name(int32_t i) {
-  if (i < 0 || i >= hsr::kAuxInstances) {
-    hsr::set_error("hsr_aux_instance_name: i=%d outside [0,%d)", i, (int)hsr::kAuxInstances);
-    return nullptr;
-  }
-  return hsr::kAuxNames[i];
-}
-
-extern "C" int hsr_scene_last_launch(char* name, int32_t capacity) {
-  const int r = hsr::g_scene_last;
-  hsr::g_scene_last = -1;
-  if (!name || capacity < 1) return r >= 0 ? 1 : 0;
-  name[0] = 0;
-  if (r < 0) return 0;
-  snprintf(name, (size_t)capacity, "%s", hsr::kSceneNames[r]);
-  return 1;
-}
-
+extern "C" const char* hsr_aux_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchAux, i); }
+extern "C" int hsr_scene_last_launch(char* name, int32_t capacity) { return hsr::record_read(hsr::kLaunchScene, name, capacity); }
 extern "C" int hsr_scene_instance_count(void) { return hsr::kSceneInstances; }
-
-extern "C" const char* hsr_scene_instance_name(int32_t i) {
-  if (i < 0 || i >= hsr::kSceneInstances) {
-    hsr::set_error("hsr_scene_instance_name: i=%d outside [0,%d)", i, (int)hsr::kSceneInstances);
-    return nullptr;
-  }
-  return hsr::kSceneNames[i];
-}
+extern "C" const char* hsr_scene_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchScene, i); }
+extern "C" int hsr_k4_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchK4, names, capacity); }
+extern "C" int hsr_k4_instance_count(void) { return hsr::kK4Instances; }
+extern "C" const char* hsr_k4_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchK4, i); }
+extern "C" int hsr_pairs_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchPairs, names, capacity); }
+extern "C" int hsr_pairs_instance_count(void) { return hsr::kPairsInstances; }
+extern "C" const char* hsr_pairs_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchPairs, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

@@ -809,10 +809,10 @@ __global__ __launch_bounds__(256) void pool_models_kernel(const PoolModelArgs a)
 using namespace hsr;
 
 // HSR_LAUNCH_CHECK that also appends the instance to the calling thread's record (hsr_pairs_last_launch) on success
-#define HSR_PAIRS_LAUNCHED(name, instance)                           \
-  do {                                                               \
-    int rc_ = hsr::pairs_launched(name " launch", (instance));       \
-    if (rc_ != HSR_OK) return rc_;                                   \
+#define HSR_PAIRS_LAUNCHED(name, instance)                                    \
+  do {                                                                        \
+    int rc_ = hsr::launched(hsr::kLaunchPairs, name " launch", (instance));   \
+    if (rc_ != HSR_OK) return rc_;                                            \
   } while (0)
 
 extern "C" int hsr_pair_prep(const void* emit_dev, int32_t emit_dtype, int64_t pair_emit, int32_t emit_bands,

@@ -370,14 +370,14 @@ extern "C" int hsr_block_mean(const void* in_dev, int32_t in_dtype, int64_t in_b
     case 2: staged = launch_block_mean_tile((const uint16_t*)in_dev, in_bs, in_ps, nb, Hc, Wc, factor, scale, out_dev, out_bs, out_ps, s); break;
     default: break;
   }
-  if (staged) return aux_launched("block_mean_tile_kernel launch", kAuxBlockMeanTile + in_dtype);
+  if (staged) return launched(kLaunchAux, "block_mean_tile_kernel launch", kAuxBlockMeanTile + in_dtype);
   switch (in_dtype) {
     case 0: hipLaunchKernelGGL(block_mean_kernel<float>, grid, block, 0, s, (const float*)in_dev, in_bs, in_ps, Hc, Wc, factor, scale, nb, out_dev, out_bs, out_ps); break;
     case 1: hipLaunchKernelGGL(block_mean_kernel<uint8_t>, grid, block, 0, s, (const uint8_t*)in_dev, in_bs, in_ps, Hc, Wc, factor, scale, nb, out_dev, out_bs, out_ps); break;
     case 2: hipLaunchKernelGGL(block_mean_kernel<uint16_t>, grid, block, 0, s, (const uint16_t*)in_dev, in_bs, in_ps, Hc, Wc, factor, scale, nb, out_dev, out_bs, out_ps); break;
     default: set_error("hsr_block_mean: in_dtype=%d (0 float32, 1 uint8, 2 uint16)", in_dtype); return HSR_ERR_UNSUPPORTED;
   }
-  return aux_launched("block_mean_kernel launch", kAuxBlockMean + in_dtype);
+  return launched(kLaunchAux, "block_mean_kernel launch", kAuxBlockMean + in_dtype);
 }
 
 extern "C" int hsr_bilinear_upsample(const float* in_dev, int64_t in_bs, int64_t in_ps, int32_t nb, int32_t Hc,
@@ -401,7 +401,7 @@ extern "C" int hsr_bilinear_upsample(const float* in_dev, int64_t in_bs, int64_t
   else
     hipLaunchKernelGGL((bilinear_up_kernel<false, false>), grid, dim3(256), 0, (hipStream_t)stream, in_dev, in_bs, in_ps, Hc, Wc,
                        factor, nb, out_dev, out_bs, out_ps);
-  return aux_launched("bilinear_up_kernel launch", kAuxBilinearUp + (vec4 ? 1 : 0) + (vec4 && in4 ? 1 : 0));
+  return launched(kLaunchAux, "bilinear_up_kernel launch", kAuxBilinearUp + (vec4 ? 1 : 0) + (vec4 && in4 ? 1 : 0));
 }
 
 extern "C" int hsr_bilinear_upsample_mask_hist(const float* in_dev, int64_t in_bs, int64_t in_ps, int32_t nb, int32_t Hc,
@@ -425,5 +425,5 @@ extern "C" int hsr_bilinear_upsample_mask_hist(const float* in_dev, int64_t in_b
   else
     hipLaunchKernelGGL(bilinear_up_hist_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, in_dev, in_bs, in_ps, Hc, Wc, factor,
                        nb, out_dev, mask_out_dev, hist1);
-  return aux_launched("bilinear_up_hist_kernel launch", kAuxBilinearUpHist + (in4 ? 1 : 0));
+  return launched(kLaunchAux, "bilinear_up_hist_kernel launch", kAuxBilinearUpHist + (in4 ? 1 : 0));
 }

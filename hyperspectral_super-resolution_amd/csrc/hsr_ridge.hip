@@ -701,7 +701,7 @@ static int launch_predict(const PredArgs& a, int degree, hipStream_t s, int npai
   raise_lds_limit(kern, lds, configured[slot]);
   if (orb) hipLaunchKernelGGL(orb, dim3(gx, slices, npairs), dim3(threads), lds, s, a, rows);
   else hipLaunchKernelGGL(generic, dim3(gx, 1, npairs), dim3(threads), lds, s, a);
-  return k4_launched(what, instance);
+  return launched(kLaunchK4, what, instance);
 }
 
 static int ensure_table(int n_in, int degree) {
@@ -781,7 +781,7 @@ extern "C" int hsr_polyfeat_expand_f64(const float* x_dev, int64_t x_rs, int64_t
               "hsr_polyfeat_expand_f64: ncols=%d ldp=%lld (need ncols >= %d)", ncols, (long long)ldp, g_table_nfeat + 1);
   hipLaunchKernelGGL(expand_f64_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, (hipStream_t)stream, x_dev, x_rs,
                      x_cs, mean_dev, scale_dev, n, n_in, g_table_nfeat, g_table_dev, p_dev, ldp, ncols);
-  return k4_launched("expand_f64_kernel launch", kK4Expand);
+  return launched(kLaunchK4, "expand_f64_kernel launch", kK4Expand);
 }
 
 extern "C" int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const double* mean_dev, const double* scale_dev,
@@ -799,7 +799,7 @@ extern "C" int hsr_pair_expand_f64(const float* x_dev, int64_t pair_x, const dou
                    n_in, g_table_nfeat, T, na, eps, g_table_dev};
   hipLaunchKernelGGL(pair_expand_f64_kernel, dim3((unsigned)((npix + 31) / 32), (unsigned)npairs), dim3(256), 0,
                      (hipStream_t)stream, a);
-  return k4_launched("pair_expand_f64_kernel launch", kK4PairExpand);
+  return launched(kLaunchK4, "pair_expand_f64_kernel launch", kK4PairExpand);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -998,7 +998,7 @@ extern "C" int hsr_ridge_stats(const float* x_dev, int64_t x_rs, int64_t x_cs, i
   static_assert(kStatsBlocks <= 64, "one lane per block");
   hipLaunchKernelGGL(ridge_stats_finish_kernel, dim3(1), dim3(64 * n_in), 0, (hipStream_t)stream, x_dev, x_cs, n, n_in, nblocks,
                      work_dev, stats_dev, mean_dev, scale_dev);
-  return k4_launched("ridge_stats_kernel launch", kK4StatsPartial, kK4StatsFinish);
+  return launched(kLaunchK4, "ridge_stats_kernel launch", kK4StatsPartial, kK4StatsFinish);
 }
 
 // One launch of ridge_assemble_kernel behind hsr_ridge_assemble (npairs = 1, strides 0, empty_identity = 0) and its batched form:
@@ -1013,7 +1013,7 @@ static int launch_assemble(const char* who, const double* g_dev, int64_t ldg, in
   const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
   hipLaunchKernelGGL(ridge_assemble_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, s, g_dev, ldg, na, nf, T, alpha, a_dev,
                      npad, b_dev, ldb, info_dev, pair_g, pair_a, pair_b, empty_identity);
-  return k4_launched("ridge_assemble_kernel launch", kK4Assemble);
+  return launched(kLaunchK4, "ridge_assemble_kernel launch", kK4Assemble);
 }
 
 // One launch of ridge_finish_kernel behind hsr_ridge_finish (npairs = 1, an empty FinishPairs: no status word, no NaN intercepts)
@@ -1033,7 +1033,7 @@ static int launch_finish(const char* who, const double* g_dev, int32_t na, int32
   if (cpy > grid) grid = (int)(cpy < 64 ? cpy : 64);
   hipLaunchKernelGGL(ridge_finish_kernel, dim3(grid, (unsigned)npairs), dim3(256), 0, s, g_dev, na, nf, T, w_dev, ldw, mean_dev,
                      scale_dev, n_in, kpad, b64_dev, b32_dev, w32_dev, mean32_dev, inv32_dev, pp);
-  return k4_launched("ridge_finish_kernel launch", kK4Finish);
+  return launched(kLaunchK4, "ridge_finish_kernel launch", kK4Finish);
 }
 
 extern "C" int hsr_ridge_assemble(const double* g_dev, int64_t ldg, int32_t na, int32_t nf, int32_t T, double alpha,

@@ -112,7 +112,7 @@ template <typename T>
 static int launch_scan(const SceneScanArgs<T>& a, hipStream_t s) {
   const int wc = a.nx * a.tile_w, hc = a.ny * a.tile_h;
   hipLaunchKernelGGL(scene_black_kernel<T>, dim3((unsigned)((wc + 255) / 256), (unsigned)((hc + a.rows - 1) / a.rows)), dim3(256), 0, s, a);
-  return scene_launched("scene_black_kernel launch", kSceneBlack + (sizeof(T) == 2 ? 1 : 0));
+  return launched(kLaunchScene, "scene_black_kernel launch", kSceneBlack + (sizeof(T) == 2 ? 1 : 0));
 }
 
 // ---- gather ----------------------------------------------------------------------------------------------------------------
@@ -182,7 +182,7 @@ static int launch_gather(const SceneGatherArgs& a, int ntiles, hipStream_t s) {
     hipLaunchKernelGGL((scene_gather_kernel<TI, TO, kEncode, true>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((scene_gather_kernel<TI, TO, kEncode, false>), grid, dim3(256), 0, s, a);
-  return scene_launched("scene_gather_kernel launch", kSceneGather + 2 * pair + (vec ? 1 : 0));
+  return launched(kLaunchScene, "scene_gather_kernel launch", kSceneGather + 2 * pair + (vec ? 1 : 0));
 }
 
 // ---- mosaic ----------------------------------------------------------------------------------------------------------------
@@ -408,7 +408,7 @@ extern "C" int hsr_scene_mosaic(const float* cubes_dev, int32_t ncubes, int32_t 
     hipLaunchKernelGGL(scene_mosaic_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(scene_mosaic_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  return scene_launched("scene_mosaic_kernel launch", kSceneMosaic + (vec ? 1 : 0));
+  return launched(kLaunchScene, "scene_mosaic_kernel launch", kSceneMosaic + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, int32_t T, int32_t th, int32_t tw, int32_t sy, int32_t sx,
@@ -445,5 +445,5 @@ extern "C" int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, in
   if (vec) launch_blend<true>(a, grid, (hipStream_t)stream);
   else launch_blend<false>(a, grid, (hipStream_t)stream);
   const int lg = K <= 1 ? 0 : K <= 2 ? 1 : K <= 4 ? 2 : K <= 8 ? 3 : 4;        // launch_blend's KMAX
-  return scene_launched("scene_blend_kernel launch", kSceneBlend + (vec ? 5 : 0) + lg);
+  return launched(kLaunchScene, "scene_blend_kernel launch", kSceneBlend + (vec ? 5 : 0) + lg);
 }

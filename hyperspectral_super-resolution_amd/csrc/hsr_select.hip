@@ -678,8 +678,8 @@ extern "C" int hsr_percentile_hist(int32_t pass, const float* x_dev, int64_t x_b
     else if (pass == 2) hipLaunchKernelGGL((select_hist_kernel<2, 0>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((select_hist_kernel<3, 0>), grid, block, 0, s, a);
   }
-  if (rows4 && !vec) return aux_launched("select_hist_rows4_kernel launch", kAuxSelectRows4 + pass - 1);
-  return aux_launched("select_hist_kernel launch", kAuxSelectHist + (pass - 1) * 2 + (vec ? 1 : 0));
+  if (rows4 && !vec) return launched(kLaunchAux, "select_hist_rows4_kernel launch", kAuxSelectRows4 + pass - 1);
+  return launched(kLaunchAux, "select_hist_kernel launch", kAuxSelectHist + (pass - 1) * 2 + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_percentile_scan(int32_t pass, int32_t nb, double pmin, double pmax, void* work_dev,
@@ -695,7 +695,7 @@ extern "C" int hsr_percentile_scan(int32_t pass, int32_t nb, double pmin, double
   if (pass == 1) hipLaunchKernelGGL(select_scan_kernel<1>, dim3(nb), dim3(256), 0, s, a, qlo, qhi, lohi_dev);
   else if (pass == 2) hipLaunchKernelGGL(select_scan_kernel<2>, dim3(nb), dim3(256), 0, s, a, qlo, qhi, lohi_dev);
   else hipLaunchKernelGGL(select_scan_kernel<3>, dim3(nb), dim3(256), 0, s, a, qlo, qhi, lohi_dev);
-  return aux_launched("select_scan_kernel launch", kAuxSelectScan + pass - 1);
+  return launched(kLaunchAux, "select_scan_kernel launch", kAuxSelectScan + pass - 1);
 }
 
 extern "C" int hsr_percentile_limits(const float* x_dev, int64_t x_bs, int64_t x_ps, const uint8_t* mask_dev,
@@ -713,7 +713,7 @@ extern "C" int hsr_percentile_limits(const float* x_dev, int64_t x_bs, int64_t x
     int rc0 = select_setup(a, x_dev, x_bs, x_ps, mask_dev, npix, nb, work_dev, "hsr_percentile_limits");
     if (rc0 != HSR_OK) return rc0;
     hipLaunchKernelGGL(select_tiny_kernel, dim3(nb), dim3(kSelThreads), 0, (hipStream_t)stream, a, pmin / 100.0, pmax / 100.0, lohi_dev);
-    return aux_launched("select_tiny_kernel launch", kAuxSelectTiny);
+    return launched(kLaunchAux, "select_tiny_kernel launch", kAuxSelectTiny);
   }
   int rc = hsr_percentile_begin(work_dev, nb, stream);
   if (rc != HSR_OK) return rc;

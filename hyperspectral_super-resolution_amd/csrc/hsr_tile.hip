@@ -100,7 +100,7 @@ static int launch_transpose(const void* in, void* out, int64_t batch, int64_t R,
   HSR_REQUIRE(tiles_c * tiles_r < ((int64_t)1 << 31) && batch <= 65535, HSR_ERR_UNSUPPORTED, "hsr_interleave_to_bip: shape too large");
   hipLaunchKernelGGL((transpose_rc_kernel<TI, TO>), dim3((unsigned)(tiles_c * tiles_r), (unsigned)batch), dim3(256), 0, s,
                      (const TI*)in, (TO*)out, R, C, tiles_c);
-  return aux_launched("transpose_rc_kernel launch", kAuxTranspose + pair);
+  return launched(kLaunchAux, "transpose_rc_kernel launch", kAuxTranspose + pair);
 }
 
 static unsigned stream_grid(int64_t n) {
@@ -122,7 +122,7 @@ extern "C" int hsr_tile_encode_u16(const float* x_dev, int64_t n, float scale, i
   const bool vec = ((((uintptr_t)x_dev) & 15) == 0) && ((((uintptr_t)out_dev) & 7) == 0);
   hipLaunchKernelGGL(hsr::tile_encode_kernel, dim3(hsr::stream_grid(n)), dim3(256), 0, (hipStream_t)stream, x_dev, n,
                      scale, has_src_nodata, src_nodata, nodata_u16, out_dev, vec);
-  return hsr::aux_launched("tile_encode_kernel launch", hsr::kAuxTileEncode + (vec ? 1 : 0));
+  return hsr::launched(hsr::kLaunchAux, "tile_encode_kernel launch", hsr::kAuxTileEncode + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_tile_decode_u16(const uint16_t* u_dev, int64_t n, float scale, int32_t nodata, float* out_dev,
@@ -134,7 +134,7 @@ extern "C" int hsr_tile_decode_u16(const uint16_t* u_dev, int64_t n, float scale
   const bool vec = ((((uintptr_t)u_dev) & 7) == 0) && ((((uintptr_t)out_dev) & 15) == 0);   // as in hsr_tile_encode_u16
   hipLaunchKernelGGL(hsr::tile_decode_kernel, dim3(hsr::stream_grid(n)), dim3(256), 0, (hipStream_t)stream, u_dev, n,
                      scale, nodata < 0 ? 0x10000u : (uint32_t)nodata, out_dev, vec);
-  return hsr::aux_launched("tile_decode_kernel launch", hsr::kAuxTileDecode + (vec ? 1 : 0));
+  return hsr::launched(hsr::kLaunchAux, "tile_decode_kernel launch", hsr::kAuxTileDecode + (vec ? 1 : 0));
 }
 
 extern "C" int hsr_interleave_to_bip(const void* in_dev, int32_t in_dtype, int32_t interleave, int64_t lines, int64_t samples,

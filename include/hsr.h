@@ -869,30 +869,31 @@ int hsr_srf_kernel_instance(int32_t deg, int32_t variant);
  * "moments_kernel<4>", "reduce_kernel" - truncated to `capacity` bytes, then clears the record; 0 (and "") if there was no
  * launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same. */
 int hsr_poly_last_launch(char* name, int32_t capacity);
-/* The same for the operators around them: the percentile select (csrc/hsr_select.hip), the resamplers (csrc/hsr_resample.hip),
- * the uint16 tile codec and the ENVI transposer (csrc/hsr_tile.hip).  Host only, same contract, so HSR_ABI_VERSION stays.
- * hsr_aux_last_launch returns 1 and writes the name of the calling thread's last successful launch from those three files -
- * kernel and template arguments as in the source, e.g. "select_hist_kernel<2, 1>", "select_tiny_kernel",
- * "block_mean_tile_kernel<uint8_t>", "bilinear_up_kernel<true, false>", "transpose_rc_kernel<uint16_t, float>"; the codec
- * kernels, which take their 16-byte path as an argument computed on the host from the two pointers, as "tile_encode_kernel vec" /
- * "tile_encode_kernel scalar" (decode alike) - truncated to `capacity` bytes, then clears the record; 0 (and "") if there was
- * no such launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same.
- * An entry point that launches several kernels (hsr_percentile_limits above 32768 pixels, a BIL cube of more than 65535
- * lines) leaves the last one.
- * hsr_aux_instance_count / hsr_aux_instance_name(i), 0 <= i < count: every name the record can return (NULL and the error
- * text outside that range). */
+/* Launch records of four more kernel families: aux, scene, k4 and pairs below.  Host only, one record per family and thread;
+ * exports only, no entry point gains an argument, so HSR_ABI_VERSION stays.  The shared contract, hsr_X_ for one family:
+ *   - every successful launch of the family's kernels appends the kernel's name to the calling thread's record; the record holds
+ *     the most recent 1 (aux, scene) or 32 (k4, pairs) launches, in launch order.  A call refused by its argument checks adds
+ *     nothing;
+ *   - hsr_X_last_launch returns 1 and writes the names joined by "; ", NUL-terminated and truncated to `capacity` bytes, then
+ *     clears the record; 0 (and "") if there was no launch since the last read.  names NULL or capacity < 1: only the return
+ *     value, the record is cleared all the same;
+ *   - a name is the kernel and its template arguments as in the source, e.g. "select_hist_kernel<2, 1>"; a path that the host
+ *     computes and that is uniform over the launch is a suffix, e.g. "tile_encode_kernel vec";
+ *   - hsr_X_instance_count / hsr_X_instance_name(i), 0 <= i < count: every name the record can hold (NULL and the error text
+ *     outside that range).  Each family has a table of its own, so a new kernel changes one count: 32 / 20 / 31 / 12.
+ * aux (hsr_aux_last_launch; hsr_aux_instance_count = 32, hsr_aux_instance_name; one slot): the operators around K1 - K3 - the
+ * percentile select (csrc/hsr_select.hip), the resamplers (csrc/hsr_resample.hip), the uint16 tile codec and the ENVI transposer
+ * (csrc/hsr_tile.hip) - e.g. "select_tiny_kernel", "block_mean_tile_kernel<uint8_t>", "bilinear_up_kernel<true, false>",
+ * "transpose_rc_kernel<uint16_t, float>"; the codec kernels, which take their 16-byte path as an argument computed on the host
+ * from the two pointers, as "tile_encode_kernel vec" / "tile_encode_kernel scalar" (decode alike).  An entry point that launches
+ * several kernels (hsr_percentile_limits above 32768 pixels, a BIL cube of more than 65535 lines) leaves the last one. */
 int hsr_aux_last_launch(char* name, int32_t capacity);
 int hsr_aux_instance_count(void);
 const char* hsr_aux_instance_name(int32_t i);
-/* The same for the scene kernels (csrc/hsr_scene.hip), in a table of their own: hsr_aux_instance_count stays 32.  Host only, per
- * thread, same contract, so HSR_ABI_VERSION stays.  Each of hsr_scene_black_counts, hsr_scene_gather_tiles, hsr_scene_mosaic and
- * hsr_scene_mosaic_blend launches one kernel; hsr_scene_last_launch returns 1 and writes the name of the calling thread's last
- * successful such launch - kernel and template arguments as in the source: "scene_black_kernel<uint16_t>",
- * "scene_gather_kernel<float, uint16_t, true, false>" (<TI, TO, kEncode, kVec>), "scene_mosaic_kernel<true>" (<kVec>),
- * "scene_blend_kernel<false, 8>" (<kVec, KMAX>) - truncated to `capacity` bytes, then clears the record; 0 (and "") if there
- * was no such launch since the last read.  name NULL or capacity < 1: only the return value, the record is cleared all the same.
- * hsr_scene_instance_count (20) / hsr_scene_instance_name(i), 0 <= i < count: every name the record can return (NULL and the
- * error text outside that range). */
+/* scene (hsr_scene_last_launch; hsr_scene_instance_count = 20, hsr_scene_instance_name; one slot): csrc/hsr_scene.hip.  Each of
+ * hsr_scene_black_counts, hsr_scene_gather_tiles, hsr_scene_mosaic and hsr_scene_mosaic_blend launches one kernel:
+ * "scene_black_kernel<uint16_t>", "scene_gather_kernel<float, uint16_t, true, false>" (<TI, TO, kEncode, kVec>),
+ * "scene_mosaic_kernel<true>" (<kVec>), "scene_blend_kernel<false, 8>" (<kVec, KMAX>). */
 int hsr_scene_last_launch(char* name, int32_t capacity);
 int hsr_scene_instance_count(void);
 const char* hsr_scene_instance_name(int32_t i);
@@ -902,16 +903,10 @@ const char* hsr_scene_instance_name(int32_t i);
  * orbit_rows < 0 answers for the library as it stands, 0 / 1 as if the rows were absent / on the device.  Host only; it
  * adds no record and changes no entry point, so HSR_ABI_VERSION stays. */
 int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t orbit_rows);
-/* Which kernel instances of the polynomial-ridge family (K4: csrc/hsr_ridge.hip, csrc/hsr_gram.hip, csrc/hsr_chol.hip) ran.  Host
- * only, per thread, same contract as the three records above: no entry point gains an argument, so HSR_ABI_VERSION stays.
- * One difference: a K4 entry point launches up to two kernels whose selection differs (Gram: main + reduce; Cholesky: factor +
- * solve; statistics: partial + finish), so the record keeps EVERY kernel the calling thread launched successfully since the last
- * read (the 32 most recent), in launch order.  hsr_k4_last_launch returns 1 and writes their names joined by "; " - e.g.
- * "gram_f64_lds_kernel wide+diag+narrow; gram_reduce_kernel" - NUL-terminated and truncated to `capacity` bytes, then clears
- * the record; 0 (and "") if there was no launch since the last read.  name NULL or capacity < 1: only the return value, the
- * record is cleared all the same.  A call refused by its argument checks adds nothing.
- * Names are the kernel and its template arguments as in the source; a path that the host computes and that is uniform over
- * the launch is a suffix:
+/* k4 (hsr_k4_last_launch; hsr_k4_instance_count = 31, hsr_k4_instance_name; the 32 most recent launches): the polynomial-ridge
+ * family, csrc/hsr_ridge.hip, csrc/hsr_gram.hip and csrc/hsr_chol.hip, under the contract above hsr_aux_last_launch.  A K4 entry
+ * point launches up to two kernels whose selection differs (Gram: main + reduce; Cholesky: factor + solve; statistics: partial +
+ * finish), hence the list - e.g. "gram_f64_lds_kernel wide+diag+narrow; gram_reduce_kernel".  The names:
  *   expand_f64_kernel, pair_expand_f64_kernel, ridge_stats_partial_kernel, ridge_stats_finish_kernel, ridge_assemble_kernel,
  *   ridge_finish_kernel, predict_kernel<1 / 2 / 4>;
  *   predict103_x16_kernel and predict103_slice_kernel<1 / 2 / 3> with " x2" (the inputs of a pixel read as five float2: x_cs == 1,
@@ -920,25 +915,18 @@ int hsr_polyfeat_predict_kernel(int32_t n_in, int32_t degree, int32_t T, int32_t
  *   gram_f64_lds_kernel with the block kinds of its plan joined by "+" in the order wide, diag, narrow; gram_f64_kernel sym /
  *   gram_f64_kernel full (with / without the symmetric skip); gram_reduce_kernel;
  *   chol_factor_res_kernel (n <= 288), chol_factor_kernel, chol_solve_kernel lds / chol_solve_kernel global (block inverses
- *   staged in LDS or read from the workspace).
- * hsr_k4_instance_count / hsr_k4_instance_name(i), 0 <= i < count: every name the record can hold (NULL and the error text
- * outside that range). */
+ *   staged in LDS or read from the workspace). */
 int hsr_k4_last_launch(char* names, int32_t capacity);
 int hsr_k4_instance_count(void);
 const char* hsr_k4_instance_name(int32_t i);
-/* The same for the tile-pair kernels (csrc/hsr_pairs.hip), in a table of their own: hsr_k4_instance_count stays 31 and
- * pair_expand_f64_kernel stays in the K4 record.  Host only, per thread, the K4 record's contract (hsr_pair_report_f64 and
- * hsr_pair_score_f64 launch two kernels per call): every kernel the calling thread launched successfully since the last read
- * (the 32 most recent), in launch order, joined by "; " - e.g. "pair_score_partial_kernel<true>; pair_score_finish_kernel" -
- * NUL-terminated and truncated to `capacity` bytes; reading clears the record; 0 (and "") without a launch; names NULL or
- * capacity < 1: only the return value, the record is cleared all the same.  A call refused by its argument checks adds nothing.
- * Exports only are added, so HSR_ABI_VERSION stays.  The 12 names: pair_prep_kernel, pair_stats_kernel,
- * pair_report_partial_kernel, pair_report_finish_kernel, pair_holdout_kernel, pair_score_partial_kernel<false> / <true> (<kVec>:
- * hsr_pair_score_f64's alignment predicate), pair_score_finish_kernel, pool_stats_kernel, pool_gram_kernel<false> / <true>
- * (<kVec>: hsr_pool_gram's), pool_models_kernel.  The one- or two-group walk of the score kernel is chosen on the device, per
- * chunk, and is not part of the name.
- * hsr_pairs_instance_count (12) / hsr_pairs_instance_name(i), 0 <= i < count: every name the record can hold (NULL and the error
- * text outside that range). */
+/* pairs (hsr_pairs_last_launch; hsr_pairs_instance_count = 12, hsr_pairs_instance_name; the 32 most recent launches): the
+ * tile-pair kernels, csrc/hsr_pairs.hip, under the same contract (pair_expand_f64_kernel stays in the K4
+ * record).  hsr_pair_report_f64 and hsr_pair_score_f64 launch two kernels per call - e.g. "pair_score_partial_kernel<true>;
+ * pair_score_finish_kernel".  The names: pair_prep_kernel, pair_stats_kernel, pair_report_partial_kernel,
+ * pair_report_finish_kernel, pair_holdout_kernel, pair_score_partial_kernel<false> / <true> (<kVec>: hsr_pair_score_f64's
+ * alignment predicate), pair_score_finish_kernel, pool_stats_kernel, pool_gram_kernel<false> / <true> (<kVec>: hsr_pool_gram's),
+ * pool_models_kernel.  The one- or two-group walk of the score kernel is chosen on the device, per chunk, and is not part of the
+ * name. */
 int hsr_pairs_last_launch(char* names, int32_t capacity);
 int hsr_pairs_instance_count(void);
 const char* hsr_pairs_instance_name(int32_t i);

@@ -36,7 +36,7 @@ NAMES = ("pair_prep_kernel", "pair_stats_kernel", "pair_report_partial_kernel", 
          "pair_score_partial_kernel<false>", "pair_score_partial_kernel<true>", "pair_score_finish_kernel", "pool_stats_kernel",
          "pool_gram_kernel<false>", "pool_gram_kernel<true>", "pool_models_kernel")
 INSTANCE_COUNT = 12
-FILL = 0xA5                      # the sentinel byte of the GPU tests' buffers (test_gpu_aux_instances.Buf)
+FILL = 0xA5                      # the sentinel byte of the GPU tests' buffers (gpu_harness.Buf)
 P = 3                            # pairs of a batch
 DT_CODE = {"float32": 0, "uint16": 2}
 NP_DT = {"float32": np.float32, "uint16": np.uint16}

@@ -15,6 +15,7 @@ import warnings
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 from oracle import oracle_np as onp
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
@@ -22,15 +23,6 @@ pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
 warnings.simplefilter("ignore")
 
 MIN_COUNT = 5
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 def _rel_err(got, ref):

@@ -24,87 +24,14 @@ import warnings
 import numpy as np
 import pytest
 
+from gpu_harness import SENT32, Buf, LaunchLog, bits_equal, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib, stream as _stream
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
 
-SEEN = set()
-FILL = 0xA5                      # sentinel byte of every buffer
-GUARD = 256                      # bytes before and after a buffer's payload (keeps the payload 256-byte aligned)
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
-
-
-def _lib():
-    from s2_emit import _native as nat
-    return nat.load()
-
-
-def _stream(torch):
-    from s2_emit import _engine as eng
-    return eng._stream(torch)
-
-
-def _record():
-    buf = C.create_string_buffer(96)
-    return buf.value.decode() if _lib().hsr_aux_last_launch(buf, 96) == 1 else None
-
-
-def _call(expect, fn, *args):
-    """Run an entry point, check its return code and the instance its (last) launch was; expect None: no launch."""
-    _lib().hsr_aux_last_launch(None, 0)
-    rc = fn(*args)
-    assert rc == 0, (rc, _lib().hsr_last_error())
-    got = _record()
-    assert got == expect, (got, expect)
-    if got is not None:
-        SEEN.add(got)
-
-
-class Buf:
-    """`nbytes` of device memory `off` bytes past a 256-byte boundary, sentinel-filled, between two sentinel guard zones."""
-
-    def __init__(self, torch, nbytes, off=0, data=None):
-        self.torch, self.nbytes, self.lo = torch, int(nbytes), GUARD + off
-        self.t = torch.full((GUARD + off + self.nbytes + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-        assert self.t.data_ptr() % 256 == 0
-        if data is not None:
-            self.put(data)
-
-    def put(self, data, at=0):
-        raw = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
-        assert at + raw.size <= self.nbytes
-        self.t[self.lo + at: self.lo + at + raw.size] = self.torch.from_numpy(raw.copy()).cuda()
-
-    @property
-    def ptr(self):
-        return C.c_void_p(self.t.data_ptr() + self.lo)
-
-    def get(self, dtype):
-        """The payload as `dtype` (host copy), after checking that nothing outside it was written."""
-        self.torch.cuda.synchronize()
-        h = self.t.cpu().numpy()
-        assert (h[:self.lo] == FILL).all() and (h[self.lo + self.nbytes:] == FILL).all(), "write outside the buffer"
-        return h[self.lo: self.lo + self.nbytes].copy().view(dtype)
-
-
-SENT32 = np.frombuffer(bytes([FILL] * 4), np.uint32)[0]
-
-
-def _bits_equal(got, ref, what):
-    got, ref = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(ref, np.float32)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    gn, rn = np.isnan(got), np.isnan(ref)
-    assert np.array_equal(gn, rn), f"{what}: NaN positions differ ({int(gn.sum())} vs {int(rn.sum())})"
-    bad = got.view(np.uint32)[~gn] != ref.view(np.uint32)[~rn]
-    assert not bad.any(), f"{what}: {int(bad.sum())} elements differ, first {got[~gn][bad][:4]} vs {ref[~rn][bad][:4]}"
+LOG = LaunchLog("hsr_aux_last_launch")
+_call = LOG.call
 
 
 def _f32(bits):
@@ -595,11 +522,11 @@ def test_block_mean_rows(torch_gpu, row):
             assert (raw[:, nb:] == SENT32).all(), "pad columns written"
             got = np.ascontiguousarray(raw[:, :nb].T).view(np.float32).reshape(nb, Hc, Wc)
         if T is np.float32:
-            _bits_equal(got, _bm_ref_f32(x, f, scale), f"{dname} vs ordered float64 sum")
+            bits_equal(got, _bm_ref_f32(x, f, scale), f"{dname} vs ordered float64 sum")
             if dname == "q12":
-                _bits_equal(got, onp.block_mean(x, f) * np.float32(scale), "q12 vs oracle")
+                bits_equal(got, onp.block_mean(x, f) * np.float32(scale), "q12 vs oracle")
         else:
-            _bits_equal(got, onp.block_mean(x, f) * np.float32(scale), "vs oracle")
+            bits_equal(got, onp.block_mean(x, f) * np.float32(scale), "vs oracle")
 
 
 # =============================================================================================================================
@@ -655,7 +582,7 @@ def _layout_in(torch, x, lay):
 def _check_rows_out(raw, nb, ref, rowlen, pad_zero, what):
     """raw uint32 (npix, rowlen): bands bit-equal to ref (nb, npix); pad floats 0.0 (16-byte stores) or untouched."""
     raw = raw.reshape(-1, rowlen)
-    _bits_equal(np.ascontiguousarray(raw[:, :nb].T).view(np.float32), ref, what)
+    bits_equal(np.ascontiguousarray(raw[:, :nb].T).view(np.float32), ref, what)
     assert (raw[:, nb:] == (0 if pad_zero else SENT32)).all(), f"{what}: pad columns"
 
 
@@ -679,7 +606,7 @@ def test_bilinear_rows(torch_gpu, row):
     if olay == "planar":
         raw = raw.reshape(nb, npf + 5)
         assert (raw[:, npf:] == SENT32).all(), "stride gap written"
-        _bits_equal(raw[:, :npf].view(np.float32), ref, "planar")
+        bits_equal(raw[:, :npf].view(np.float32), ref, "planar")
     else:
         _check_rows_out(raw, nb, ref, ops, inst != UP_FF, olay)
     xb.get(np.uint8)
@@ -784,7 +711,7 @@ def test_tile_decode_rows(torch_gpu, row):
     ub, ob = Buf(torch, max(n, 1) * 2, ioff, u), Buf(torch, n * 4, ooff)
     _call(f"tile_decode_kernel {path}" if n else None, lib.hsr_tile_decode_u16, ub.ptr, n, 1e-4 if scale is None else scale,
           -1 if nd is None else nd, ob.ptr, _stream(torch))
-    _bits_equal(ob.get(np.float32), onp.tile_decode_u16(u, scale, nd), "decode")
+    bits_equal(ob.get(np.float32), onp.tile_decode_u16(u, scale, nd), "decode")
 
 
 # =============================================================================================================================
@@ -815,7 +742,7 @@ def test_interleave_to_bip_rows(torch_gpu, row):
           ob.ptr, odt, _stream(torch))
     got = ob.get(TO).reshape(want.shape)
     if TO is np.float32:
-        _bits_equal(got, want, "transpose")
+        bits_equal(got, want, "transpose")
     else:
         assert np.array_equal(got, want)
 
@@ -860,10 +787,24 @@ def test_sinkhorn_small_shapes(torch_gpu, ns, nt):
 
 
 # =============================================================================================================================
+# the guarded buffer itself
+# =============================================================================================================================
+def test_buf_get_notices_a_byte_written_on_either_side_of_the_payload(torch_gpu):
+    payload = np.arange(64, dtype=np.uint8)
+    buf = Buf(torch_gpu, 64, 4, payload)
+    assert np.array_equal(buf.get(np.uint8), payload)
+    for at in (buf.lo - 1, buf.lo + buf.nbytes):
+        buf = Buf(torch_gpu, 64, 4, payload)
+        buf.t[at] = 0
+        with pytest.raises(AssertionError, match="write outside the buffer"):
+            buf.get(np.uint8)
+
+
+# =============================================================================================================================
 # completeness
 # =============================================================================================================================
 def test_rows_reach_every_instance(torch_gpu):
     lib = _lib()
     table = {lib.hsr_aux_instance_name(i).decode() for i in range(lib.hsr_aux_instance_count())}
     assert len(table) == lib.hsr_aux_instance_count()
-    assert SEEN == table, (sorted(table - SEEN), sorted(SEEN - table))
+    assert LOG.seen == table, (sorted(table - LOG.seen), sorted(LOG.seen - table))

@@ -24,6 +24,7 @@ import warnings
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 from oracle import oracle_np as onp
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
@@ -33,15 +34,6 @@ warnings.simplefilter("ignore")
 MIN_COUNT = 5
 GEOMS = {"tail": (16, 64), "standalone": (3, 90)}
 _tiles = {}
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 def _table():

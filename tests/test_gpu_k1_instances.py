@@ -65,6 +65,7 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
@@ -344,15 +345,6 @@ POISON = 1.0e30                                           # the last tile's own 
 CASES = _cases()
 SEEN = set()
 FORMS_SEEN = set()                                        # (degree, variant, form) of every tail row that passed
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 def _record():

@@ -2,7 +2,7 @@
 csrc/hsr_chol.hip) against float64 / longdouble NumPy references.
 
 One case table per family.  The entry points are called through ctypes, so that pointers can be offset and leading
-dimensions padded: every output - work buffers at exactly their *_work_bytes included - is a `Buf` of test_gpu_aux_instances
+dimensions padded: every output - work buffers at exactly their *_work_bytes included - is a `Buf` of gpu_harness
 (sentinel fill between two 256-byte guard zones), and every byte a call does not own (guards, pad columns, stride gaps) must
 come back untouched.  After every call the launch record (hsr_k4_last_launch) must show the kernels the row names; the last test
 checks that the rows together reached every name hsr_k4_instance_name enumerates.  Inputs come from seeded generators; gaps of
@@ -28,62 +28,21 @@ import pytest
 
 from oracle import oracle_np as onp
 from conftest import load_golden
-from test_gpu_aux_instances import FILL, Buf, _bits_equal
+from gpu_harness import FILL, Buf, LaunchLog, bits_equal, same_bits, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib, stream as _stream
 from test_gpu_tile_pairs_shapes import ROWS, chol_instances, gram_kinds, sizes
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
 
-SEEN = set()
+LOG = LaunchLog("hsr_k4_last_launch")   # its checked calls take the record as the library joins it: "first; second"
+_call = LOG.call
 LD = np.longdouble
 U53, U52 = 2.0 ** -53, 2.0 ** -52
 WORST = {}                       # family -> largest observed error / bar (printed by the last test)
 
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
-
-
-def _lib():
-    from s2_emit import _native as nat
-    return nat.load()
-
-
-def _stream(torch):
-    from s2_emit import _engine as eng
-    return eng._stream(torch)
-
-
 def _note(family, value):
     WORST[family] = max(WORST.get(family, 0.0), float(value))
-
-
-def _call(expect, fn, *args):
-    """Run an entry point, check its return code and the kernels its launches were (in order)."""
-    lib = _lib()
-    lib.hsr_k4_last_launch(None, 0)
-    rc = fn(*args)
-    assert rc == 0, (rc, lib.hsr_last_error())
-    buf = C.create_string_buffer(256)
-    assert lib.hsr_k4_last_launch(buf, 256) == 1
-    got = buf.value.decode()
-    assert got == expect, (got, expect)
-    assert lib.hsr_k4_last_launch(buf, 256) == 0 and buf.value == b""          # cleared by the read
-    SEEN.update(got.split("; "))
-
-
-def _same_bits(got, ref, what):
-    got, ref = np.ascontiguousarray(got), np.ascontiguousarray(ref, dtype=got.dtype)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    iv = {4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
-    gn, rn = np.isnan(got), np.isnan(ref)
-    assert np.array_equal(gn, rn), f"{what}: NaN positions differ ({int(gn.sum())} vs {int(rn.sum())})"
-    bad = (got.view(iv) != ref.view(iv)) & ~gn
-    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first {got[bad][:4]} vs {ref[bad][:4]}"
 
 
 class Mat:
@@ -180,9 +139,9 @@ def test_stats_exact_integers(torch_gpu):
         sc_ref = np.sqrt(m2_ref / nn)
         sc_ref[sc_ref == 0.0] = 1.0
         what = f"n={n} n_in={n_in} {layout}"
-        _same_bits(stats, np.concatenate([[nn], m_ref, m2_ref]), what + " stats")
-        _same_bits(mean, m_ref, what + " mean")
-        _same_bits(scale, sc_ref, what + " scale")
+        same_bits(stats, np.concatenate([[nn], m_ref, m2_ref]), what + " stats")
+        same_bits(mean, m_ref, what + " mean")
+        same_bits(scale, sc_ref, what + " scale")
         if n_in >= 3:
             assert stats[2 * n_in] == 0.0 and scale[-1] == 1.0
 
@@ -279,7 +238,7 @@ def test_expand(torch_gpu, n_in, degree):
                     got = P.get()
                     what = f"n={n} {layout} ncols={ncols} ldp={ldp}"
                     assert (got[:, 0].view(np.uint64) == np.float64(1.0).view(np.uint64)).all(), what
-                    _same_bits(got[:, 1:nf + 1], ref, what)
+                    same_bits(got[:, 1:nf + 1], ref, what)
                     assert (got[:, nf + 1:].view(np.uint64) == 0).all(), what + ": pad columns"
 
 
@@ -317,7 +276,7 @@ def test_pair_expand(torch_gpu, n_in, degree, T):
             assert (got[p][~ok].view(np.uint64) == 0).all(), what + ": masked-out rows"
             g = got[p][ok]
             assert (g[:, 0] == 1.0).all() and (g[:, nf + 1:na].view(np.uint64) == 0).all() and (g[:, na + T:].view(np.uint64) == 0).all()
-            _same_bits(g[:, 1:nf + 1], _monomials(X[p].T[ok], mean[p], scale[p], n_in, degree), what)
+            same_bits(g[:, 1:nf + 1], _monomials(X[p].T[ok], mean[p], scale[p], n_in, degree), what)
             u = np.clip(Y[p].T[ok].astype(np.float64), eps, 1 - eps)
             ref = np.log(u / (1 - u))
             ulp = np.abs(g[:, na:na + T] - ref) / np.spacing(np.abs(ref))
@@ -328,7 +287,7 @@ def test_pair_expand(torch_gpu, n_in, degree, T):
             off = lambda b, stride, size: C.c_void_p(b.ptr.value + p * stride * size)
             _call("pair_expand_f64_kernel", lib.hsr_pair_expand_f64, off(xb, px, 4), 0, off(md, pms, 8), off(sd, pms, 8), 0,
                   off(yb, py, 4), 0, off(mb, pm, 1), 0, npix, n_in, degree, T, eps, Q1.ptr, ldq, 0, na, 1, _stream(torch))
-            _same_bits(Q1.get(), got[p], what + " alone")
+            same_bits(Q1.get(), got[p], what + " alone")
 
 
 # =============================================================================================================================
@@ -402,13 +361,13 @@ def test_gram(torch_gpu, na, nb):
                     want, bnd = ref[:, perm], None if bound is None else bound[:, perm]
                 what = f"({na}, {nb}) n={n} {kind} {name}"
                 if bnd is None:
-                    _same_bits(got, want, what)
+                    same_bits(got, want, what)
                 else:
                     err = np.abs(got.astype(LD) - want)
                     _note("gram (2 n 2^-53 |A|^T |B|)", np.max(err / bnd))
                     assert (err <= bnd).all(), (what, float(np.max(err / bnd)))
                 if same:
-                    _same_bits(got[:, :na], got[:, :na].T.copy(), what + ": symmetric square part")
+                    same_bits(got[:, :na], got[:, :na].T.copy(), what + ": symmetric square part")
     # the record's capacity: truncated, NUL-terminated, and cleared all the same
     lib = _lib()
     Q = _gram_data(rng, 9, nb, "normal")
@@ -446,7 +405,7 @@ def test_gram_batched(torch_gpu, na, nb):
             got = Cd.get().reshape(P, na, ldc)
             assert (np.ascontiguousarray(got[:, :, nb:]).view(np.uint8) == FILL).all()
             for p in range(P):
-                _same_bits(got[p][:, :nb], _gram_call(torch, expect, Q[p], na, Q[p], nb, n, True, 2, 0), f"n={n} P={P} pair {p}")
+                same_bits(got[p][:, :nb], _gram_call(torch, expect, Q[p], na, Q[p], nb, n, True, 2, 0), f"n={n} P={P} pair {p}")
 
 
 @pytest.mark.parametrize("shape", sorted({(r.nb, r.degree, r.T) for r in ROWS}))
@@ -540,8 +499,8 @@ def test_assemble_finish(torch_gpu, n_in, degree, T):
         _call("ridge_assemble_kernel", lib.hsr_ridge_assemble, Gd.ptr, ldg, na, nf, T, alpha, Ad.ptr, npad, Bd.ptr, ldb, info.ptr, st)
         A_ref, B_ref = _assemble_ref(G, na, nf, T, alpha, npad)
         A, B = Ad.get(np.float64).reshape(npad, npad), Bd.get()
-        _same_bits(A, A_ref, f"A pair {p}")
-        _same_bits(B, B_ref, f"B pair {p}")
+        same_bits(A, A_ref, f"A pair {p}")
+        same_bits(B, B_ref, f"B pair {p}")
         assert (A[nf:, nf:] == np.eye(npad - nf)).all() and (A[nf:, :nf] == 0).all() and (B[nf:].view(np.uint64) == 0).all()
         assert info.get(np.int32)[0] == 0
         Wd = Mat(torch, nf, T, ldw, np.float64, off=8, data=Ws[p], gap=np.nan)
@@ -554,7 +513,7 @@ def test_assemble_finish(torch_gpu, n_in, degree, T):
         got[2] = got[2].reshape(kpad, T)
         ref = _finish_ref(G, na, nf, T, Ws[p], means[p], scales[p], kpad)
         for g, r, name in zip(got, ref, ("b64", "b32", "W32", "mean32", "inv32")):
-            _same_bits(g, r, f"{name} pair {p}")
+            same_bits(g, r, f"{name} pair {p}")
         single.append((A, B, got))
     # batched: pair 1 has no training row; pair 2's Cholesky word is set
     pg, pa, pb = na * ldg + 4, npad * npad + 6, npad * ldb + 2
@@ -566,8 +525,8 @@ def test_assemble_finish(torch_gpu, n_in, degree, T):
     assert (info.get(np.int32) == 0).all()
     assert (np.ascontiguousarray(B[:, :, T:]).view(np.uint8) == FILL).all()
     for k, p in enumerate((0, 2)):
-        _same_bits(A[p], single[k][0], f"batched A pair {p}")
-        _same_bits(B[p][:, :T], single[k][1], f"batched B pair {p}")
+        same_bits(A[p], single[k][0], f"batched A pair {p}")
+        same_bits(B[p][:, :T], single[k][1], f"batched B pair {p}")
     assert (A[1] == np.eye(npad)).all() and (B[1][:, :T].view(np.uint64) == 0).all()
     pw, pms, pbo, pw32, pmi = nf * ldw + 2, n_in + 1, T + 3, kpad * T + 5, n_in + 2
     wrows = np.full((P, nf, ldw), np.nan)
@@ -583,14 +542,14 @@ def test_assemble_finish(torch_gpu, n_in, degree, T):
     assert list(status.get(np.int32)) == [0, 1, 2]
     b64h, b32h, W32h, m32h, i32h = b64.get(), b32.get(), W32.get().reshape(P, kpad, T), m32.get(), i32.get()
     for g, r, name in zip((b64h[0], b32h[0], W32h[0], m32h[0], i32h[0]), single[0][2], ("b64", "b32", "W32", "mean32", "inv32")):
-        _same_bits(g, r, f"batched {name} pair 0")
+        same_bits(g, r, f"batched {name} pair 0")
     for p in (1, 2):
         assert np.isnan(b64h[p]).all() and np.isnan(b32h[p]).all(), p
-        _same_bits(W32h[p][:nf], Ws[p].astype(np.float32), f"W32 pair {p}")
+        same_bits(W32h[p][:nf], Ws[p].astype(np.float32), f"W32 pair {p}")
         assert (W32h[p][nf:].view(np.uint32) == 0).all()
-        _same_bits(m32h[p], means[p].astype(np.float32), f"mean32 pair {p}")
-        _same_bits(i32h[p], (1.0 / scales[p]).astype(np.float32), f"inv32 pair {p}")
-    _same_bits(W32h[2], single[1][2][2], "batched W32 pair 2")
+        same_bits(m32h[p], means[p].astype(np.float32), f"mean32 pair {p}")
+        same_bits(i32h[p], (1.0 / scales[p]).astype(np.float32), f"inv32 pair {p}")
+    same_bits(W32h[2], single[1][2][2], "batched W32 pair 2")
 
 
 # =============================================================================================================================
@@ -668,7 +627,7 @@ def test_chol(torch_gpu, n):
                     _note("chol factor vs numpy (rtol 1e-10 / atol 1e-12)", np.max(np.abs(L - ref) / (1e-12 + 1e-10 * np.abs(ref))))
                     np.testing.assert_allclose(L, ref, rtol=1e-10, atol=1e-12, err_msg=what)
             else:
-                _same_bits(L, L0, what + ": factor")
+                same_bits(L, L0, what + ": factor")
             Xl = X.astype(LD)
             r2 = np.abs(Al @ Xl - Bm.astype(LD)).sum(axis=0).max() / (n * anorm * np.abs(Xl).sum(axis=0).max() * U52)
             _note(f"chol solve ratio, {kind} (<= 1)", r2)
@@ -715,8 +674,8 @@ def test_chol_bad_pivot(torch_gpu, n, pivots):
             assert np.isnan(Ag[p][:, n:]).all() and np.isnan(Bg[p][:, nrhs:]).all()
             assert np.isnan(Ag[p][:, :n][keep]).all()
         for i, p in enumerate((0, 2)):
-            _same_bits(np.tril(Ag[p][:, :n]), singles[i][0], f"n={n} bad pivot {kp}: factor of pair {p}")
-            _same_bits(Bg[p][:, :nrhs], singles[i][1], f"n={n} bad pivot {kp}: solution of pair {p}")
+            same_bits(np.tril(Ag[p][:, :n]), singles[i][0], f"n={n} bad pivot {kp}: factor of pair {p}")
+            same_bits(Bg[p][:, :nrhs], singles[i][1], f"n={n} bad pivot {kp}: solution of pair {p}")
 
 
 # =============================================================================================================================
@@ -829,11 +788,11 @@ def test_predict(torch_gpu, shape, slot):
                 base.append(got)
             p = i % P
             odd = Mat(torch, npix, n_in, even + 1, np.float32, data=X[p], gap=np.nan)
-            _bits_equal(run(_predict_name(slot, "scalar"), entry, odd, even + 1, 1, p), base[p], "odd pitch")
+            bits_equal(run(_predict_name(slot, "scalar"), entry, odd, even + 1, 1, p), base[p], "odd pitch")
             off4 = Mat(torch, npix, n_in, even, np.float32, off=4, data=X[p], gap=np.nan)
-            _bits_equal(run(_predict_name(slot, "scalar"), entry, off4, even, 1, p), base[p], "base off by 4 bytes")
+            bits_equal(run(_predict_name(slot, "scalar"), entry, off4, even, 1, p), base[p], "base off by 4 bytes")
             bands = Mat(torch, n_in, npix, npix + 3, np.float32, data=X[p].T, gap=np.nan)
-            _bits_equal(run(_predict_name(slot, "scalar"), entry, bands, 1, npix + 3, p), base[p], "band-major")
+            bits_equal(run(_predict_name(slot, "scalar"), entry, bands, 1, npix + 3, p), base[p], "band-major")
             # batched, odd pair stride: pair 1 starts 4 bytes off an 8-byte boundary
             pair_x = npix * even + 1
             rows = np.full((P, npix, even), np.nan, np.float32)
@@ -846,7 +805,7 @@ def test_predict(torch_gpu, shape, slot):
             got = out.get().reshape(P, T, ostride)
             assert (np.ascontiguousarray(got[:, :, npix:]).view(np.uint8) == FILL).all()
             for q in range(P):
-                _bits_equal(got[q][:, :npix], base[q], f"batched pair {q}")
+                bits_equal(got[q][:, :npix], base[q], f"batched pair {q}")
 
 
 # =============================================================================================================================
@@ -898,14 +857,14 @@ def test_single_fit_status(torch_gpu):
     m32, i32 = torch.empty(10, dtype=torch.float32, device="cuda"), torch.empty(10, dtype=torch.float32, device="cuda")
     assert lib.hsr_ridge_finish(_ptr(G), d.na, d.nf, 6, _ptr(Bp), 6, _ptr(mean), _ptr(scale), 10, d.kpad, _ptr(b), _ptr(b32), _ptr(Wf),
                                 _ptr(m32), _ptr(i32), st) == 0
-    _same_bits(m.intercept_, b.cpu().numpy(), "intercept_")
-    _same_bits(m.coef_, Bp[:d.nf].t().contiguous().cpu().numpy(), "coef_")
+    same_bits(m.intercept_, b.cpu().numpy(), "intercept_")
+    same_bits(m.coef_, Bp[:d.nf].t().contiguous().cpu().numpy(), "coef_")
     for name, t in (("W", Wf), ("b", b32), ("mean", m32), ("inv", i32)):
-        _bits_equal(m._dev[name].cpu().numpy(), t.cpu().numpy(), name)
+        bits_equal(m._dev[name].cpu().numpy(), t.cpu().numpy(), name)
     old = s2_emit.PolyRidge(degree=3, alpha=1.0)
     old.n_in, old.n_feat, old.n_targets, old._dev = 10, d.nf, 6, dict(W=Wf, b=b32, mean=m32, inv=i32)
     Xte = g["Xtest"].reshape(-1, 10).astype(np.float32)
-    _bits_equal(m.predict(Xte), old.predict(Xte), "predictions")
+    bits_equal(m.predict(Xte), old.predict(Xte), "predictions")
     np.testing.assert_allclose(m.predict(Xte), g["pred_logit"], rtol=0, atol=2e-4)
 
 
@@ -917,5 +876,5 @@ def test_rows_reach_every_k4_instance():
     assert len(table) == lib.hsr_k4_instance_count()
     for k in sorted(WORST):
         print(f"largest error / bar: {k}: {WORST[k]:.3e}")
-    assert SEEN <= table, SEEN - table
-    assert table <= SEEN, f"instances no row reached: {sorted(table - SEEN)}"
+    assert LOG.seen <= table, LOG.seen - table
+    assert table <= LOG.seen, f"instances no row reached: {sorted(table - LOG.seen)}"

@@ -24,6 +24,7 @@ import warnings
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 import match_pair_cases as mpc
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(180)]
@@ -35,15 +36,6 @@ KEYS = ("coeffs", "emit_rgb_matched_60m", "s2_rgb_60m_n", "valid60", "emit_rgb_1
 LIMIT_REL = 2e-6        # of max |plane|: the K1 bar
 CURVE_ATOL = 2e-6
 IMAGE_ATOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 def _host(res):

@@ -2,7 +2,7 @@
 the three pooling kernels - on an MI355X, row by row of the tables of tests/pair_cases.py, against the references stated there.
 
 The entry points are called through ctypes.  Inputs and outputs lie in buffers filled with a sentinel byte between two guard
-zones (Buf of test_gpu_aux_instances.py), pairs `stride` elements apart with sentinel gaps: what a call does not own must come
+zones (Buf of gpu_harness.py), pairs `stride` elements apart with sentinel gaps: what a call does not own must come
 back untouched.  After every call the library's launch record (hsr_pairs_last_launch) is read and compared with the sequence the
 row names; a second launch must give identical bits; and a pair's outputs must carry the same bits alone and at every position of
 a batch of 3 (_positions).  The last test checks that the rows reached every name hsr_pairs_instance_name enumerates and prints
@@ -14,55 +14,18 @@ import numpy as np
 import pytest
 
 import pair_cases as pc
-from test_gpu_aux_instances import FILL, Buf, _bits_equal
+from gpu_harness import FILL, Buf, LaunchLog, bits_equal, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib, stream as _stream
 from test_gpu_tile_pairs_pool import SMALL, small  # noqa: F401  (the fixture of the driver test)
 from test_gpu_tile_pairs_validate import ANGLE_ATOL
 
 pytestmark = pytest.mark.gpu
 
-SEEN = set()
+LOG = LaunchLog("hsr_pairs_last_launch", joined=True)
+_call, _record = LOG.call, LOG.read
 WORST = {}                       # bar -> largest error seen under it
 ORDERS = ((0, 1, 2), (1, 2, 0), (2, 0, 1), (0,), (1,), (2,))
 F32, F64, I64, I32, U8 = np.float32, np.float64, np.int64, np.int32, np.uint8
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
-
-
-def _lib():
-    from s2_emit import _native as nat
-    return nat.load()
-
-
-def _stream(torch):
-    from s2_emit import _engine as eng
-    return eng._stream(torch)
-
-
-def _record():
-    buf = C.create_string_buffer(2048)
-    return buf.value.decode().split("; ") if _lib().hsr_pairs_last_launch(buf, 2048) == 1 else None
-
-
-def _call(expect, fn, *args):
-    """Run an entry point and check its return code and the launch record: exactly `expect`, or a refusal with no launch."""
-    lib = _lib()
-    lib.hsr_pairs_last_launch(None, 0)
-    rc = fn(*args)
-    got = _record()
-    if expect is None:
-        assert rc != 0 and got is None and lib.hsr_last_error(), (rc, got)
-        return
-    assert rc == 0, (rc, lib.hsr_last_error())
-    assert got == expect, (got, expect)
-    assert _record() is None                                 # cleared when read
-    SEEN.update(got)
 
 
 def _same(a, b):
@@ -148,7 +111,7 @@ def test_record_lists_launches_in_order_and_keeps_the_last_32(torch_gpu):
 # =============================================================================================================================
 # prep
 # =============================================================================================================================
-def _prep_call(torch, row, order, expect=pc.PREP_SEQ, **over):
+def _prep_call(torch, row, order, refused=False, **over):
     r, n, o = row, len(order), list(order)
     emit, s2 = pc.prep_inputs(r)
     eb, eimg = _in(torch, [emit[i] for i in o], r.pair_emit)
@@ -158,7 +121,8 @@ def _prep_call(torch, row, order, expect=pc.PREP_SEQ, **over):
     xb, yb, mb = Buf(torch, n * r.nb * r.npix * 4, 4), Buf(torch, n * r.T * r.npix * 4, 12), Buf(torch, n * r.npix, 1)
     a = dict(edt=r.edt, pair_emit=r.pair_emit, T=r.T, sdt=r.sdt, pair_s2=r.pair_s2, nb=r.nb, f=r.f, P=n)
     a.update(over)
-    _call(expect, _lib().hsr_pair_prep, eb.ptr, pc.DT_CODE[a["edt"]], a["pair_emit"], r.B, bb.ptr, a["T"], sb.ptr, pc.DT_CODE[a["sdt"]],
+    check = LOG.refused if refused else lambda *call: _call(pc.PREP_SEQ, *call)
+    check(_lib().hsr_pair_prep, eb.ptr, pc.DT_CODE[a["edt"]], a["pair_emit"], r.B, bb.ptr, a["T"], sb.ptr, pc.DT_CODE[a["sdt"]],
           a["pair_s2"], a["nb"], r.H, r.W, a["f"], 0.0 if r.end is None else r.end, int(r.end is not None),
           0.0 if r.snd is None else r.snd, int(r.snd is not None), xb.ptr, yb.ptr, mb.ptr, a["P"], _stream(torch))
     out = dict(x=xb.get(F32).reshape(n, r.nb, r.npix), y=yb.get(F32).reshape(n, r.T, r.npix), mask=mb.get(U8).reshape(n, r.npix))
@@ -175,14 +139,14 @@ def test_prep(torch_gpu, row):
     emit, s2 = pc.prep_inputs(row)
     for p in range(pc.P):
         x, y, mask = pc.prep_reference(row, emit[p], s2[p])
-        _bits_equal(base["x"][p], x, f"x of pair {p}")
-        _bits_equal(base["y"][p], y, f"y of pair {p}")
+        bits_equal(base["x"][p], x, f"x of pair {p}")
+        bits_equal(base["y"][p], y, f"y of pair {p}")
         np.testing.assert_array_equal(base["mask"][p], mask, err_msg=f"mask of pair {p}")
 
 
 @pytest.mark.parametrize("case", pc.PREP_REFUSED, ids=lambda c: c[0])
 def test_prep_refusals_launch_nothing(torch_gpu, case):
-    out = _prep_call(torch_gpu, pc.PREP_REFUSED_BASE, (0, 1, 2), expect=None, **case[1])
+    out = _prep_call(torch_gpu, pc.PREP_REFUSED_BASE, (0, 1, 2), refused=True, **case[1])
     for k, v in out.items():
         assert (v.view(U8) == FILL).all(), k
 
@@ -611,7 +575,7 @@ def test_driver_records_what_pairs_py_launches(torch_gpu, small, side):
         got = _record()
         assert got == pc.DRIVER_RECORDS[name], (name, got)
         assert (out.status.cpu().numpy() == 0).all(), name
-        SEEN.update(got)
+        LOG.seen.update(got)
 
 
 # =============================================================================================================================
@@ -621,6 +585,6 @@ def test_rows_reached_every_instance():
     lib = _lib()
     table = [lib.hsr_pairs_instance_name(i).decode() for i in range(lib.hsr_pairs_instance_count())]
     assert table == list(pc.NAMES) and len(set(table)) == pc.INSTANCE_COUNT
-    assert SEEN == set(table), sorted(set(table) - SEEN)
+    assert LOG.seen == set(table), sorted(set(table) - LOG.seen)
     for key in sorted(WORST):
         print(f"largest error / bound under [{key}]: {WORST[key]:.3e}")

@@ -15,20 +15,12 @@ import numpy as np
 import pytest
 
 from conftest import load_golden, unpack_srf
+from gpu_harness import torch_gpu  # noqa: F401
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
 
 warnings.simplefilter("ignore")
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()                                 # fail loudly if the extension is missing
-    return torch
 
 
 def _rel_err(got, ref):

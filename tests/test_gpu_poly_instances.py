@@ -20,11 +20,14 @@ import warnings
 import numpy as np
 import pytest
 
+from gpu_harness import LaunchLog, bits_equal, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib
 from oracle import oracle_np as onp
 
 pytestmark = pytest.mark.gpu
 
-SEEN = set()
+LOG = LaunchLog("hsr_poly_last_launch")
+_call = LOG.call
 ALL_INSTANCES = (
     {f"apply_rows_kernel<{q}, {n}, {b}>" for q in range(1, 5) for n in range(1, 6) for b in ("false", "true")}
     | {f"apply_rows_lds_kernel<{q}>" for q in range(1, 5)}
@@ -36,46 +39,8 @@ ALL_INSTANCES = (
 assert len(ALL_INSTANCES) == 62
 
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
-
-
-def _lib():
-    from s2_emit import _native as nat
-    return nat.load()
-
-
-def _record():
-    buf = C.create_string_buffer(96)
-    return buf.value.decode() if _lib().hsr_poly_last_launch(buf, 96) == 1 else None
-
-
-def _call(expect, fn, *args):
-    """Run an entry point, check its return code and the instance it launched."""
-    _lib().hsr_poly_last_launch(None, 0)
-    rc = fn(*args)
-    assert rc == 0, (rc, _lib().hsr_last_error())
-    got = _record()
-    assert got == expect, (got, expect)
-    SEEN.add(got)
-
-
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _bits_equal(got, ref, what):
-    got, ref = np.asarray(got, np.float32), np.asarray(ref, np.float32)
-    assert got.shape == ref.shape, what
-    gn, rn = np.isnan(got), np.isnan(ref)
-    assert np.array_equal(gn, rn), f"{what}: NaN positions differ"
-    bad = got.view(np.uint32)[~gn] != ref.view(np.uint32)[~rn]
-    assert not bad.any(), f"{what}: {int(bad.sum())} elements differ, first {got[~gn][bad][:4]} vs {ref[~rn][bad][:4]}"
 
 
 # ---- float64 references ------------------------------------------------------------------------------------------------------
@@ -151,9 +116,9 @@ def _apply_rows_case(torch, rng, nb, row, deg, npix, expect, *, use_coeffs=True,
     torch.cuda.synchronize()
     got = od.cpu().numpy().reshape(npix, out_row)
     ref = _apply_ref(x[:, :nb], c, lohi, mask, clip)
-    _bits_equal(got[:, :nb], ref, f"{expect} nb={nb} deg={deg} npix={npix}")
+    bits_equal(got[:, :nb], ref, f"{expect} nb={nb} deg={deg} npix={npix}")
     if out_row == row and expect.startswith("apply_rows"):
-        _bits_equal(got[:, nb:], x[:, nb:], f"{expect}: pad columns pass through")
+        bits_equal(got[:, nb:], x[:, nb:], f"{expect}: pad columns pass through")
     else:                                                            # scalar / planar paths write the band columns only
         assert (got[:, nb:] == sentinel).all(), f"{expect}: pad columns written"
     rest = ob.cpu().numpy()
@@ -176,7 +141,7 @@ def _apply_planar_case(torch, rng, nb, deg, npix, plane, expect, *, mask_offset=
     torch.cuda.synchronize()
     got = od.cpu().numpy().reshape(nb, plane)
     ref = _apply_ref(np.ascontiguousarray(x[:, :npix].T), c, lohi, mask if use_mask else None, clip).T
-    _bits_equal(got[:, :npix], ref, f"{expect} nb={nb} npix={npix} plane={plane}")
+    bits_equal(got[:, :npix], ref, f"{expect} nb={nb} npix={npix} plane={plane}")
     assert (got[:, npix:] == -5.0).all()
 
 
@@ -203,8 +168,8 @@ def _apply_batch_case(torch, rng, nb, deg, sizes, use_mask, expect, clip=True):
     for i, n in enumerate(sizes):
         got = ods[i].cpu().numpy().reshape(n + slack, row)
         ref = _apply_ref(xs[i][:, :nb], c[0 if shared else i], None, masks[i] if use_mask & 1 else None, clip)
-        _bits_equal(got[:n, :nb], ref, f"{expect} tile {i} npix={n} use_mask={use_mask}")
-        _bits_equal(got[:n, nb:], xs[i][:, nb:], f"{expect} tile {i}: pad columns")
+        bits_equal(got[:n, :nb], ref, f"{expect} tile {i} npix={n} use_mask={use_mask}")
+        bits_equal(got[:n, nb:], xs[i][:, nb:], f"{expect} tile {i}: pad columns")
         assert (got[n:] == -9.0).all(), f"{expect} tile {i}: rows past npix written"
 
 
@@ -277,8 +242,8 @@ def test_apply_rows_grid_stride_branch(torch_gpu):
     _call("apply_rows_kernel<1, 3, false>", _lib().hsr_poly_apply, _p(xd), 1, 4, None, _p(cd), 1, 2, npix, None, 1, _p(od), 1, 4, None)
     torch.cuda.synchronize()
     got = od.cpu().numpy().reshape(npix, 4)
-    _bits_equal(got[:, 0], _apply_ref(x[:, :1], c, None, None, True)[:, 0], "grid-stride apply")
-    _bits_equal(got[:, 1:], x[:, 1:], "grid-stride pad columns")
+    bits_equal(got[:, 0], _apply_ref(x[:, :1], c, None, None, True)[:, 0], "grid-stride apply")
+    bits_equal(got[:, 1:], x[:, 1:], "grid-stride pad columns")
 
 
 def _tie_probe(rng):
@@ -347,7 +312,7 @@ def test_apply_horner_is_not_contracted(torch_gpu, kind, q, n):
               _p(cd), nb, n - 1, npix, None, 0, _p(od), plane, 1, None)
         torch.cuda.synchronize()
         got = od.cpu().numpy().reshape(nb, plane)[:, :npix].T
-    _bits_equal(got, ref, f"{kind} Q={q} N={n}: Horner contracted")
+    bits_equal(got, ref, f"{kind} Q={q} N={n}: Horner contracted")
 
 
 # ---- moments ----------------------------------------------------------------------------------------------------------------
@@ -644,6 +609,6 @@ def test_valid_mask_kernel(torch_gpu, nbx, row, pos, ylay, min_in, npix):
 
 def test_poly_case_table_reaches_every_instance(torch_gpu):
     """Runs last in this module: the rows above reached all 62 instances."""
-    missing = ALL_INSTANCES - SEEN
+    missing = ALL_INSTANCES - LOG.seen
     assert not missing, sorted(missing)
-    assert SEEN <= ALL_INSTANCES, sorted(SEEN - ALL_INSTANCES)
+    assert LOG.seen <= ALL_INSTANCES, sorted(LOG.seen - ALL_INSTANCES)

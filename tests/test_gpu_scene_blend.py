@@ -4,20 +4,12 @@ the seam it is there to remove, and fuse_scene with a stride against the chain o
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 from test_scene_blend_host import blend_ref64, check_blend
 
 pytestmark = pytest.mark.gpu
 
 T = 3
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 def _bits(a):

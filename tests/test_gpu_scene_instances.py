@@ -2,59 +2,26 @@
 MI355X, row by row of the tables of tests/scene_cases.py, against the references stated there.
 
 The entry points are called through ctypes.  Every output lies `off` bytes past a 256-byte boundary in a buffer filled with a
-sentinel byte, between two guard zones (Buf of test_gpu_aux_instances.py): what a call does not own must come back untouched.
+sentinel byte, between two guard zones (Buf of gpu_harness.py): what a call does not own must come back untouched.
 After every call the library's launch record (hsr_scene_last_launch) is read and compared with the instance the row expects, a
 name computed by scene_cases' mirror of the selection rules.  Every comparison is exact - integers or bits - except the blend's
 pixels under two or more values, which are held to the derived bound (K + 2) 2^-24 sum w |v| / sum w (check_blend).  The last
 test checks that the rows reached every name hsr_scene_instance_name enumerates.  What the rows claim about themselves (which
 pixels count, which loops make a second trip, ...) is checked without a GPU in test_scene_instances_host.py."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import scene_cases as sc
-from test_gpu_aux_instances import FILL, SENT32, Buf
+from gpu_harness import FILL, SENT16, SENT32, Buf, LaunchLog, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib, stream as _stream
 from test_scene_blend_host import check_blend
 
 pytestmark = pytest.mark.gpu
 
-SEEN = set()
+LOG = LaunchLog("hsr_scene_last_launch")
+_call = LOG.call
 WORST = {}                       # K -> largest blend error over its bound
 F32, U16 = sc.F32, sc.U16
-SENT16 = np.frombuffer(bytes([FILL] * 2), np.uint16)[0]
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
-
-
-def _lib():
-    from s2_emit import _native as nat
-    return nat.load()
-
-
-def _stream(torch):
-    from s2_emit import _engine as eng
-    return eng._stream(torch)
-
-
-def _call(expect, fn, *args):
-    """Run an entry point, check its return code and that the launch record names the expected instance."""
-    lib = _lib()
-    lib.hsr_scene_last_launch(None, 0)
-    rc = fn(*args)
-    assert rc == 0, (rc, lib.hsr_last_error())
-    buf = C.create_string_buffer(96)
-    got = buf.value.decode() if lib.hsr_scene_last_launch(buf, 96) == 1 else None
-    assert got == expect, (got, expect)
-    assert lib.hsr_scene_last_launch(buf, 96) == 0 and buf.value == b""          # cleared when read
-    SEEN.add(got)
 
 
 def _bits(a):
@@ -275,6 +242,6 @@ def test_rows_reach_every_instance(torch_gpu):
     assert lib.hsr_scene_instance_count() == 20
     table = {lib.hsr_scene_instance_name(i).decode() for i in range(20)}
     assert len(table) == 20
-    assert SEEN == table, (sorted(table - SEEN), sorted(SEEN - table))
-    print("scene instances seen: %d of %d" % (len(SEEN & table), len(table)))
+    assert LOG.seen == table, (sorted(table - LOG.seen), sorted(LOG.seen - table))
+    print("scene instances seen: %d of %d" % (len(LOG.seen & table), len(table)))
     print("blend: largest error / bound per K: " + ", ".join(f"K={k}: {WORST[k]:.3f}" for k in sorted(WORST)))

@@ -6,19 +6,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_harness import torch_gpu  # noqa: F401
 from scene_cases import assemble as _assemble            # hsr_scene_mosaic in NumPy, shared with the instance tests
 from test_scene_tiles_host import SCALE, TILE, black_rule, g15_mask, g15_settings, window_counts
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 @pytest.fixture(scope="module")

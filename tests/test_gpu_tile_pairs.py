@@ -5,18 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_harness import torch_gpu  # noqa: F401
 from test_tile_pairs_host import block_mean_rule, decode_u16, g12_inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 @pytest.fixture(scope="module")

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_harness import torch_gpu  # noqa: F401
 from test_gpu_tile_pairs_report import _check_close
 from test_gpu_tile_pairs_validate import _check_view, _dev_u16, _groups, _same_bits
 from test_tile_pairs_host import decode_u16, g12_inputs
@@ -17,15 +18,6 @@ from test_tile_pairs_validate_host import validation_reference
 pytestmark = pytest.mark.gpu
 
 FIT_KEYS = ("mean", "scale", "Bp", "b64", "W32", "b32", "mean32", "inv32")
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 @pytest.fixture(scope="module")

@@ -6,19 +6,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_harness import torch_gpu  # noqa: F401
 from test_tile_pairs_host import decode_u16, g12_inputs
 from test_tile_pairs_report_host import report_reference
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 @pytest.fixture(scope="module")

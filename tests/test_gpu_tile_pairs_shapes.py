@@ -32,19 +32,11 @@ from typing import Optional, Tuple
 import numpy as np
 import pytest
 
+from gpu_harness import torch_gpu  # noqa: F401
 from oracle import oracle_np as onp
 from test_tile_pairs_report_host import report_reference
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_harness import torch_gpu  # noqa: F401
 from test_tile_pairs_host import block_mean_rule, decode_u16, g12_inputs
 from test_tile_pairs_report_host import report_reference
 from test_tile_pairs_validate_host import checkerboard_mask, validation_reference
@@ -18,15 +19,6 @@ pytestmark = pytest.mark.gpu
 FIELDS = ("pred_coarse", "cube_coarse", "n", "rmse", "r2", "mean_ref", "sam", "n_sam", "ergas", "sam_map")
 FIT_KEYS = ("mean", "scale", "Bp", "b64", "W32", "b32", "mean32", "inv32")
 ANGLE_ATOL = 5e-6          # degrees: a cosine within a few ulp of 1 moves acos by up to sqrt(2 * 4 * 2^-53) rad = 1.7e-6 deg; x 3
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    from s2_emit import _native as nat
-    nat.load()
-    return torch
 
 
 @pytest.fixture(scope="module")
