@@ -95,9 +95,17 @@ enum PairsInstance : int {
   kPairsInstances
 };
 
+// Kernel instances of hsr_ortho.hip, the index of the name table behind hsr_ortho_last_launch / hsr_ortho_instance_name
+// (csrc/hsr_lib.hip): a table of its own, so the scene one keeps its 20 names.
+enum OrthoInstance : int {
+  kOrthoBip = 0,                           // + 2 * kMask + kVec
+  kOrthoBsq = kOrthoBip + 4,               // + kMask
+  kOrthoInstances = kOrthoBsq + 2
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs}_last_launch, csrc/hsr_lib.hip).
-enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs };
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

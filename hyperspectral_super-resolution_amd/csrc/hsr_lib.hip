@@ -82,7 +82,7 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// Launch records (hsr_{aux,scene,k4,pairs}_last_launch): per family and thread, the kernels launched successfully since the last
+// Launch records (hsr_{aux,scene,k4,pairs,ortho}_last_launch): per family and thread, the kernels launched successfully since the last
 // read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
 // the list is full.  Indices turn into names only when read.
 static const char* const kAuxNames[] = {
@@ -131,14 +131,19 @@ static const char* const kPairsNames[] = {
     "pair_score_partial_kernel<false>", "pair_score_partial_kernel<true>", "pair_score_finish_kernel",
     "pool_stats_kernel", "pool_gram_kernel<false>", "pool_gram_kernel<true>", "pool_models_kernel",
 };
+static const char* const kOrthoNames[] = {
+    "ortho_bip_kernel<false, false>", "ortho_bip_kernel<false, true>", "ortho_bip_kernel<true, false>", "ortho_bip_kernel<true, true>",
+    "ortho_bsq_kernel<false>", "ortho_bsq_kernel<true>",
+};
 template <int N>
 constexpr int length(const char* const (&)[N]) { return N; }
+static_assert(length(kOrthoNames) == kOrthoInstances, "kOrthoNames: one name per OrthoInstance");
 static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
 static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
 static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
 static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per PairsInstance");
 
-// Aux and scene entry points launch one kernel each, so their record keeps the last launch only; K4 and pairs entry points
+// Aux, scene and ortho entry points launch one kernel each, so their record keeps the last launch only; K4 and pairs entry points
 // launch up to two, and a caller may read after several calls.
 constexpr int kRecordCap = 32;
 struct Family {
@@ -152,12 +157,14 @@ static const Family kFamilies[] = {
     {kSceneNames, kSceneInstances, 1, "hsr_scene_instance_name"},  // kLaunchScene
     {kK4Names, kK4Instances, kRecordCap, "hsr_k4_instance_name"},  // kLaunchK4
     {kPairsNames, kPairsInstances, kRecordCap, "hsr_pairs_instance_name"},  // kLaunchPairs
+    {kOrthoNames, kOrthoInstances, 1, "hsr_ortho_instance_name"},  // kLaunchOrtho
 };
+static_assert(sizeof(kFamilies) / sizeof(kFamilies[0]) == kLaunchFamilies, "kFamilies: one row per LaunchFamily");
 struct Record {
   int seq[kRecordCap];
   int count;
 };
-static thread_local Record g_records[4];
+static thread_local Record g_records[kLaunchFamilies];
 
 static void record_append(LaunchFamily f, int instance) {
   Record& r = g_records[f];
@@ -215,6 +222,9 @@ extern "C" const char* hsr_k4_instance_name(int32_t i) { return hsr::instance_na
 extern "C" int hsr_pairs_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchPairs, names, capacity); }
 extern "C" int hsr_pairs_instance_count(void) { return hsr::kPairsInstances; }
 extern "C" const char* hsr_pairs_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchPairs, i); }
+extern "C" int hsr_ortho_last_launch(char* name, int32_t capacity) { return hsr::record_read(hsr::kLaunchOrtho, name, capacity); }
+extern "C" int hsr_ortho_instance_count(void) { return hsr::kOrthoInstances; }
+extern "C" const char* hsr_ortho_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchOrtho, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

@@ -19,6 +19,7 @@ from .ridge import PolyRidge, predict_cube_logit, flatten_pixels, subsample_band
 from .pairs import TilePairOutput, TilePairValidation, fuse_tile_pair, fuse_tile_pairs
 from .scenes import (Window, SceneOutput, scene_windows, select_tiles, find_valid_paired_tiles, extract_tile_pairs,
                      mosaic_tiles, fuse_scene)
+from .ortho import OrthoOutput, apply_glt, ortho_scene, glt_from_xy, quality_mask
 from ._native import HsrUnavailable, HsrError
 
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
@@ -34,5 +35,6 @@ _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
-          "Window", "SceneOutput"]
+          "Window", "SceneOutput",
+          "apply_glt", "ortho_scene", "glt_from_xy", "quality_mask", "OrthoOutput"]
 __all__ = _REFERENCE_SURFACE + _COPIED_BY_CALLERS + _FUSED

@@ -184,6 +184,8 @@ SIGNATURES = {
     "hsr_scene_gather_tiles": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _i32, _vp, _vp]),
     "hsr_scene_mosaic": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _i32, _vp]),
     "hsr_scene_mosaic_blend": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i32, _f32, _vp]),
+    "hsr_ortho_glt": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _i32,
+                                _vp, _vp, _vp]),
     "hsr_block_mean": (C.c_int, [_vp, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
     "hsr_bilinear_upsample_mask_hist": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -204,6 +206,9 @@ SIGNATURES = {
     "hsr_pairs_last_launch": (C.c_int, [C.c_char_p, _i32]),
     "hsr_pairs_instance_count": (C.c_int, []),
     "hsr_pairs_instance_name": (C.c_char_p, [_i32]),
+    "hsr_ortho_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_ortho_instance_count": (C.c_int, []),
+    "hsr_ortho_instance_name": (C.c_char_p, [_i32]),
     "hsr_step_plan_create": (C.c_int, [C.POINTER(StepDesc), C.POINTER(_vp)]),
     "hsr_step_plan_destroy": (None, [_vp]),
     "hsr_step_plan_slots": (C.c_int, [_vp]),

@@ -844,6 +844,42 @@ int hsr_scene_mosaic_blend(const float* cubes_dev, int32_t ncubes, int32_t T, in
                            const int32_t* start_dev, int32_t ny, int32_t nx, float* out_dev, int32_t H, int32_t W, float fill,
                            hsr_stream_t stream);
 
+/* ---- EMIT swath -> orthorectified scene: the GLT gather with masks (s2_emit.ortho; csrc/hsr_ortho.hip) ---------------------------
+ * What stands in front of the scene entries: an EMIT L2A granule is a swath (rows = downtrack, cols = crosstrack, bands) float32
+ * with a geometry lookup table glt (glt_h, glt_w, 2) int32 - per map cell the ONE-based swath column glt[.., 0] and row
+ * glt[.., 1], glt_nodata (0) = no data - a per-pixel quality mask and a bit-packed per-band mask.  The reference orthorectifies
+ * with NumPy: EMIT_data/emit_tools.py apply_glt (:153-181) under ortho_xr (:184-268), after emit_xarray (:115-119) has written
+ * -9999 into the swath where quality_mask (:271-298) == 1 or a bit of band_mask (:301-321) is set; EMIT_data/emit_proj.py
+ * nc_to_envi builds the same table (:683-687), drops the entries that leave the swath (:691-717) and gathers 32 bands at a time
+ * (:947-987).  hsr_ortho_glt replaces the fill, the index and the permute passes by ONE launch on the caller's stream that writes
+ * every output byte once (no memset of the output).  For output pixel (y, x) of the window [row0, row0 + out_h) x [col0, col0 +
+ * out_w) of the GLT grid, with xv = glt[row0 + y, col0 + x, 0] and yv = glt[row0 + y, col0 + x, 1]:
+ *   1. xv == glt_nodata or yv == glt_nodata: every band is `fill` (valid_glt of apply_glt :173).
+ *   2. otherwise sx = xv - 1, sy = yv - 1 in 64 bits (INT32_MIN cannot wrap); outside [0, cols) x [0, rows): every band is `fill`
+ *      and the pixel counts as dropped (nc_to_envi's rule; apply_glt alone would raise or wrap a negative index).  Such an entry
+ *      is never dereferenced.
+ *   3. otherwise band b is swath[sy, sx, b] with its bits - NaN payloads, -0.0, denormals, +-inf - except that it is `masked`
+ *      where qmask_dev is given and qmask[sy, sx] == 1 (exactly 1: 2 or 255 do not mask), or where bmask_dev is given and
+ *      (bmask[sy, sx, b >> 3] >> (7 - (b & 7))) & 1 is set (np.unpackbits' order; bits past `bands` are ignored; bmask_bytes >=
+ *      ceil(bands / 8) is the byte pitch of a pixel, 36 for EMIT's 285 bands).  `masked` is the -9999 literal of
+ *      emit_tools.py:117-119 as a parameter of its own, separate from `fill`.
+ * layout 0 (bip): out (out_h, out_w, bands), what apply_glt returns; layout 1 (bsq): out (bands, out_h, out_w), a scene as the
+ * scene entries take it; the same bits either way.  qmask_dev (rows, cols) uint8, bmask_dev (rows, cols, bmask_bytes) uint8 and
+ * dropped_dev may each be NULL.  dropped_dev (one int64) is zeroed by the call and receives integer adds, so the count does not
+ * depend on the order (the convention of hsr_scene_black_counts).  All byte offsets are 64-bit.
+ * Refused before any launch: NULL swath / glt / out, non-positive sizes, a window that leaves the GLT grid, bmask_dev with
+ * bmask_bytes < ceil(bands / 8), layout outside {0, 1} (HSR_ERR_INVALID); bands > 512 (the LDS tile of the bsq transposition: 64
+ * pixels x (bands | 1) floats), rows cols > 2^31 - 1, out_h out_w > 2^31 - 1 (HSR_ERR_UNSUPPORTED).
+ * A workgroup owns 64 consecutive pixels of an output row: their GLT entries are read once, 512 contiguous bytes; a spectrum is
+ * read as one contiguous run of `bands` floats by one wave - bands / 4 float4 and bands % 4 floats behind them - four (bsq: eight)
+ * spectra in flight per wave, and not at all for fill and quality-masked pixels.  The float4 are 16-byte aligned accesses when
+ * bands % 4 == 0 and both bases lie on 16 bytes (then every pixel base does; bip only) and dword-aligned ones otherwise: the
+ * same bits.  bsq transposes through LDS and stores 256-byte row segments per band. */
+int hsr_ortho_glt(const float* swath_dev, int32_t rows, int32_t cols, int32_t bands, const int32_t* glt_dev, int32_t glt_h,
+                  int32_t glt_w, int32_t glt_nodata, int32_t row0, int32_t col0, int32_t out_h, int32_t out_w,
+                  const uint8_t* qmask_dev, const uint8_t* bmask_dev, int32_t bmask_bytes, float fill, float masked,
+                  int32_t layout /* 0 bip, 1 bsq */, float* out_dev, int64_t* dropped_dev, hsr_stream_t stream);
+
 /* ---- diagnostics -------------------------------------------------------------------------------
  * Pure streaming read of `bytes` bytes (a multiple of 16, 16-byte aligned base): the measured HBM read ceiling of
  * the box, reported by bench.py beside the vendor peak.  mode 0: K1's own load shape - non-temporal LDS-DMA
@@ -930,6 +966,13 @@ const char* hsr_k4_instance_name(int32_t i);
 int hsr_pairs_last_launch(char* names, int32_t capacity);
 int hsr_pairs_instance_count(void);
 const char* hsr_pairs_instance_name(int32_t i);
+/* ortho (hsr_ortho_last_launch; hsr_ortho_instance_count = 6, hsr_ortho_instance_name; one slot): csrc/hsr_ortho.hip, a fifth
+ * family under the same contract with a table of its own (the four above keep 32 / 20 / 31 / 12).  hsr_ortho_glt launches one
+ * kernel: "ortho_bip_kernel<false, true>" (<kMask, kVec>: a quality or band mask is given; 16-byte aligned float4 - bands % 4 == 0
+ * and both bases on 16 bytes - instead of dword-aligned ones and a tail) or "ortho_bsq_kernel<true>" (<kMask>). */
+int hsr_ortho_last_launch(char* name, int32_t capacity);
+int hsr_ortho_instance_count(void);
+const char* hsr_ortho_instance_name(int32_t i);
 
 #ifdef __cplusplus
 }
