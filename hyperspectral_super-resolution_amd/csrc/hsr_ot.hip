@@ -46,11 +46,20 @@ struct OtWork {
 
 static size_t ot_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-static size_t ot_layout(int64_t n, int64_t m, OtWork* w, unsigned char* base) {
+// The regions of the workspace in the order they lie in it (the `which` of hsr_ot_work_region)
+enum { kOtRegState, kOtRegK, kOtRegPartial, kOtRegErrpart, kOtRegU0, kOtRegU1, kOtRegV0, kOtRegV1, kOtRegions };
+
+// region_off / region_bytes (optional, kOtRegions entries each): where every region starts and how many bytes of it are used
+static size_t ot_layout(int64_t n, int64_t m, OtWork* w, unsigned char* base, size_t* region_off = nullptr,
+                        size_t* region_bytes = nullptr) {
   const int32_t nchunks = (int32_t)((n + kOtRowsPerChunk - 1) / kOtRowsPerChunk);
   size_t off = 0;
+  int region = 0;
   auto take = [&](size_t bytes) {
     unsigned char* p = base ? base + off : nullptr;
+    if (region_off) region_off[region] = off;
+    if (region_bytes) region_bytes[region] = bytes;
+    ++region;
     off += ot_align(bytes);
     return p;
   };
@@ -283,6 +292,20 @@ extern "C" int64_t hsr_ot_work_bytes(int64_t n, int64_t m) {
   return (int64_t)hsr::ot_layout(n, m, nullptr, nullptr);
 }
 
+extern "C" int hsr_ot_work_region(int64_t n, int64_t m, int32_t which, int64_t* offset_bytes, int64_t* count) {
+  using namespace hsr;
+  HSR_REQUIRE(offset_bytes && count, HSR_ERR_INVALID, "hsr_ot_work_region: NULL output");
+  HSR_REQUIRE(which >= 0 && which < kOtRegions, HSR_ERR_INVALID, "hsr_ot_work_region: which=%d outside [0, %d]", (int)which,
+              kOtRegions - 1);
+  HSR_REQUIRE(n >= 1 && m >= 1 && n <= (1 << 20) && m <= (1 << 20), HSR_ERR_UNSUPPORTED,
+              "hsr_ot_work_region: n=%lld m=%lld outside [1, 2^20]", (long long)n, (long long)m);
+  size_t off[kOtRegions], bytes[kOtRegions];
+  ot_layout(n, m, nullptr, nullptr, off, bytes);
+  *offset_bytes = (int64_t)off[which];
+  *count = (int64_t)(bytes[which] / 8);
+  return HSR_OK;
+}
+
 // The solve in three stages, for callers that want to look at the state between blocks of iterations (one host
 // synchronisation per look) instead of enqueueing all numItermax iterations: after convergence the remaining
 // launches return at once, but ~800 empty launches still cost ~2 ms.
@@ -361,6 +384,7 @@ extern "C" int hsr_ot_sinkhorn_barycentric(const double* x_dev, int64_t n, const
                                            int32_t num_iter_max, double stop_thr, void* work_dev, double* ybar_dev,
                                            int32_t* info_dev, hsr_stream_t stream) {
   HSR_REQUIRE(num_iter_max >= 0, HSR_ERR_INVALID, "hsr_ot_sinkhorn_barycentric: numItermax must be >= 0");
+  HSR_REQUIRE(ybar_dev, HSR_ERR_INVALID, "hsr_ot_sinkhorn_barycentric: NULL ybar");   // before begin launches anything
   int rc = hsr_ot_begin(x_dev, n, y_dev, m, reg, work_dev, stream);
   if (rc == HSR_OK) rc = hsr_ot_iterate(n, m, 0, num_iter_max, stop_thr, work_dev, nullptr, stream);
   if (rc == HSR_OK) rc = hsr_ot_finish(y_dev, n, m, num_iter_max, work_dev, ybar_dev, info_dev, stream);

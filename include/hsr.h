@@ -401,6 +401,11 @@ int hsr_interleave_to_bip(const void* in_dev, int32_t in_dtype, int32_t interlea
  * PARITY UNPINNED: POT is absent offline; validated against the oracle's restatement and OT invariants.
  * Workspace: hsr_ot_work_bytes(n, m) bytes (the n x m float64 kernel matrix dominates), 256-byte aligned. */
 int64_t hsr_ot_work_bytes(int64_t n, int64_t m);
+/* Where a part of the workspace lies, for callers that look at the solve between stages: byte offset from work_dev
+ * (256-byte aligned) and the number of 8-byte elements used.  which: 0 state (the 24 bytes of info_dev), 1 K [n][m],
+ * 2 column partial sums [ceil(n/64)][m], 3 error partial sums [ceil(m/64)], 4 u0, 5 u1 [n], 6 v0, 7 v1 [m].
+ * Iteration ii reads u, v of buffer ii & 1 and writes buffer (ii + 1) & 1.  Host only. */
+int hsr_ot_work_region(int64_t n, int64_t m, int32_t which, int64_t* offset_bytes, int64_t* count);
 /* The same solve in stages: begin (kernel matrix, u = 1/n, v = 1/m, state reset), iterate [first_iter, first_iter +
  * count) - may be called repeatedly, copying the 24-byte state to info_dev so that a caller can stop enqueueing
  * once break_iter / conv_iter is set (one host synchronisation per look) - and finish (barycentric projection with

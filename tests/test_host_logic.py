@@ -100,6 +100,60 @@ def test_sizing_helpers_and_error_strings():
     assert lib.hsr_interleave_to_bip(P, 0, 3, 4, 4, 4, P, 0, None) == 1
 
 
+def test_ot_entry_points_refuse_bad_arguments():
+    """Every refusal of the five Sinkhorn entry points comes before the first launch: none of these calls touches a device."""
+    lib = nat.load()
+    P, nan, big = ctypes.c_void_p(256), float("nan"), (1 << 20) + 1
+
+    def refused(fn, ok, at, bad, code=1):
+        args = list(ok)
+        args[at] = bad
+        rc = fn(*args)
+        assert rc == code and lib.hsr_last_error(), (fn.__name__, at, bad, rc)
+
+    begin = [P, 10, P, 10, 0.05, P, None]
+    for at, bad in ((0, None), (2, None), (5, None), (4, 0.0), (4, nan), (4, -0.05), (5, ctypes.c_void_p(264))):
+        refused(lib.hsr_ot_begin, begin, at, bad)
+    iterate = [10, 10, 0, 5, 1e-6, P, None, None]
+    for at, bad in ((5, None), (2, -1), (3, -1)):
+        refused(lib.hsr_ot_iterate, iterate, at, bad)
+    finish = [P, 10, 10, 5, P, P, None, None]
+    for at, bad in ((0, None), (5, None), (4, None), (3, -1)):
+        refused(lib.hsr_ot_finish, finish, at, bad)
+    whole = [P, 10, P, 10, 0.05, 5, 1e-6, P, P, None, None]
+    for at, bad in ((0, None), (2, None), (8, None), (7, None), (4, 0.0), (4, nan), (5, -1)):
+        refused(lib.hsr_ot_sinkhorn_barycentric, whole, at, bad)
+    refused(lib.hsr_ot_sinkhorn_barycentric, whole, 8, None)
+    assert b"NULL ybar" in lib.hsr_last_error()                                  # refused by the call itself, not after begin's launch
+    for fn, ok, n_at, m_at in ((lib.hsr_ot_begin, begin, 1, 3), (lib.hsr_ot_iterate, iterate, 0, 1), (lib.hsr_ot_finish, finish, 1, 2),
+                               (lib.hsr_ot_sinkhorn_barycentric, whole, 1, 3)):
+        for at in (n_at, m_at):
+            for bad in (0, -1, big):
+                refused(fn, ok, at, bad, code=2)
+            assert b"outside [1, 2^20]" in lib.hsr_last_error()
+
+
+def test_ot_work_regions():
+    """hsr_ot_work_region: eight disjoint 256-byte aligned regions in the order state, K, partial, errpart, u0, u1, v0, v1 that end
+    at hsr_ot_work_bytes; counts in 8-byte elements."""
+    lib = nat.load()
+    off, cnt = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    for n, m in ((1, 1), (1, 2), (64, 64), (65, 2), (257, 129), (3, 4162), (5000, 5000), (1 << 20, 1), (1, 1 << 20)):
+        at = 0
+        nchunks = (n + 63) // 64
+        for which, want in enumerate((3, n * m, nchunks * m, (m + 63) // 64, n, n, m, m)):
+            assert lib.hsr_ot_work_region(n, m, which, ctypes.byref(off), ctypes.byref(cnt)) == 0
+            assert off.value == at and off.value % 256 == 0 and cnt.value == want, (n, m, which, off.value, cnt.value)
+            at = off.value + (cnt.value * 8 + 255) // 256 * 256
+        assert at == lib.hsr_ot_work_bytes(n, m)
+    for which in (-1, 8, 1 << 30):
+        assert lib.hsr_ot_work_region(10, 10, which, ctypes.byref(off), ctypes.byref(cnt)) == 1 and b"which" in lib.hsr_last_error()
+    assert lib.hsr_ot_work_region(10, 10, 1, None, ctypes.byref(cnt)) == 1 and b"NULL" in lib.hsr_last_error()
+    assert lib.hsr_ot_work_region(10, 10, 1, ctypes.byref(off), None) == 1
+    for n, m in ((0, 10), (10, 0), ((1 << 20) + 1, 10), (10, (1 << 20) + 1)):
+        assert lib.hsr_ot_work_region(n, m, 1, ctypes.byref(off), ctypes.byref(cnt)) == 2
+
+
 def test_batch_plan_host_side():
     """hsr_batch_plan is pure host code: per-tile slot ranges == hsr_partial_slots of each tile, one unit per
     (tile, slot), longest units first, part_dev pointers inside the workspace."""
