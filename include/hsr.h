@@ -9,7 +9,20 @@
  * Conventions
  *   - plain C: pointers + sizes, no C++/torch types.  `*_dev` pointers are device (HBM) addresses
  *     owned by the caller; the library never allocates or frees on a launch path, never
- *     synchronises the device, and is safe to capture in a hipGraph.
+ *     synchronises the device, and is safe to capture in a hipGraph.  A captured chain of calls can be replayed
+ *     over new CONTENTS of the same buffers with nothing re-issued in between: pointers, sizes and every other
+ *     host argument are fixed at capture; every status word, counter, ticket and workspace a call uses is
+ *     re-armed by the call itself, in stream order (tests/test_gpu_graph_capture.py replays the chains listed in
+ *     tests/capture_cases.py and reuses their scratch across shapes).  Operands a call overwrites in place
+ *     (a_dev / b_dev of the Cholesky solve) are the caller's to write again.
+ *     NOT capturable, by design: hsr_pipeline_submit / _flush /
+ *     _fit_done (events and a side stream, device-side polls, a ticket base the host advances per call);
+ *     hsr_srf_integrate_moments[_u16]_apply when given a job (hsr_apply_job.fit_ticket_base is a host value
+ *     that has to advance by the workgroups of every earlier launch - a replay would reuse the captured one;
+ *     with job == NULL they are the plain entry points); the collectives hsr_allreduce_* / hsr_reduce_f64 /
+ *     hsr_bcast (RCCL's contract, not this library's).  Creation, destruction, sizing and status calls
+ *     (hsr_*_create*, hsr_*_destroy, hsr_polyfeat_prepare, hsr_batch_plan, hsr_pipeline_status, ...) are not
+ *     launch-path calls and belong outside a capture.
  *   - every call is stream ordered on `stream` (a hipStream_t passed as void*; NULL = default).
  *   - return value: HSR_OK or an error code; hsr_last_error() gives the thread-local message.
  *   - images use (band_stride, pixel_stride) addressing, see below; both layouts are accepted everywhere.
@@ -184,7 +197,9 @@ int hsr_srf_integrate_moments_u16_apply(const uint16_t* cube_dev, int64_t npix, 
  * tickets.  The summation tree is the one of hsr_moments_reduce (lane l adds slots l, l+64, ...; butterfly over the
  * lanes), so moments and coefficients carry the same bits as the two-launch form.
  *   group_partials_dev  64 * nb * (3deg+2) doubles of scratch
- *   tickets_dev         65 int32, ZERO before the first launch; the kernel leaves them zero
+ *   tickets_dev         65 int32, ZERO before the first launch; the kernel leaves them zero, so a caller zeroes them once and
+ *                       never again - between calls, between replays of a captured launch, or when a tile of another size
+ *                       follows in the same buffers (partials_dev and group_partials_dev need no initialisation at all)
  *   moments_dev         (nb, 3deg+2) float64 out;   coeffs_dev (nb, deg+1) float64 out, highest power first
  *   min_count           as hsr_poly_solve */
 typedef struct hsr_fused_fit {
@@ -260,7 +275,9 @@ int hsr_poly_apply(const float* x_dev, int64_t x_bs, int64_t x_ps, const uint8_t
 /* ---- a4: exact masked percentiles (np.percentile, linear interpolation) ------------------------
  * color.py:31-32: per channel the (pmin, pmax) percentiles of the masked values, exact order
  * statistics + NumPy's lerp, in float64.  3-pass radix select on the float32 keys.
- *   work_dev: workspace of hsr_percentile_work_bytes(nb) bytes;  lohi_dev: (nb, 2) doubles out.
+ *   work_dev: workspace of hsr_percentile_work_bytes(nb) bytes, needs no initialisation: hsr_percentile_limits zeroes what it
+ *   uses in stream order (or, up to 32768 pixels, does not touch it), so it may hold what a call with more bands or more pixels
+ *   left;  lohi_dev: (nb, 2) doubles out.
  */
 size_t hsr_percentile_work_bytes(int32_t nb);
 int hsr_percentile_limits(const float* x_dev, int64_t x_bs, int64_t x_ps,
