@@ -103,9 +103,19 @@ enum OrthoInstance : int {
   kOrthoInstances = kOrthoBsq + 2
 };
 
+// Kernel instances of hsr_color.hip, the index of the name table behind hsr_color_last_launch / hsr_color_instance_name
+// (csrc/hsr_lib.hip, include/hsr_color.h): a table of its own, so the five others keep their sizes.
+enum ColorInstance : int {
+  kColorMoments = 0,                       // + 3 * LX + LY (load modes of x and y: 0 dword, 1 padded rows, 2 packed rows)
+  kColorMomentsF64 = kColorMoments + 9,
+  kColorReduceSolve,
+  kColorApply,                             // + 3 * LIN + LOUT
+  kColorInstances = kColorApply + 9
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho}_last_launch, csrc/hsr_lib.hip).
-enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchFamilies };
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)
@@ -141,6 +151,20 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
+}
+
+// The 63 adds of wave_sum's xor butterfly (32, 16, .., 1) over 64 lane sums, done by one thread: t[l] = v[l] + v[l ^ off]
+// for l < off is the value every lane of the pair holds after a level, so a[0] after the last level is wave_sum's result
+// bit for bit.  ``col`` = address of lane 0's sum, ``ld`` doubles between lanes.
+__device__ __forceinline__ double butterfly_tree64(const double* col, int ld) {
+  double a[32];
+#pragma unroll
+  for (int l = 0; l < 32; ++l) a[l] = col[(size_t)l * ld] + col[(size_t)(l + 32) * ld];
+#pragma unroll
+  for (int off = 16; off >= 1; off >>= 1)
+#pragma unroll
+    for (int l = 0; l < off; ++l) a[l] = a[l] + a[l + off];
+  return a[0];
 }
 
 // Streaming (non-temporal) accesses: everything on this path is touched exactly once, and letting

@@ -178,20 +178,6 @@ __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ mo
   if (b < nb) solve_band(moments + (size_t)b * moment_count(deg), deg, min_count, coeffs + (size_t)b * (deg + 1));
 }
 
-// The 63 adds of wave_sum's xor butterfly (32, 16, .., 1) over 64 lane sums, done by one thread: t[l] = v[l] + v[l ^ off]
-// for l < off is the value every lane of the pair holds after a level, so a[0] after the last level is wave_sum's result
-// bit for bit.  ``col`` = address of lane 0's sum, ``ld`` doubles between lanes.
-__device__ __forceinline__ double butterfly_tree64(const double* col, int ld) {
-  double a[32];
-#pragma unroll
-  for (int l = 0; l < 32; ++l) a[l] = col[(size_t)l * ld] + col[(size_t)(l + 32) * ld];
-#pragma unroll
-  for (int off = 16; off >= 1; off >>= 1)
-#pragma unroll
-    for (int l = 0; l < off; ++l) a[l] = a[l] + a[l + off];
-  return a[0];
-}
-
 // reduce + solve in one launch: one workgroup per band.  Same tree as row_sum / reduce_kernel - "lane" l adds slots
 // l, l + 64, ... in order, then the butterfly over the 64 lane sums - but laid out for the slot-major partials: a
 // 16-lane group reads the band's 3deg+2 moments of ONE slot (112 contiguous bytes for deg 3), so a load instruction

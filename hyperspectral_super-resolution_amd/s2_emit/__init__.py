@@ -14,6 +14,7 @@ from .color import (
     histogram_match_rgb, ot_match_rgb_sinkhorn_pot
 )
 from .poly_regression import fit_ot_poly_rgb, apply_poly_rgb
+from .affine import fit_ot_affine_rgb, apply_affine_rgb, fit_affine_rgb
 from .fusion import SpectralFusion, fuse_pair, match_pair, calibrate_pseudo_to_real_linear
 from .ridge import PolyRidge, predict_cube_logit, flatten_pixels, subsample_bands_evenly
 from .pairs import TilePairOutput, TilePairValidation, fuse_tile_pair, fuse_tile_pairs
@@ -30,7 +31,7 @@ _REFERENCE_SURFACE = (
     "pseudo_s2_rgb show_side_by_side resize_s2_rgb_to robust_norm robust_norm_rgb "
     "apply_shared_percentile_stretch histogram_match_rgb ot_match_rgb_sinkhorn_pot load_s2_rgb_u8"
 ).split()
-_COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb"]
+_COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb", "fit_ot_affine_rgb", "apply_affine_rgb", "fit_affine_rgb"]
 _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real_linear",
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",

@@ -2,7 +2,7 @@
 
 PyTorch is used only as plumbing (HBM allocations, the current HIP stream, torch.distributed);
 every operator here is one or a few stream-ordered calls into libhsr_mi355x.so through its C ABI
-(include/hsr.h).  Nothing in this module synchronises the device.
+(include/hsr.h, include/hsr_color.h).  Nothing in this module synchronises the device.
 
 Image-like tensors come in two layouts (include/hsr.h, "band_stride / pixel_stride"):
   PLANAR    (nb, npix)   band-major planes
@@ -787,6 +787,111 @@ def poly_apply(x, coeffs, mask=None, lohi=None, clip=True, layout: str = PLANAR,
 def poly_apply_stretch_only(x, lohi, layout: str = PLANAR, out=None, nb: Optional[int] = None):
     """float32(clip((x - lo)/(hi - lo + 1e-12), 0, 1)) per channel: K3 without a polynomial."""
     return poly_apply(x, None, None, lohi, True, layout, out, nb)
+
+
+# ---------------------------------------------------------------------------------------------
+# cross-channel affine colour transfer (include/hsr_color.h, csrc/hsr_color.hip)
+# ---------------------------------------------------------------------------------------------
+class AffineWorkspace:
+    """Per-device scratch of an affine fit, allocated once and reusable: the partial slots, the 22 reduced moments and
+    At = (A row-major, t), 12 doubles.  ``A`` and ``t`` are views of ``At``."""
+
+    def __init__(self, device):
+        torch = nat.require_gpu()
+        lib = nat.load()
+        self.partials = torch.empty(lib.hsr_affine_partials_bytes() // 8, dtype=torch.float64, device=device)
+        self.moments = torch.zeros(nat.HSR_AFFINE_MOMENTS, dtype=torch.float64, device=device)
+        self.At = torch.zeros(12, dtype=torch.float64, device=device)
+        self.slots = 0
+
+    @property
+    def A(self):
+        return self.At[:9].view(3, 3)
+
+    @property
+    def t(self):
+        return self.At[9:]
+
+
+def _img3(t, layout: str):
+    """(band_stride, pixel_stride, npix) of a three-channel float32 image: (3, npix) planar or (npix, >= 3) pixel-major."""
+    bs, ps, n, npix = _img(t, layout, 3)
+    if layout == PLANAR and t.shape[0] != 3:
+        raise ValueError(f"planar colour image must be (3, npix); got {tuple(t.shape)}")
+    return bs, ps, npix
+
+
+def affine_moments(x, y, ws: AffineWorkspace, mask=None, lohi_x=None, lohi_y=None, layout: str = PIXMAJOR,
+                   y_layout: Optional[str] = None):
+    """The 22 moment partials of a float32 image pair -> ws.partials / ws.slots; affine_solve(ws, ...) finishes the fit."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    xbs, xps, npix = _img3(x, layout)
+    ybs, yps, ny = _img3(y, y_layout or layout)
+    if ny != npix or x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise ValueError("x and y must be float32 three-channel images of the same pixel count")
+    slots = C.c_int32(0)
+    with _launch(x) as st:
+        nat.check(lib.hsr_affine_moments(_ptr(x), xbs, xps, _ptr(y), ybs, yps, _ptr(mask), npix, _ptr(lohi_x), _ptr(lohi_y),
+                                         _ptr(ws.partials), C.byref(slots), st), "hsr_affine_moments")
+    ws.slots = slots.value
+    return ws
+
+
+def affine_moments_f64(x, y, ws: AffineWorkspace):
+    """The same partials for float64 sample rows x, y (n, 3) on the GPU (the OT path)."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    n = int(x.shape[0])
+    for t in (x, y):
+        if not (t.dtype == torch.float64 and t.is_cuda and t.dim() == 2 and tuple(t.shape) == (n, 3) and t.stride(1) == 1):
+            raise ValueError("x and y must be (n, 3) float64 on the GPU with unit channel stride")
+    slots = C.c_int32(0)
+    with _launch(x) as st:
+        nat.check(lib.hsr_affine_moments_f64(_ptr(x), max(int(x.stride(0)), 3), _ptr(y), max(int(y.stride(0)), 3), n,
+                                             _ptr(ws.partials), C.byref(slots), st), "hsr_affine_moments_f64")
+    ws.slots = slots.value
+    return ws
+
+
+def affine_solve(ws: AffineWorkspace, min_count: int):
+    """Fixed-order reduction of the last moments launch + the np.linalg.lstsq solve -> (ws.A (3, 3), ws.t (3,)) on the device."""
+    lib = nat.load()
+    with _launch(ws.partials) as st:
+        nat.check(lib.hsr_affine_reduce_solve(_ptr(ws.partials), ws.slots, int(min_count), _ptr(ws.moments), _ptr(ws.At), st),
+                  "hsr_affine_reduce_solve")
+    return ws.A, ws.t
+
+
+def affine_solve_host(moments: np.ndarray, min_count: int) -> np.ndarray:
+    """Host twin of the solve (same C code compiled for the CPU): 22 moments -> At (12,); needs only the library."""
+    lib = nat.load()
+    m = np.ascontiguousarray(moments, dtype=np.float64).reshape(nat.HSR_AFFINE_MOMENTS)
+    out = np.zeros(12, dtype=np.float64)
+    nat.check(lib.hsr_affine_solve_host(m.ctypes.data_as(C.POINTER(C.c_double)), int(min_count),
+                                        out.ctypes.data_as(C.POINTER(C.c_double))), "hsr_affine_solve_host")
+    return out
+
+
+def affine_apply(x, At, mask=None, lohi=None, clip_mode: int = 1, layout: str = PIXMAJOR, out=None,
+                 out_layout: Optional[str] = None):
+    """out = x @ A + t on a float32 three-channel image.  At: 12 contiguous float64 on the device (A row-major, then t).
+    clip_mode 0 none, 1 transformed pixels, 2 every pixel."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    xbs, xps, npix = _img3(x, layout)
+    if x.dtype != torch.float32:
+        raise ValueError("x must be a float32 image")
+    if not (At.dtype == torch.float64 and At.is_cuda and At.numel() == 12 and At.is_contiguous()):
+        raise ValueError("At must be 12 contiguous float64 on the GPU")
+    o = out if out is not None else torch.empty_like(x, memory_format=torch.contiguous_format)
+    obs, ops, no = _img3(o, out_layout or layout)
+    if no != npix or o.dtype != torch.float32:
+        raise ValueError("out must be a float32 image of x's pixel count")
+    with _launch(x) as st:
+        nat.check(lib.hsr_affine_apply(_ptr(x), xbs, xps, _ptr(mask), _ptr(At), npix, _ptr(lohi), int(clip_mode), _ptr(o),
+                                       obs, ops, st), "hsr_affine_apply")
+    return o
 
 
 def percentile_limits(x, mask=None, pmin=2.0, pmax=98.0, layout: str = PLANAR, nb: Optional[int] = None,

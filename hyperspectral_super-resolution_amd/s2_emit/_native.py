@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h and include/hsr_color.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -242,6 +242,24 @@ SIGNATURES = {
     "hsr_bcast": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
 }
 
+# The affine colour family, include/hsr_color.h: a table of its own (SIGNATURES is hsr.h's, name for name); load() types both.
+_pf64 = C.POINTER(_f64)
+HSR_AFFINE_MOMENTS = 22
+HSR_AFFINE_MAX_SLOTS = 512
+HSR_AFFINE_SLOT_PIXELS = 2048
+COLOR_SIGNATURES = {
+    "hsr_affine_partial_slots": (C.c_int, [_i64]),
+    "hsr_affine_partials_bytes": (C.c_size_t, []),
+    "hsr_affine_moments": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _pi32, _vp]),
+    "hsr_affine_moments_f64": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _pi32, _vp]),
+    "hsr_affine_reduce_solve": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp]),
+    "hsr_affine_solve_host": (C.c_int, [_pf64, _i64, _pf64]),
+    "hsr_affine_apply": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _i64, _vp]),
+    "hsr_color_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_color_instance_count": (C.c_int, []),
+    "hsr_color_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -265,7 +283,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -3,7 +3,9 @@
 On the measured path (reference poly_regression.py:126-127,161) is
 ``apply_shared_percentile_stretch``: exact masked percentiles by a device radix select
 (csrc/hsr_select.hip) and the stretch itself fused into K3 (csrc/hsr_poly.hip).  The remaining
-names are API surface kept for drop-in use: plain host NumPy, no kernels.
+names are API surface kept for drop-in use: plain host NumPy, no kernels -
+except ``ot_match_rgb_sinkhorn_pot`` given GPU tensors, which runs wholly on the device (.affine,
+csrc/hsr_color.hip); its NumPy-input form is unchanged.
 """
 from __future__ import annotations
 
@@ -123,8 +125,20 @@ def ot_match_rgb_sinkhorn_pot(
     3D colour transfer: Sinkhorn OT on masked RGB samples, barycentric targets, affine least
     squares, applied inside the mask (color.py:65-116).  Sampling follows the reference's PCG64
     stream on the host; the Sinkhorn iterations run on the GPU in float64 (see ._ot).
+    GPU tensors in: the whole matcher stays on the device - sampling, Sinkhorn, the moments, the lstsq solve and the apply
+    (.affine, csrc/hsr_color.hip) - and a float32 GPU tensor comes back; fewer than 2 usable rows return a clone of the source.
     """
     from . import _ot
+    if _is_torch(src_rgb):
+        from . import affine
+        torch = nat.require_gpu()
+        src = affine._device_image(torch, src_rgb, "src_rgb")
+        ref = affine._device_image(torch, ref_rgb, "ref_rgb")
+        m = affine._device_mask(torch, mask, src.shape[:2], src.device).reshape(src.shape[:2])
+        fit = affine._fit_ot_device(torch, src, ref, m, n_samples, reg, numItermax, stopThr, seed)
+        if fit is None:
+            return src_rgb.clone()
+        return affine.apply_affine_rgb(src, fit[0], fit[1], m)
     s = _ot.sample_pairs(src_rgb, ref_rgb, mask, n_samples, seed, min_rows=2)
     if s is None:
         return src_rgb.copy()

@@ -1146,7 +1146,7 @@ def _match_pair_side_stream(torch, dev, which: int = 0):
 def match_pair(R, emit_w, srf_dict, good_mask, s2_rgb_hi, factor: int = 6, deg: int = 4, use_ot: bool = True,
                n_samples: int = 5000, reg: float = 0.05, numItermax: int = 300, stopThr: float = 1e-6, seed: int = 0,
                src_scale: float = 1.0 / 255.0, rgb_bands=("B4", "B3", "B2"), positive_band: str = "B2",
-               as_numpy: bool = True):
+               as_numpy: bool = True, model: str = "poly"):
     """The reference driver (s2_emit/poly_regression.py:96-172 == notebook cell 81) on in-memory,
     grid-aligned arrays, device resident:
 
@@ -1161,7 +1161,14 @@ def match_pair(R, emit_w, srf_dict, good_mask, s2_rgb_hi, factor: int = 6, deg: 
     ``coeffs`` (3, deg+1), ``emit_rgb_matched_60m`` (H,W,3), ``s2_rgb_60m_n`` (H,W,3), ``valid60`` (H,W),
     ``emit_rgb_10m_matched`` (H*f, W*f, 3), ``mask10`` - NumPy arrays, or GPU tensors if as_numpy=False.
     The two resampling steps replace GDAL's reproject for aligned grids (parity unpinned, see hsr.h).
+
+    model="affine": phase 3 fits the cross-channel map rgb' = rgb A + t instead of three polynomials (``deg`` is unused) -
+    fit_ot_affine_rgb on the stretched images with use_ot=True, the least squares over all valid pixels (min_count 200)
+    otherwise - and both applies use it (csrc/hsr_color.hip).  The dict then carries ``affine_A`` (3,3) and ``affine_t`` (3,)
+    in place of ``coeffs``; every other key is the same.
     """
+    if model not in ("poly", "affine"):
+        raise ValueError(f"model must be 'poly' or 'affine'; got {model!r}")
     torch = nat.require_gpu()
     from .poly_regression import fit_ot_poly_rgb
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -1211,6 +1218,25 @@ def match_pair(R, emit_w, srf_dict, good_mask, s2_rgb_hi, factor: int = 6, deg: 
     cur.wait_stream(side2)
     lohi_e.record_stream(cur)
     s2_n = eng.poly_apply_stretch_only(s2_60, lohi_s, PM, nb=3)
+    if model == "affine":
+        from . import affine
+        if use_ot:
+            emit_n = eng.poly_apply_stretch_only(emit_rgb, lohi_e, PM, nb=3)
+            fit = affine._fit_ot_device(torch, emit_n.reshape(H, W, 4), s2_n.reshape(H, W, 4), valid60.reshape(H, W), n_samples, reg,
+                                        numItermax, stopThr, seed)
+            fit = fit if fit is not None else affine._identity(torch, dev)
+        else:
+            aws = eng.AffineWorkspace(dev)
+            eng.affine_moments(emit_rgb, s2_60, aws, valid60, lohi_e, lohi_s, PM)
+            fit = eng.affine_solve(aws, 200)
+        At = torch.cat([fit[0].reshape(9), fit[1]]).contiguous()
+        matched60 = eng.affine_apply(emit_rgb, At, valid60, lohi_e, 2, PM)
+        cur.wait_stream(side)
+        for t_ in (emit_rgb_10, mask10, lohi10):
+            t_.record_stream(cur)
+        matched10 = eng.affine_apply(emit_rgb_10, At, mask10, lohi10, 2, PM)
+        return _match_pair_result(dict(affine_A=At[:9].view(3, 3), affine_t=At[9:]), matched60, s2_n, valid60, matched10, mask10,
+                                  lohi_e, lohi_s, lohi10, H, W, factor, as_numpy)
     if use_ot:
         emit_n = eng.poly_apply_stretch_only(emit_rgb, lohi_e, PM, nb=3)
         co = fit_ot_poly_rgb(emit_n[:, :3].reshape(H, W, 3), s2_n[:, :3].reshape(H, W, 3), valid60.reshape(H, W),
@@ -1225,8 +1251,14 @@ def match_pair(R, emit_w, srf_dict, good_mask, s2_rgb_hi, factor: int = 6, deg: 
     for t_ in (emit_rgb_10, mask10, lohi10):
         t_.record_stream(cur)
     matched10 = eng.poly_apply(emit_rgb_10, coeffs, mask10, lohi10, True, PM, nb=3)
+    return _match_pair_result(dict(coeffs=coeffs), matched60, s2_n, valid60, matched10, mask10, lohi_e, lohi_s, lohi10, H, W,
+                              factor, as_numpy)
+
+
+def _match_pair_result(fit, matched60, s2_n, valid60, matched10, mask10, lohi_e, lohi_s, lohi10, H, W, factor, as_numpy):
+    """The result dict of match_pair: the fit's own keys first, then the images, masks and limits."""
     Hh, Wh = H * factor, W * factor
-    res = dict(coeffs=coeffs, emit_rgb_matched_60m=matched60[:, :3].reshape(H, W, 3),
+    res = dict(fit, emit_rgb_matched_60m=matched60[:, :3].reshape(H, W, 3),
                s2_rgb_60m_n=s2_n[:, :3].reshape(H, W, 3), valid60=valid60.reshape(H, W).bool(),
                emit_rgb_10m_matched=matched10[:, :3].reshape(Hh, Wh, 3), mask10=mask10.reshape(Hh, Wh).bool(),
                lohi_emit_60m=lohi_e, lohi_s2_60m=lohi_s, lohi_emit_10m=lohi10)
