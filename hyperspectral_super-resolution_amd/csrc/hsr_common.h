@@ -113,9 +113,19 @@ enum ColorInstance : int {
   kColorInstances = kColorApply + 9
 };
 
+// Kernel instances of hsr_coreg.hip, the index of the name table behind hsr_coreg_last_launch / hsr_coreg_instance_name
+// (csrc/hsr_lib.hip, include/hsr_coreg.h): a table of its own, so the six others keep their sizes.
+enum CoregInstance : int {
+  kCoregSurface = 0,                       // + 0 <float>, 1 <uint16_t>
+  kCoregPeaks = kCoregSurface + 2,
+  kCoregFitModel,
+  kCoregWarp,                              // + 2 * (0 <float>, 1 <uint16_t>) + (0 LDS, 1 DIRECT)
+  kCoregInstances = kCoregWarp + 4
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color}_last_launch, csrc/hsr_lib.hip).
-enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchFamilies };
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

@@ -4,6 +4,7 @@
 
 #include "hsr_common.h"
 #include "../../include/hsr_color.h"
+#include "../../include/hsr_coreg.h"
 
 namespace hsr {
 
@@ -83,7 +84,7 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// Launch records (hsr_{aux,scene,k4,pairs,ortho,color}_last_launch): per family and thread, the kernels launched successfully since the last
+// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg}_last_launch): per family and thread, the kernels launched successfully since the last
 // read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
 // the list is full.  Indices turn into names only when read.
 static const char* const kAuxNames[] = {
@@ -145,17 +146,24 @@ static const char* const kColorNames[] = {
     "affine_apply_kernel<1, 0>", "affine_apply_kernel<1, 1>", "affine_apply_kernel<1, 2>",
     "affine_apply_kernel<2, 0>", "affine_apply_kernel<2, 1>", "affine_apply_kernel<2, 2>",
 };
+static const char* const kCoregNames[] = {
+    "coreg_surface_kernel<float>", "coreg_surface_kernel<uint16_t>", "coreg_peaks_kernel", "coreg_fit_model_kernel",
+    "coreg_warp_kernel<float, LDS>", "coreg_warp_kernel<float, DIRECT>",
+    "coreg_warp_kernel<uint16_t, LDS>", "coreg_warp_kernel<uint16_t, DIRECT>",
+};
 template <int N>
 constexpr int length(const char* const (&)[N]) { return N; }
 static_assert(length(kOrthoNames) == kOrthoInstances, "kOrthoNames: one name per OrthoInstance");
 static_assert(length(kColorNames) == kColorInstances, "kColorNames: one name per ColorInstance");
+static_assert(length(kCoregNames) == kCoregInstances, "kCoregNames: one name per CoregInstance");
 static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
 static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
 static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
 static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per PairsInstance");
 
 // Aux, scene and ortho entry points launch one kernel each, so their record keeps the last launch only; K4 and pairs entry points
-// launch up to two, and a caller may read after several calls; a colour fit is a chain of three entry points, read after the chain.
+// launch up to two, and a caller may read after several calls; a colour fit is a chain of three entry points and a
+// co-registration one of four, read after the chain.
 constexpr int kRecordCap = 32;
 constexpr int kColorRecordCap = 8;
 struct Family {
@@ -171,6 +179,7 @@ static const Family kFamilies[] = {
     {kPairsNames, kPairsInstances, kRecordCap, "hsr_pairs_instance_name"},  // kLaunchPairs
     {kOrthoNames, kOrthoInstances, 1, "hsr_ortho_instance_name"},  // kLaunchOrtho
     {kColorNames, kColorInstances, kColorRecordCap, "hsr_color_instance_name"},  // kLaunchColor
+    {kCoregNames, kCoregInstances, kColorRecordCap, "hsr_coreg_instance_name"},  // kLaunchCoreg
 };
 static_assert(sizeof(kFamilies) / sizeof(kFamilies[0]) == kLaunchFamilies, "kFamilies: one row per LaunchFamily");
 struct Record {
@@ -242,6 +251,10 @@ extern "C" const char* hsr_ortho_instance_name(int32_t i) { return hsr::instance
 extern "C" int hsr_color_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchColor, names, capacity); }
 extern "C" int hsr_color_instance_count(void) { return hsr::kColorInstances; }
 extern "C" const char* hsr_color_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchColor, i); }
+
+extern "C" int hsr_coreg_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchCoreg, names, capacity); }
+extern "C" int hsr_coreg_instance_count(void) { return hsr::kCoregInstances; }
+extern "C" const char* hsr_coreg_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchCoreg, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

@@ -21,6 +21,8 @@ from .pairs import TilePairOutput, TilePairValidation, fuse_tile_pair, fuse_tile
 from .scenes import (Window, SceneOutput, scene_windows, select_tiles, find_valid_paired_tiles, extract_tile_pairs,
                      mosaic_tiles, fuse_scene)
 from .ortho import OrthoOutput, apply_glt, ortho_scene, glt_from_xy, quality_mask
+from .coreg import (TiePoints, ShiftModel, CoregOutput, closest_band, tie_point_grid, match_windows, fit_shift_model, warp_scene,
+                    coregister_scene)
 from ._native import HsrUnavailable, HsrError
 
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
@@ -37,5 +39,7 @@ _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
           "Window", "SceneOutput",
+          "coregister_scene", "match_windows", "fit_shift_model", "warp_scene", "tie_point_grid", "closest_band",
+          "TiePoints", "ShiftModel", "CoregOutput",
           "apply_glt", "ortho_scene", "glt_from_xy", "quality_mask", "OrthoOutput"]
 __all__ = _REFERENCE_SURFACE + _COPIED_BY_CALLERS + _FUSED

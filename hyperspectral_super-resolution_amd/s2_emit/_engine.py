@@ -894,6 +894,109 @@ def affine_apply(x, At, mask=None, lohi=None, clip_mode: int = 1, layout: str = 
     return o
 
 
+# ---------------------------------------------------------------------------------------------
+# co-registration (include/hsr_coreg.h, csrc/hsr_coreg.hip)
+# ---------------------------------------------------------------------------------------------
+def _plane(torch, t, what, dtypes):
+    """(row stride, h, w) of a 2-D GPU tensor with unit column stride: a band of a scene passes without a copy."""
+    if not (t.is_cuda and t.dim() == 2 and t.dtype in dtypes and (t.shape[1] == 1 or t.stride(1) == 1) and t.stride(0) >= t.shape[1]):
+        raise ValueError(f"{what} must be a 2-D GPU tensor of {' or '.join(str(d) for d in dtypes)} with unit column stride")
+    return int(t.stride(0)), int(t.shape[0]), int(t.shape[1])
+
+
+def _s2_dtype(torch, t, what):
+    if t.dtype == torch.float32:
+        return 0
+    if t.dtype == torch.uint16:
+        return 1
+    raise ValueError(f"{what} must be float32 or uint16, got {t.dtype}")
+
+
+def coreg_surface(emit_plane, s2_plane, origins, window: int, factor: int, max_shift: int, min_valid: int, emit_mask=None,
+                  s2_nodata=None, out=None):
+    """The score surfaces (P, 2R+1, 2R+1) float64 of the tie points ``origins`` (P, 2) int32, all on the device."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    ers, he, we = _plane(torch, emit_plane, "emit_plane", (torch.float32,))
+    srs, hs, ws = _plane(torch, s2_plane, "s2_plane", (torch.float32, torch.uint16))
+    mrs = 0
+    if emit_mask is not None:
+        mrs, mh, mw = _plane(torch, emit_mask, "emit_mask", (torch.uint8, torch.bool))
+        if (mh, mw) != (he, we):
+            raise ValueError(f"emit_mask must be {(he, we)}, got {(mh, mw)}")
+    if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.is_contiguous()):
+        raise ValueError("origins must be a contiguous (P, 2) int32 GPU tensor")
+    P, D = int(origins.shape[0]), 2 * int(max_shift) + 1
+    surf = out if out is not None else torch.empty((P, D, D), dtype=torch.float64, device=emit_plane.device)
+    with _launch(emit_plane) as st:
+        nat.check(lib.hsr_coreg_surface(_ptr(emit_plane), ers, he, we, _ptr(emit_mask), mrs, _ptr(s2_plane),
+                                        _s2_dtype(torch, s2_plane, "s2_plane"), srs, hs, ws, 0 if s2_nodata is None else 1,
+                                        0.0 if s2_nodata is None else float(s2_nodata), _ptr(origins), P, int(window), int(factor),
+                                        int(max_shift), int(min_valid), _ptr(surf), st), "hsr_coreg_surface")
+    return surf
+
+
+def coreg_peaks(surface, origins, window: int, factor: int, max_shift: int, emit_shape, s2_shape, min_score: float, out=None):
+    """surfaces -> the (P, 8) float64 tie-point records [cy, cx, dy, dx, score, sharpness, n_valid, status]."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    P = int(origins.shape[0])
+    table = out if out is not None else torch.empty((P, nat.HSR_COREG_RECORD), dtype=torch.float64, device=surface.device)
+    with _launch(surface) as st:
+        nat.check(lib.hsr_coreg_peaks(_ptr(surface), _ptr(origins), P, int(window), int(factor), int(max_shift), int(emit_shape[0]),
+                                      int(emit_shape[1]), int(s2_shape[0]), int(s2_shape[1]), float(min_score), _ptr(table), st),
+                  "hsr_coreg_peaks")
+    return table
+
+
+def coreg_fit_model(table, kind: int, min_points: int, reject_px: float, s2_shape, out=None):
+    """records (updated in place: outliers get status 5) -> the 10 doubles of the shift model, on the device."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.shape[1] == nat.HSR_COREG_RECORD
+            and table.is_contiguous()):
+        raise ValueError("table must be a contiguous (P, 8) float64 GPU tensor")
+    model = out if out is not None else torch.empty(nat.HSR_COREG_MODEL, dtype=torch.float64, device=table.device)
+    with _launch(table) as st:
+        nat.check(lib.hsr_coreg_fit_model(_ptr(table), int(table.shape[0]), int(kind), int(min_points), float(reject_px),
+                                          int(s2_shape[0]), int(s2_shape[1]), _ptr(model), st), "hsr_coreg_fit_model")
+    return model
+
+
+def coreg_fit_model_host(table: np.ndarray, kind: int, min_points: int, reject_px: float, s2_shape):
+    """Host twin of the fit (the same C code compiled for the CPU): (P, 8) records -> (records after rejection, model (10,))."""
+    lib = nat.load()
+    t = np.array(table, dtype=np.float64, order="C").reshape(-1, nat.HSR_COREG_RECORD)
+    model = np.zeros(nat.HSR_COREG_MODEL, dtype=np.float64)
+    pd = C.POINTER(C.c_double)
+    buf = t if t.size else np.zeros(nat.HSR_COREG_RECORD)
+    nat.check(lib.hsr_coreg_fit_model_host(buf.ctypes.data_as(pd), int(t.shape[0]), int(kind), int(min_points), float(reject_px),
+                                           int(s2_shape[0]), int(s2_shape[1]), model.ctypes.data_as(pd)), "hsr_coreg_fit_model_host")
+    return t, model
+
+
+def coreg_warp(scene, model, fill: float, max_abs_shift: float, max_abs_slope: float, nodata=None, out=None, status=None):
+    """The corrected (bands, H, W) scene, float32 or uint16, under the 10-double ``model`` on the device -> (out, status)."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    if not (scene.is_cuda and scene.dim() == 3 and scene.stride(2) == 1):
+        raise ValueError("scene must be a (bands, H, W) GPU tensor with unit column stride")
+    if not (model.is_cuda and model.dtype == torch.float64 and model.numel() == nat.HSR_COREG_MODEL and model.is_contiguous()):
+        raise ValueError("model must be 10 contiguous float64 on the GPU")
+    dt = _s2_dtype(torch, scene, "scene")
+    o = out if out is not None else torch.empty(tuple(scene.shape), dtype=scene.dtype, device=scene.device)
+    if not (o.is_cuda and o.dtype == scene.dtype and tuple(o.shape) == tuple(scene.shape) and o.stride(2) == 1):
+        raise ValueError("out must be a GPU tensor of the scene's shape and dtype with unit column stride")
+    status = status if status is not None else torch.empty(1, dtype=torch.int32, device=scene.device)
+    b, h, w = (int(s) for s in scene.shape)
+    with _launch(scene) as st:
+        nat.check(lib.hsr_coreg_warp(_ptr(scene), dt, b, h, w, int(scene.stride(0)), int(scene.stride(1)), _ptr(model),
+                                     0 if nodata is None else 1, 0.0 if nodata is None else float(nodata), float(fill),
+                                     float(max_abs_shift), float(max_abs_slope), _ptr(o), int(o.stride(0)), int(o.stride(1)),
+                                     _ptr(status), st), "hsr_coreg_warp")
+    return o, status
+
+
 def percentile_limits(x, mask=None, pmin=2.0, pmax=98.0, layout: str = PLANAR, nb: Optional[int] = None,
                       group=None, distributed: Optional[bool] = None, _reduce=None):
     """Exact np.percentile(vals[mask], [pmin, pmax]) per channel -> (nb, 2) float64 on the device.

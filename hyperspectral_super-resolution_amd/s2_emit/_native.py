@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h and include/hsr_color.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h and include/hsr_coreg.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -260,6 +260,22 @@ COLOR_SIGNATURES = {
     "hsr_color_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The co-registration family, include/hsr_coreg.h: again a table of its own; load() types all three.
+HSR_COREG_RECORD = 8
+HSR_COREG_MODEL = 10
+COREG_SIGNATURES = {
+    "hsr_coreg_surface": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i32, _f64, _vp, _i32, _i32,
+                                    _i32, _i32, _i32, _vp, _vp]),
+    "hsr_coreg_peaks": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f64, _vp, _vp]),
+    "hsr_coreg_fit_model": (C.c_int, [_vp, _i32, _i32, _i32, _f64, _i32, _i32, _vp, _vp]),
+    "hsr_coreg_fit_model_host": (C.c_int, [_pf64, _i32, _i32, _i32, _f64, _i32, _i32, _pf64]),
+    "hsr_coreg_warp": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _f64, _f64, _f64, _f64, _vp, _i64, _i64, _vp,
+                                 _vp]),
+    "hsr_coreg_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_coreg_instance_count": (C.c_int, []),
+    "hsr_coreg_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -283,7 +299,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
