@@ -928,6 +928,8 @@ def coreg_surface(emit_plane, s2_plane, origins, window: int, factor: int, max_s
         raise ValueError("origins must be a contiguous (P, 2) int32 GPU tensor")
     P, D = int(origins.shape[0]), 2 * int(max_shift) + 1
     surf = out if out is not None else torch.empty((P, D, D), dtype=torch.float64, device=emit_plane.device)
+    if P == 0:                                        # no tie point: nothing to launch, and an empty tensor has no address to pass
+        return surf
     with _launch(emit_plane) as st:
         nat.check(lib.hsr_coreg_surface(_ptr(emit_plane), ers, he, we, _ptr(emit_mask), mrs, _ptr(s2_plane),
                                         _s2_dtype(torch, s2_plane, "s2_plane"), srs, hs, ws, 0 if s2_nodata is None else 1,
@@ -942,6 +944,8 @@ def coreg_peaks(surface, origins, window: int, factor: int, max_shift: int, emit
     lib = nat.load()
     P = int(origins.shape[0])
     table = out if out is not None else torch.empty((P, nat.HSR_COREG_RECORD), dtype=torch.float64, device=surface.device)
+    if P == 0:
+        return table
     with _launch(surface) as st:
         nat.check(lib.hsr_coreg_peaks(_ptr(surface), _ptr(origins), P, int(window), int(factor), int(max_shift), int(emit_shape[0]),
                                       int(emit_shape[1]), int(s2_shape[0]), int(s2_shape[1]), float(min_score), _ptr(table), st),
@@ -957,8 +961,10 @@ def coreg_fit_model(table, kind: int, min_points: int, reject_px: float, s2_shap
             and table.is_contiguous()):
         raise ValueError("table must be a contiguous (P, 8) float64 GPU tensor")
     model = out if out is not None else torch.empty(nat.HSR_COREG_MODEL, dtype=torch.float64, device=table.device)
+    # no record: the kernel still writes the zero model (kind_used -1); it reads nothing, but the entry refuses the NULL of an empty tensor
+    rows = table if table.shape[0] else table.new_empty((1, nat.HSR_COREG_RECORD))
     with _launch(table) as st:
-        nat.check(lib.hsr_coreg_fit_model(_ptr(table), int(table.shape[0]), int(kind), int(min_points), float(reject_px),
+        nat.check(lib.hsr_coreg_fit_model(_ptr(rows), int(table.shape[0]), int(kind), int(min_points), float(reject_px),
                                           int(s2_shape[0]), int(s2_shape[1]), _ptr(model), st), "hsr_coreg_fit_model")
     return model
 

@@ -123,7 +123,10 @@ def match_windows(emit_plane, s2_plane, *, grid=None, emit_mask=None, s2_nodata=
         origins = grid.to(device=e.device, dtype=torch.int32).contiguous()
     else:
         g = np.ascontiguousarray(np.asarray(grid).reshape(-1, 2), dtype=np.int32)
-        origins = torch.from_numpy(g).pin_memory().to(e.device, non_blocking=True)      # pinned: the upload does not block the host
+        if g.size == 0:
+            origins = torch.empty((0, 2), dtype=torch.int32, device=e.device)           # a scene too small for one window
+        else:
+            origins = torch.from_numpy(g).pin_memory().to(e.device, non_blocking=True)  # pinned: the upload does not block the host
     min_valid = max(1, int(math.ceil(float(min_valid_frac) * window * window)))
     surface = eng.coreg_surface(e, s, origins, window, factor, max_shift, min_valid, m, s2_nodata)
     table = eng.coreg_peaks(surface, origins, window, factor, max_shift, e.shape, s.shape, min_score)

@@ -63,12 +63,13 @@ def texture(hs, ws, seed):
     return t
 
 
-def scene_pair(he, we, f, model, seed, dtype="f32"):
-    """(emit (he, we) float32, s2 (he f, we f) float32 or uint16, truth model).  S2 is the texture; EMIT the block mean of the
-    texture displaced by `model` (order-3 spline)."""
-    hs, ws = he * f, we * f
-    t = texture(hs, ws, seed)
-    yy, xx = np.meshgrid(np.arange(hs, dtype=np.float64), np.arange(ws, dtype=np.float64), indexing="ij")
+def scene_pair(he, we, f, model, seed, dtype="f32", hs=None, ws=None):
+    """(emit (he, we) float32, s2 (hs, ws) float32 or uint16; hs, ws default to he f, we f).  S2 is the texture, cut to (hs, ws);
+    EMIT the block mean of the texture displaced by `model` (order-3 spline) over its own he f x we f S2 pixels, whatever the cut."""
+    he_s, we_s = he * f, we * f
+    hs, ws = he_s if hs is None else hs, we_s if ws is None else ws
+    t = texture(max(hs, he_s), max(ws, we_s), seed)
+    yy, xx = np.meshgrid(np.arange(he_s, dtype=np.float64), np.arange(we_s, dtype=np.float64), indexing="ij")
     dy, dx = shift_field(model, yy, xx)
     disp = ndimage.map_coordinates(t, [yy + dy + PAD, xx + dx + PAD], order=3, mode="nearest")
     emit = disp.reshape(he, f, we, f).mean(axis=(1, 3)).astype(np.float32)
@@ -150,9 +151,15 @@ def peak_margin(surface):
 # name: he, we (EMIT), f, w, R, origins, dtype, extra (row-stride padding, elements), mask, min_valid, truth (dy0, dx0), seed
 #   mask: none | part (a black S2 rectangle = nodata / NaN, and a masked EMIT corner) | all (every EMIT pixel masked)
 #   min_valid: an int, or "met" / "missed": exactly the count of valid pairs of the worst candidate, and one more
-def _srow(he, we, f, w, R, origins, dtype="f32", extra=0, mask="none", min_valid=None, truth=(0.0, 0.0), seed=1, const=False):
+#   hs, ws: the S2 plane, default f he, f we.  pads: (EMIT, S2, mask) row-stride paddings of their own, default `extra` for all
+#   three.  offs: (EMIT, S2, mask) base offsets in bytes past a 256-byte boundary, default (4, 12 or 2 for uint16, 1).
+#   inside: what the region test must say of every origin, for the rows whose origins straddle it
+def _srow(he, we, f, w, R, origins, dtype="f32", extra=0, mask="none", min_valid=None, truth=(0.0, 0.0), seed=1, const=False,
+          hs=None, ws=None, pads=None, offs=None, inside=None):
     return dict(he=he, we=we, f=f, w=w, R=R, origins=origins, dtype=dtype, extra=extra, mask=mask,
-                min_valid=min_valid if min_valid is not None else max(1, (3 * w * w + 3) // 4), truth=truth, seed=seed, const=const)
+                min_valid=min_valid if min_valid is not None else max(1, (3 * w * w + 3) // 4), truth=truth, seed=seed, const=const,
+                hs=he * f if hs is None else hs, ws=we * f if ws is None else ws, pads=pads if pads is not None else (extra,) * 3,
+                offs=offs if offs is not None else (4, 2 if dtype == "u16" else 12, 1), inside=inside)
 
 
 def _grid65():
@@ -185,8 +192,33 @@ SURFACE_ROWS = {
     # the four edges, touched (R = f: f i0 - R = 0 at i0 = 1; f (i0 + w) + R = hs at i0 = 15) and crossed
     "edges": _srow(24, 24, 6, 8, 6, [(1, 5), (0, 5), (15, 5), (16, 5), (5, 1), (5, 0), (5, 15), (5, 16), (1, 1), (15, 15), (-1, 5),
                                      (5, -3), (17, 5), (5, 40)], truth=(1.0, 1.0), seed=18),
+    # rectangular planes, f in {3, 4, 5, 7, 8}; R above and equal to f here, below it in strides-mask-u16
+    "rect-f3-R4": _srow(20, 34, 3, 8, 4, [(3, 5), (9, 20)], truth=(1.3, -2.4), seed=31),
+    "rect-f4-R5": _srow(30, 18, 4, 9, 5, [(4, 2), (17, 7)], truth=(-2.3, 3.2), seed=32, dtype="u16"),
+    "rect-f5-R5": _srow(18, 26, 5, 8, 5, [(2, 11), (8, 3)], truth=(3.3, -1.7), seed=33),
+    "rect-f7-R9": _srow(14, 22, 7, 9, 9, [(2, 9), (3, 4)], truth=(-6.2, 4.4), seed=34, dtype="u16"),
+    "rect-f8-R8": _srow(22, 13, 8, 8, 8, [(9, 1), (3, 4)], truth=(5.3, -6.7), seed=35),
+    "rect-f8-R24": _srow(16, 26, 8, 8, 24, [(4, 9)], truth=(-13.3, 17.25), seed=36, dtype="u16"),
+    # strides of their own: the EMIT plane, the S2 plane and the mask padded by three different amounts, at three different offsets
+    "strides-mask": _srow(24, 30, 6, 8, 6, [(2, 2), (8, 8), (13, 12), (4, 20)], mask="part", truth=(1.3, -0.7), seed=37, min_valid=20,
+                          pads=(5, 11, 3), offs=(8, 20, 3)),
+    "strides-mask-u16": _srow(20, 28, 4, 8, 3, [(2, 2), (9, 12), (11, 3)], mask="part", truth=(0.7, -1.2), seed=38, min_valid=20,
+                              dtype="u16", pads=(7, 2, 13), offs=(12, 6, 2)),
+    # an S2 plane that is not f x EMIT.  short-wide: rows i0 <= 12 by EMIT but <= 8 by S2, columns j0 <= 8 by EMIT but <= 10 by S2, so
+    # (9, 4) passes the EMIT bound and fails the S2 bound on rows, (4, 9) the reverse on columns; tall-narrow is its transpose
+    "s2-short-wide": _srow(20, 16, 6, 8, 6, [(1, 1), (8, 8), (5, 3), (9, 4), (12, 4), (13, 4), (4, 9), (4, 10), (4, 11)], hs=104, ws=118,
+                           truth=(1.2, -0.8), seed=39, inside=[True, True, True, False, False, False, False, False, False]),
+    "s2-tall-narrow": _srow(16, 20, 6, 8, 6, [(1, 1), (8, 8), (3, 5), (4, 9), (4, 12), (4, 13), (9, 4), (10, 4), (11, 4)], hs=118, ws=104,
+                            truth=(-0.8, 1.2), seed=40, dtype="u16", inside=[True, True, True, False, False, False, False, False, False]),
+    # the eight inequalities on a plane with he, we, hs / f, ws / f all different (24, 30, 27, 22), each touched and crossed by an
+    # origin of its own.  Rows: f i0 - R >= 0 at 1 | 0, i0 >= 0 at 0 | -1, i0 + w <= he at 16 | 17, the S2 bound at 18 | 19.
+    # Columns: 1 | 0, 0 | -1, the S2 bound at 13 | 14, j0 + w <= we at 22 | 23.  Then the two inside corners.
+    "edges-rect": _srow(24, 30, 6, 8, 6, [(1, 5), (0, 5), (-1, 5), (16, 5), (17, 5), (18, 5), (19, 5), (5, 1), (5, 0), (5, -1), (5, 13),
+                                          (5, 14), (5, 22), (5, 23), (1, 1), (16, 13)], hs=162, ws=132, truth=(1.0, 1.0), seed=41,
+                        inside=[True, False, False, True, False, False, False, True, False, False, True, False, False, False, True, True]),
 }
 EDGES_INSIDE = [True, False, True, False, True, False, True, False, True, True, False, False, False, False]
+SURFACE_ROWS["edges"]["inside"] = EDGES_INSIDE
 NODATA_F32, NODATA_U16 = -9999.0, 0
 
 
@@ -194,8 +226,8 @@ NODATA_F32, NODATA_U16 = -9999.0, 0
 def surface_case(name):
     r = SURFACE_ROWS[name]
     he, we, f, w, R = r["he"], r["we"], r["f"], r["w"], r["R"]
-    hs, ws = he * f, we * f
-    emit, s2 = scene_pair(he, we, f, make_model(hs, ws, *r["truth"]), r["seed"], r["dtype"])
+    hs, ws = r["hs"], r["ws"]
+    emit, s2 = scene_pair(he, we, f, make_model(hs, ws, *r["truth"]), r["seed"], r["dtype"], hs, ws)
     mask, nodata = None, None
     origins = np.array(r["origins"], np.int32).reshape(-1, 2)
     if r["const"]:                                   # point 0: a constant EMIT window; point 1: a constant S2 region
@@ -222,11 +254,11 @@ def surface_case(name):
         probe, _ = surface_ref_counts(emit, mask, s2, nodata, origins, w, f, R)
         min_valid = int(probe.min()) + (1 if min_valid == "missed" else 0)
     ref, bar = surface_ref(emit, mask, s2, nodata, origins, w, f, R, min_valid)
-    ev, ers, eback = strided(emit, r["extra"], np.float32(np.nan))
-    sv, srs, sback = strided(s2, r["extra"], s2.dtype.type(7))
+    ev, ers, eback = strided(emit, r["pads"][0], np.float32(np.nan))
+    sv, srs, sback = strided(s2, r["pads"][1], s2.dtype.type(7))
     mback, mrs = None, 0
     if mask is not None:
-        _, mrs, mback = strided(mask, r["extra"], np.uint8(1))
+        _, mrs, mback = strided(mask, r["pads"][2], np.uint8(1))
     out = dict(emit=emit, s2=s2, mask=mask, nodata=nodata, origins=origins, min_valid=min_valid, ref=ref, bar=bar,
                emit_back=eback, emit_rs=ers, s2_back=sback, s2_rs=srs, mask_back=mback, mask_rs=mrs, hs=hs, ws=ws)
     for v in out.values():
@@ -377,12 +409,23 @@ PEAK_SHAPES = dict(he=24, we=24, hs=144, ws=144)
 PEAK_SURFACES = _peak_surfaces()
 
 
-def peak_case():
-    """All crafted surfaces as one call: (surface (P, 7, 7), origins, expected status)."""
+# the rectangular set: rows i0 in 1 .. 14 (the S2 bound; EMIT allows 16), columns j0 in 1 .. 22 (the EMIT bound; S2 allows 23)
+PEAK_SHAPES_RECT = dict(he=24, we=30, hs=138, ws=190)
+PEAK_OUTSIDE_RECT = {"outside-top": (0, 5), "outside-bottom": (15, 5), "outside-left": (5, 0), "outside-right": (5, 23)}
+
+
+def peak_case(rect=False):
+    """All crafted surfaces as one call: (names, surface (P, 7, 7), origins, expected status).  rect: on PEAK_SHAPES_RECT, every
+    origin with i0 != j0, and one OUTSIDE record per axis and side, each outside on that axis only."""
     names = list(PEAK_SURFACES)
-    surf = np.stack([PEAK_SURFACES[n][0] for n in names]).astype(np.float64)
-    origins = np.array([(0, 0) if n == "outside" else (3 + k % 5, 2 + k % 7) for k, n in enumerate(names)], np.int32)
-    want = np.array([PEAK_SURFACES[n][1] for n in names])
+    if rect:
+        names = [n for n in names if n != "outside"] + list(PEAK_OUTSIDE_RECT)
+    surf = np.stack([PEAK_SURFACES["outside" if n in PEAK_OUTSIDE_RECT else n][0] for n in names]).astype(np.float64)
+    if rect:
+        origins = np.array([PEAK_OUTSIDE_RECT[n] if n in PEAK_OUTSIDE_RECT else (3 + k % 5, 9 + k % 7) for k, n in enumerate(names)], np.int32)
+    else:
+        origins = np.array([(0, 0) if n == "outside" else (3 + k % 5, 2 + k % 7) for k, n in enumerate(names)], np.int32)
+    want = np.array([OUTSIDE if n in PEAK_OUTSIDE_RECT else PEAK_SURFACES[n][1] for n in names])
     return names, surf, origins, want
 
 
@@ -456,46 +499,53 @@ def _records(points, truth, status=None):
     return t
 
 
-def _grid_points(n=5, lo=47.5, step=48.0):
-    return [(lo + step * i, lo + step * j) for i in range(n) for j in range(n)]
+def _scaled(points, hs, ws):
+    """Points laid out on the 288 x 288 scene, stretched to (hs, ws); unchanged at 288 x 288."""
+    ky, kx = hs / 288.0, ws / 288.0
+    return [(cy * ky, cx * kx) for cy, cx in points]
 
 
-def _with_outlier(delta_sign, reject_px=1.0):
+def _grid_points(n=5, lo=47.5, step=48.0, hs=MODEL_HS, ws=MODEL_WS):
+    return _scaled([(lo + step * i, lo + step * j) for i in range(n) for j in range(n)], hs, ws)
+
+
+def _with_outlier(delta_sign, reject_px=1.0, hs=MODEL_HS, ws=MODEL_WS):
     """The regular grid with exact affine shifts and one record pushed so that its residual after the first fit is reject_px
     times (1 + 1e-3 delta_sign): just outside (+1) or just inside (-1)."""
-    truth = make_model(MODEL_HS, MODEL_WS, 1.25, -2.5, 0.004, -0.003, 0.002, 0.005)
-    base = _records(_grid_points(), truth)
+    truth = make_model(hs, ws, 1.25, -2.5, 0.004, -0.003, 0.002, 0.005)
+    base = _records(_grid_points(hs=hs, ws=ws), truth)
     probe = base.copy()
     probe[7, 2] += 1.0
-    _, m, _, _ = model_ref(probe, 1, 1, 1e9, MODEL_HS, MODEL_WS)
+    _, m, _, _ = model_ref(probe, 1, 1, 1e9, hs, ws)
     dy, dx = shift_field(m, probe[7, 0], probe[7, 1])
     rho = float(np.hypot(probe[7, 2] - dy, probe[7, 3] - dx))           # the residual of a unit push (linear in the push)
     base[7, 2] += reject_px * (1.0 + 1e-3 * delta_sign) / rho
     return base
 
 
-def _model_rows():
-    truth = make_model(MODEL_HS, MODEL_WS, 1.25, -2.5, 0.004, -0.003, 0.002, 0.005)
-    shift = make_model(MODEL_HS, MODEL_WS, -0.75, 3.5)
-    grid = _grid_points()
+def _model_rows(hs=MODEL_HS, ws=MODEL_WS):
+    """The rows on a (hs, ws) scene: the same truths, the tables rebuilt from them at that shape."""
+    truth = make_model(hs, ws, 1.25, -2.5, 0.004, -0.003, 0.002, 0.005)
+    shift = make_model(hs, ws, -0.75, 3.5)
+    grid = _grid_points(hs=hs, ws=ws)
     rows = {}
     rows["affine-grid"] = dict(table=_records(grid, truth), kind=1, kind_used=1, n_used=25)
     rows["translation-grid"] = dict(table=_records(grid, shift), kind=0, kind_used=0, n_used=25)
     rows["translation-of-affine"] = dict(table=_records(grid, truth), kind=0, kind_used=0, reject_px=5.0, n_used=25)
-    rows["outlier-outside"] = dict(table=_with_outlier(+1), kind=1, kind_used=1, n_used=24, outliers=[7])
-    rows["outlier-inside"] = dict(table=_with_outlier(-1), kind=1, kind_used=1, n_used=25)
+    rows["outlier-outside"] = dict(table=_with_outlier(+1, hs=hs, ws=ws), kind=1, kind_used=1, n_used=24, outliers=[7])
+    rows["outlier-inside"] = dict(table=_with_outlier(-1, hs=hs, ws=ws), kind=1, kind_used=1, n_used=25)
     far = _records(grid, truth)
     far[3, 2:4] += (1.8, -2.4)
     far[20, 2:4] -= (2.0, 2.0)
     rows["two-outliers"] = dict(table=far, kind=1, kind_used=1, n_used=23, outliers=[3, 20])
     rows["two-outliers-translation"] = dict(table=_with_far(shift, grid), kind=0, kind_used=0, n_used=23, outliers=[3, 20])
-    line = [(47.5 + 30.0 * k, 20.5 + 15.0 * k) for k in range(8)]
+    line = _scaled([(47.5 + 30.0 * k, 20.5 + 15.0 * k) for k in range(8)], hs, ws)
     rows["collinear"] = dict(table=_records(line, shift), kind=1, kind_used=0, n_used=8)
-    column = [(47.5 + 30.0 * k, 100.5) for k in range(6)]
+    column = _scaled([(47.5 + 30.0 * k, 100.5) for k in range(6)], hs, ws)
     rows["collinear-column"] = dict(table=_records(column, shift), kind=1, kind_used=0, n_used=6)
     for n_ok in (0, 1, 2, 3):
         st = [OK if k < n_ok else (LOW_SCORE, BORDER, OUTSIDE, NO_SCORE)[k % 4] for k in range(9)]
-        pts = [(40.5, 30.5), (200.5, 60.5), (90.5, 250.5)] + _grid_points(3)[3:]
+        pts = _scaled([(40.5, 30.5), (200.5, 60.5), (90.5, 250.5)], hs, ws) + _grid_points(3, hs=hs, ws=ws)[3:]
         t = _records(pts, truth, st)
         t[n_ok:, 2:4] = 0.0
         rows[f"ok-{n_ok}"] = dict(table=t, kind=1, kind_used=-1 if n_ok == 0 else (1 if n_ok == 3 else 0), n_used=n_ok)
@@ -504,12 +554,33 @@ def _model_rows():
     rows["min-points-met"] = dict(table=_records(grid, truth), kind=1, min_points=25, kind_used=1, n_used=25)
     # the rejection leaves fewer than min_points: the second pass gives the zero model
     rows["min-points-after-rejection"] = dict(table=far.copy(), kind=1, min_points=24, kind_used=-1, n_used=0, outliers=[3, 20])
+    return _finish_model_rows(rows, hs, ws)
+
+
+def _finish_model_rows(rows, hs, ws):
     for r in rows.values():
         r.setdefault("min_points", 1)
         r.setdefault("reject_px", 1.0)
         r.setdefault("outliers", [])
+        r.setdefault("hs", hs)
+        r.setdefault("ws", ws)
         r["table"].setflags(write=False)
     return rows
+
+
+def _clamp_rows():
+    """Scenes one, two or three pixels across: xc = (ws - 1) / 2 <= 1 or yc <= 1, so the fit scales that axis by max(.., 1) = 1.
+    The records are a 5 x 5 grid about the scene centre; the fit takes records as they come, inside the scene or not."""
+    rows = {}
+    for hs, ws in ((200, 1), (200, 3), (2, 344), (2, 1)):
+        truth = make_model(hs, ws, 1.25, -2.5, 0.004, -0.003, 0.002, 0.005)
+        sy, sx = max(hs, 6) / 6.0, max(ws, 6) / 6.0
+        pts = [(truth[7] + sy * (i - 2), truth[6] + sx * (j - 2)) for i in range(5) for j in range(5)]
+        rows[f"clamp-{hs}x{ws}"] = dict(table=_records(pts, truth), kind=1, kind_used=1, n_used=25, hs=hs, ws=ws)
+        far = _records(pts, truth)
+        far[3, 2:4] += (1.8, -2.4)
+        rows[f"clamp-{hs}x{ws}-outlier"] = dict(table=far, kind=1, kind_used=1, n_used=24, outliers=[3], hs=hs, ws=ws)
+    return _finish_model_rows(rows, None, None)
 
 
 def _with_far(shift, grid):
@@ -520,6 +591,8 @@ def _with_far(shift, grid):
 
 
 MODEL_ROWS = _model_rows()
+MODEL_RECT = (200, 344)                            # xc != yc and hx != hy
+MODEL_ROWS_ALL = dict(MODEL_ROWS, **{"rect-" + k: v for k, v in _model_rows(*MODEL_RECT).items()}, **_clamp_rows())
 
 
 # =============================================================================================================================
@@ -580,9 +653,19 @@ def warp_instance(dtype, slope_bound):
 
 # name: dtype, bands, h, w, model terms, bad (none | nan | nodata), bound (max_abs_shift, max_abs_slope), off (base misalignment,
 # bytes), extra (row-stride padding), fill, status (what the device-side check of the bound must say)
-def _wrow(dtype, bands, h, w, model, bad="none", bound=(13.0, 0.05), off=0, extra=0, fill=None, status=0, kind="texture"):
+#   out_off, out_extra: the same two of the output, default the input's.  in_gap, out_gap: elements between the bands, so that the
+#   band stride is h rs + gap.  centre: (xc, yc) of the model, default the centre of the scene that is warped
+def _wrow(dtype, bands, h, w, model, bad="none", bound=(13.0, 0.05), off=0, extra=0, fill=None, status=0, kind="texture",
+          out_off=None, out_extra=None, in_gap=0, out_gap=0, centre=None):
     return dict(dtype=dtype, bands=bands, h=h, w=w, model=model, bad=bad, bound=bound, off=off, extra=extra, fill=fill, status=status,
-                kind=kind)
+                kind=kind, out_off=off if out_off is None else out_off, out_extra=extra if out_extra is None else out_extra,
+                in_gap=in_gap, out_gap=out_gap, centre=centre)
+
+
+_STEEP = dict(dy0=0.8, dx0=-1.1, dy_x=0.3, dy_y=-0.2, dx_x=0.25, dx_y=0.3)
+_OFF_CENTRE = (299.5, 209.5)                       # the centre of a 420 x 600 scene, of which the rows warp a 50 x 131 corner
+WARP_TILE_W, WARP_TILE_H = (63, 64, 65, 128), (15, 16, 17, 32)
+WARP_THIN = ((1, 1), (1, 70), (40, 1), (2, 3), (3, 2))
 
 
 WARP_ROWS = {
@@ -606,7 +689,33 @@ WARP_ROWS = {
     "bound-exceeded": _wrow("f32", 1, 50, 131, dict(dy0=0.8, dx0=-1.1, dy_x=0.3, dy_y=-0.2, dx_x=0.25, dx_y=0.3), bad="nan", status=1),
     "shift-bound-exceeded": _wrow("u16", 1, 30, 40, dict(dy0=14.0), status=1),
     "nan-model": _wrow("f32", 1, 20, 30, dict(dy0=float("nan")), status=1),
+    # the output with a row stride, a band stride and a base offset of its own; gaps between the bands on one side or on both
+    "strides-lds": _wrow("f32", 2, 40, 70, dict(dy0=1.25, dx0=-0.75), bad="nan", off=4, extra=3, out_off=12, out_extra=7, in_gap=5,
+                         out_gap=9),
+    "strides-direct": _wrow("f32", 2, 37, 67, _STEEP, bad="nan", bound=(80.0, 2.0), off=8, extra=2, out_off=4, out_extra=5, out_gap=11),
+    "strides-u16-lds": _wrow("u16", 3, 40, 67, dict(dy0=0.375, dx0=-1.5), bad="nodata", off=2, extra=1, out_off=6, out_extra=4, in_gap=7),
+    "strides-u16-direct": _wrow("u16", 2, 37, 70, dict(dy0=1.5, dx0=2.5, dx_x=0.5), bad="nodata", bound=(40.0, 2.0), off=6, extra=5,
+                                out_off=2, out_extra=2, in_gap=3, out_gap=1),
+    # a model centred on a larger scene: m[6], m[7] are not ((w - 1) / 2, (h - 1) / 2)
+    "off-centre": _wrow("f32", 2, 50, 131, dict(dy0=0.8, dx0=-1.1, dy_x=0.01, dy_y=-0.02, dx_x=0.015, dx_y=0.012), bad="nan",
+                        centre=_OFF_CENTRE),
+    "off-centre-direct": _wrow("u16", 2, 50, 131, dict(dy0=0.5, dx0=1.0, dy_x=0.05, dy_y=-0.04, dx_x=0.06, dx_y=0.03), bad="nodata",
+                               bound=(80.0, 2.0), centre=_OFF_CENTRE),
+    # extents at a multiple of the 64 x 16 tile, one less and one more
+    "tile-15x63": _wrow("f32", 2, 15, 63, dict(dy0=0.6, dx0=-1.3), bad="nan"),
+    "tile-16x64": _wrow("f32", 2, 16, 64, dict(dy0=-0.6, dx0=1.3), bad="nan"),
+    "tile-17x65": _wrow("u16", 2, 17, 65, dict(dy0=0.6, dx0=-1.3), bad="nodata"),
+    "tile-32x128": _wrow("f32", 2, 32, 128, dict(dy0=-1.6, dx0=0.3), bad="nodata"),
+    "tile-16x65-direct": _wrow("f32", 2, 16, 65, dict(dy0=0.6, dx0=-1.3, dx_y=0.2), bound=(40.0, 2.0)),
 }
+# planes thinner than the four taps: every tap clamps.  A fractional shift along the axes longer than one pixel, small enough that
+# some pixels stay inside, and an integer one; a 1 x 1 plane has the zero shift alone to stay inside
+for _h, _w in WARP_THIN:
+    _dt = "u16" if (_h, _w) in ((40, 1), (3, 2)) else "f32"
+    WARP_ROWS[f"thin-{_h}x{_w}-frac"] = _wrow(_dt, 2, _h, _w, dict(dy0=0.25 if _h > 1 else 0.0, dx0=-0.375 if _w > 1 else 0.0))
+    WARP_ROWS[f"thin-{_h}x{_w}-int"] = _wrow(_dt, 2, _h, _w, dict(dy0=1.0 if _h > 1 else 0.0, dx0=-1.0 if _w > 1 else 0.0))
+WARP_ROWS["thin-1x1-outside"] = _wrow("f32", 1, 1, 1, dict(dx0=0.25))
+WARP_ROWS["thin-2x3-direct"] = _wrow("u16", 2, 2, 3, dict(dy0=0.25, dx0=-0.375), bound=(13.0, 2.0))
 
 
 @functools.lru_cache(maxsize=None)
@@ -636,6 +745,8 @@ def warp_case(name):
     terms = dict(r["model"])
     kind = terms.pop("kind", 1)
     model = make_model(h, w, kind=kind, **terms)
+    if r["centre"] is not None:
+        model[6], model[7] = r["centre"]
     if kind == -1:
         model[:] = 0.0
         model[9] = -1.0
@@ -648,11 +759,21 @@ def warp_case(name):
     return out
 
 
-def pack_scene(scene, extra, sentinel):
-    """(bands, h, w + extra) backing array holding `scene`, the padding filled with `sentinel`."""
-    back = np.full(scene.shape[:2] + (scene.shape[2] + extra,), sentinel, dtype=scene.dtype)
-    back[:, :, :scene.shape[2]] = scene
+def pack_scene(scene, extra, sentinel, gap=0):
+    """(bands, h (w + extra) + gap) backing array holding `scene` in rows of w + extra elements, the row padding and the gap after
+    every band filled with `sentinel`; band b of the scene is unpack_scene(back, h, w, extra)[b]."""
+    bands, h, w = scene.shape
+    back = np.full((bands, h * (w + extra) + gap), sentinel, dtype=scene.dtype)
+    back[:, :h * (w + extra)].reshape(bands, h, w + extra)[:, :, :w] = scene
     return back
+
+
+def unpack_scene(back, h, w, extra):
+    """(the (bands, h, w) payload of a pack_scene array, a mask of its elements outside the payload)."""
+    rows = back[:, :h * (w + extra)].reshape(back.shape[0], h, w + extra)
+    outside = np.ones(back.shape, bool)
+    outside[:, :h * (w + extra)].reshape(back.shape[0], h, w + extra)[:, :, :w] = False
+    return rows[:, :, :w], outside
 
 
 # =============================================================================================================================
@@ -666,26 +787,31 @@ E2E_MODELS = {
 DECOY = 12                                         # the tie point whose EMIT window is replaced by one (-4, +3) S2 pixels off
 
 
-def e2e_origins():
-    he, f, w, R, step = E2E["he"], E2E["f"], E2E["w"], E2E["R"], E2E["step"]
+# a rectangular pair: he != we, and an S2 scene five rows longer than f he
+E2E_RECT = dict(E2E, he=48, we=60, hs=48 * 6 + 5, ws=60 * 6, seed=22)
+
+
+def e2e_origins(p=E2E):
+    he, we, f, w, R, step = p["he"], p["we"], p["f"], p["w"], p["R"], p["step"]
+    hs, ws = p.get("hs", he * f), p.get("ws", we * f)
     inset = -(-R // f)
-    hi = min(he - w, (he * f - R - f * w) // f)
-    ax = np.arange(inset, hi + 1, step)
-    return np.stack(np.meshgrid(ax, ax, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.int32)
+    ai = np.arange(inset, min(he - w, (hs - R - f * w) // f) + 1, step)
+    aj = np.arange(inset, min(we - w, (ws - R - f * w) // f) + 1, step)
+    return np.stack(np.meshgrid(ai, aj, indexing="ij"), axis=-1).reshape(-1, 2).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=None)
-def e2e_case(name, dtype="f32"):
+def e2e_case(name, dtype="f32", rect=False):
     """The scene pair with a planted decoy, the reference chain (surface -> peaks -> model) and the truth."""
-    p = dict(E2E)
+    p = dict(E2E_RECT if rect else E2E)
     he, we, f, R = p["he"], p["we"], p["f"], p["R"]
-    hs, ws = he * f, we * f
+    hs, ws, seed = p.get("hs", he * f), p.get("ws", we * f), p.get("seed", 21)
     truth = make_model(hs, ws, **E2E_MODELS[name])
-    emit, s2 = scene_pair(he, we, f, truth, 21, dtype)
-    origins = e2e_origins()
+    emit, s2 = scene_pair(he, we, f, truth, seed, dtype, hs, ws)
+    origins = e2e_origins(p)
     i0, j0 = origins[DECOY]
     off = make_model(hs, ws, truth[0] - 4.0, truth[3] + 3.0, *truth[[1, 2, 4, 5]])
-    decoy, _ = scene_pair(he, we, f, off, 21, dtype)
+    decoy, _ = scene_pair(he, we, f, off, seed, dtype, hs, ws)
     emit[i0:i0 + p["w"], j0:j0 + p["w"]] = decoy[i0:i0 + p["w"], j0:j0 + p["w"]]
     min_valid = int(np.ceil(p["min_valid_frac"] * p["w"] ** 2))
     surf, bar = surface_ref(emit, None, s2, None, origins, p["w"], f, R, min_valid)
@@ -693,6 +819,37 @@ def e2e_case(name, dtype="f32"):
     table, model, coef, mbar = model_ref(table0, 1 if name == "affine" else 0, 1, p["reject_px"], hs, ws)
     out = dict(emit=emit, s2=s2, origins=origins, truth=truth, surface=surf, bar=bar, table0=table0, table=table, model=model,
                coef=coef, model_bar=mbar, min_valid=min_valid, hs=hs, ws=ws, params=p)
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def masked_case(dtype="f32"):
+    """The rectangular translation pair with an EMIT mask and S2 nodata: one window wholly masked, one half masked, a masked
+    stripe through others, a nodata rectangle in the S2 scene (NaN and inf beside it for float32), and the reference chain under
+    them.  (emit, mask uint8, s2, nodata, origins, surface, bar, table0, min_valid, params)."""
+    c = e2e_case("translation", dtype, True)
+    p = c["params"]
+    emit, s2, origins = c["emit"].copy(), c["s2"].copy(), c["origins"]
+    nodata = NODATA_U16 if dtype == "u16" else NODATA_F32
+    s2[np.equal(s2, nodata)] = 1
+    s2[150:200, 100:130] = nodata
+    if dtype == "f32":
+        s2[150:200, 130:136] = np.nan
+        s2[210, 260] = np.inf
+    mask = np.ones(emit.shape, np.uint8)
+    i0, j0 = origins[9]
+    mask[i0:i0 + p["w"], j0:j0 + p["w"]] = 0                 # a whole window
+    i0, j0 = origins[3]
+    mask[i0:i0 + p["w"], j0:j0 + 4] = 0                      # half a window: fewer pairs than min_valid
+    mask[40:42, :] = 0                                       # a stripe through the last row of windows: still enough pairs
+    mask[mask != 0] = 1 + (np.arange(int(mask.sum())) % 250).astype(np.uint8)
+    surf, bar = surface_ref(emit, mask, s2, nodata, origins, p["w"], p["f"], p["R"], c["min_valid"])
+    table0 = peaks_ref(surf, origins, p["w"], p["f"], p["R"], p["he"], p["we"], c["hs"], c["ws"], p["min_score"])
+    out = dict(emit=emit, mask=mask, s2=s2, nodata=nodata, origins=origins, surface=surf, bar=bar, table0=table0,
+               min_valid=c["min_valid"], params=p, hs=c["hs"], ws=c["ws"])
     for v in out.values():
         if isinstance(v, np.ndarray):
             v.setflags(write=False)

@@ -228,41 +228,58 @@ def test_closest_band_and_argument_checks():
 
 
 # ---- the fit's host twin ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(cc.MODEL_ROWS))
+@pytest.mark.parametrize("name", list(cc.MODEL_ROWS_ALL))
 def test_fit_model_host(name):
-    r = cc.MODEL_ROWS[name]
-    want_t, want_m, coef, bar = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], cc.MODEL_HS, cc.MODEL_WS)
-    t, m = eng.coreg_fit_model_host(r["table"], r["kind"], r["min_points"], r["reject_px"], (cc.MODEL_HS, cc.MODEL_WS))
+    r = cc.MODEL_ROWS_ALL[name]
+    hs, ws = r["hs"], r["ws"]
+    want_t, want_m, coef, bar = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], hs, ws)
+    t, m = eng.coreg_fit_model_host(r["table"], r["kind"], r["min_points"], r["reject_px"], (hs, ws))
     assert np.array_equal(t[:, 7], want_t[:, 7]) and np.array_equal(t[:, 2:4], want_t[:, 2:4])
     assert (m[9], m[8]) == (want_m[9], want_m[8]) == (r["kind_used"], r["n_used"])
-    diff = np.abs(cc.scaled_coefficients(m, cc.MODEL_HS, cc.MODEL_WS) - coef).max()
-    print(f"{name}: diff {diff:.3g}, bar {bar:.3g}")
+    diff = np.abs(cc.scaled_coefficients(m, hs, ws) - coef).max()
+    print(f"{name}: diff {diff:.3g}, bar {bar:.3g}, |err| / bar {diff / bar if bar else 0.0:.3g}")
     assert diff <= bar
     if m[9] < 0:
         assert not m[:9].any()
     else:
-        assert (m[6], m[7]) == (0.5 * (cc.MODEL_WS - 1), 0.5 * (cc.MODEL_HS - 1))
+        assert (m[6], m[7]) == (0.5 * (ws - 1), 0.5 * (hs - 1))
     if m[9] < 1:
         assert not m[[1, 2, 4, 5]].any()
 
 
-@pytest.mark.parametrize("name", list(cc.MODEL_ROWS))
+@pytest.mark.parametrize("name", list(cc.MODEL_ROWS_ALL))
 def test_model_row_claims(name):
-    r = cc.MODEL_ROWS[name]
-    t, m, _, _ = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], cc.MODEL_HS, cc.MODEL_WS)
+    r = cc.MODEL_ROWS_ALL[name]
+    hs, ws = r["hs"], r["ws"]
+    t, m, coef, bar = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], hs, ws)
     assert list(np.flatnonzero(t[:, 7] == cc.OUTLIER)) == r["outliers"] and (m[9], m[8]) == (r["kind_used"], r["n_used"])
     assert not t[t[:, 7] != cc.OK, 2:4].any()
-    if name.startswith("outlier-"):
+    if "outlier-outside" in name or "outlier-inside" in name:
         # the pushed record's residual after the first fit lies within 1e-3 of reject_px, on the side the name says
-        first = cc._fit_ref(np.array(r["table"]), r["kind"], 1, cc.MODEL_HS, cc.MODEL_WS)[0]
+        first = cc._fit_ref(np.array(r["table"]), r["kind"], 1, hs, ws)[0]
         rec = r["table"][7]
         dy, dx = cc.shift_field(first, rec[0], rec[1])
         res = np.hypot(rec[2] - dy, rec[3] - dx)
-        assert abs(res / r["reject_px"] - 1) < 2e-3 and (res > r["reject_px"]) == (name == "outlier-outside")
-    if name.startswith("collinear"):
-        use, X, _ = cc._design(np.array(r["table"]), cc.MODEL_HS, cc.MODEL_WS)
+        assert abs(res / r["reject_px"] - 1) < 2e-3 and (res > r["reject_px"]) == name.endswith("outlier-outside")
+    if "collinear" in name:
+        use, X, _ = cc._design(np.array(r["table"]), hs, ws)
         ev = np.linalg.eigvalsh(X.T @ X)
         assert ev[0] < 1e-12 * ev[-1] and use.sum() >= 3
+    if name.startswith("rect-"):
+        # the same truths as the square row, the table rebuilt at the rectangular shape
+        sq = cc.MODEL_ROWS[name[5:]]
+        assert (hs, ws) == cc.MODEL_RECT and all(r[k] == sq[k] for k in ("kind", "kind_used", "n_used", "outliers", "min_points"))
+        assert len(r["table"]) == len(sq["table"]) and np.array_equal(r["table"][:, 7], sq["table"][:, 7])
+        if r["kind_used"] == 1:
+            # a fit that exchanged hs and ws leaves the bar: the reference of the exchanged shape, in this shape's scaled coefficients
+            _, swapped, _, _ = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], ws, hs)
+            off = np.abs(cc.scaled_coefficients(swapped, hs, ws) - coef).max()
+            assert off > 1e6 * bar and (swapped[6], swapped[7]) == (m[7], m[6]) != (m[6], m[7])
+    if name.startswith("clamp-"):
+        xc, yc = 0.5 * (ws - 1), 0.5 * (hs - 1)
+        assert min(xc, yc) <= 1.0 and (m[6], m[7]) == (xc, yc) and m[[1, 2, 4, 5]].all()
+        _, X, (_, _, hx, hy) = cc._design(np.array(r["table"]), hs, ws)
+        assert (hx, hy) == (max(xc, 1.0), max(yc, 1.0)) and 1.0 in (hx, hy) and np.ptp(X[:, 1]) > 0 and np.ptp(X[:, 2]) > 0
 
 
 def test_model_rows_cover_the_classes():
@@ -271,6 +288,14 @@ def test_model_rows_cover_the_classes():
     assert {int((r["table"][:, 7] == cc.OK).sum()) if len(r["table"]) else 0 for r in R.values()} >= {0, 1, 2, 3, 25}
     assert any(r["outliers"] and r["kind_used"] == k for r in R.values() for k in (-1, 0, 1))
     assert {"outlier-inside", "outlier-outside", "collinear", "min-points-unmet", "no-records"} <= set(R)
+    A = cc.MODEL_ROWS_ALL
+    assert all((r["hs"], r["ws"]) == (cc.MODEL_HS, cc.MODEL_WS) for r in R.values()) and all(A[n] is R[n] for n in R)
+    assert {n[5:] for n in A if n.startswith("rect-")} == set(R) and cc.MODEL_RECT[0] != cc.MODEL_RECT[1]
+    assert all(abs(v - round(v)) == 0.5 for v in (0.5 * (cc.MODEL_RECT[0] - 1), 0.5 * (cc.MODEL_RECT[1] - 1)))      # xc != yc, hx != hy
+    clamp = {(r["hs"], r["ws"]) for n, r in A.items() if n.startswith("clamp-")}
+    assert clamp == {(200, 1), (200, 3), (2, 344), (2, 1)}                # xc = 0 and xc = 1 (the clamp's edge), yc = 0.5, both axes
+    assert any(r["outliers"] for n, r in A.items() if n.startswith("clamp-"))
+    assert len(A) == 2 * len(R) + 2 * len(clamp)
 
 
 # ---- the surface table ---------------------------------------------------------------------------------------------------------------
@@ -290,6 +315,10 @@ def test_surface_row_conditions(name):
     assert (status[~inside] == cc.OUTSIDE).all() and (status[inside] != cc.OUTSIDE).all()
     if name == "edges":
         assert list(inside) == cc.EDGES_INSIDE and (status[inside] == cc.OK).all()
+    elif r["inside"] is not None:
+        # origins on both sides of the region test: the test says what the row says, and the inside ones recover the planted shift
+        assert list(inside) == r["inside"] and fin[inside].all() and (status[inside] == cc.OK).all()
+        assert (np.abs(table[inside, 2:4] - np.array(r["truth"])) <= 0.5).all(), table[inside, 2:4]
     elif r["mask"] == "all" or r["const"]:
         assert not fin.any() and (status == cc.NO_SCORE).all()
     elif name == "min-valid-missed":
@@ -307,11 +336,87 @@ def test_surface_row_conditions(name):
         assert c["mask"].min() == 0 and c["mask"].max() > 1 and (~cc.s2_valid(c["s2"], c["nodata"])).sum() > 100
     if r["extra"]:
         assert c["emit_rs"] > r["we"] and c["s2_rs"] > c["ws"] and np.array_equal(c["s2_back"][:, :c["ws"]], c["s2"])
+    assert (c["hs"], c["ws"]) == c["s2"].shape == (r["hs"], r["ws"]) and c["emit"].shape == (r["he"], r["we"])
+    assert (c["emit_rs"], c["s2_rs"]) == (r["we"] + r["pads"][0], r["ws"] + r["pads"][1])
+    if c["mask"] is not None:
+        assert c["mask_rs"] == r["we"] + r["pads"][2] and np.array_equal(c["mask_back"][:, :r["we"]], c["mask"])
+
+
+OWN_STRIDES = [n for n, r in cc.SURFACE_ROWS.items() if len(set(r["pads"])) == 3 and 0 not in r["pads"]]
+STRADDLING = ("edges-rect", "s2-short-wide", "s2-tall-narrow")
+
+
+@pytest.mark.parametrize("name", STRADDLING)
+def test_region_rows_see_swapped_extents(name):
+    """The inside list of these rows changes when he <-> we, and when hs <-> ws, are exchanged in the region test."""
+    r = cc.SURFACE_ROWS[name]
+    assert len({r["he"], r["we"], r["hs"] // r["f"], r["ws"] // r["f"]}) == 4
+
+    def inside(he, we, hs, ws):
+        return [cc.region_inside(i, j, r["w"], r["f"], r["R"], he, we, hs, ws) for i, j in r["origins"]]
+
+    assert inside(r["he"], r["we"], r["hs"], r["ws"]) == r["inside"] and True in r["inside"] and False in r["inside"]
+    assert inside(r["we"], r["he"], r["hs"], r["ws"]) != r["inside"]
+    assert inside(r["he"], r["we"], r["ws"], r["hs"]) != r["inside"]
+    if name != "edges-rect":
+        # which of the two bounds decides: on one axis an origin passes the EMIT bound and fails the S2 bound, on the other the reverse
+        big = 10 ** 6
+        emit_only, s2_only = inside(r["he"], r["we"], big, big), inside(big, big, r["hs"], r["ws"])
+        a, b = r["origins"][3], r["origins"][6]                    # the first outside origin along each axis, the other coordinate at 4
+        assert (a[0] == 4) != (a[1] == 4) and (b[0] == 4) != (b[1] == 4) and (a[0] == 4) != (b[0] == 4)
+        assert {(emit_only[3], s2_only[3]), (emit_only[6], s2_only[6])} == {(True, False), (False, True)}
+
+
+def _restrided(back, rs, shape, sentinel):
+    """The (h, w) plane that a reader with row stride `rs` sees at the base of `back` (past its end: `sentinel`)."""
+    flat = back.reshape(-1)
+    need = (shape[0] - 1) * rs + shape[1]
+    if need > flat.size:
+        flat = np.concatenate([flat, np.full(need - flat.size, sentinel, flat.dtype)])
+    return np.lib.stride_tricks.as_strided(flat, shape, (rs * flat.itemsize, flat.itemsize), writeable=False)
+
+
+@pytest.mark.parametrize("name", OWN_STRIDES)
+def test_stride_rows_see_exchanged_strides(name):
+    """The reference from the backing arrays under exchanged row strides - the mask read with emit_rs; emit_rs <-> s2_rs - leaves
+    the bar of the row's own reference somewhere (or its NaN pattern)."""
+    r, c = cc.SURFACE_ROWS[name], cc.surface_case(name)
+    assert c["mask"] is not None and len({c["emit_rs"] - r["we"], c["s2_rs"] - r["ws"], c["mask_rs"] - r["we"]}) == 3
+    assert len(set(r["offs"])) == 3
+    eshape, sshape = c["emit"].shape, c["s2"].shape
+    nan, seven, one = np.float32(np.nan), c["s2"].dtype.type(7), np.uint8(1)
+
+    def ref(ers, srs, mrs):
+        return cc.surface_ref(_restrided(c["emit_back"], ers, eshape, nan), _restrided(c["mask_back"], mrs, eshape, one),
+                              _restrided(c["s2_back"], srs, sshape, seven), c["nodata"], c["origins"], r["w"], r["f"], r["R"], c["min_valid"])[0]
+
+    def differs(got):
+        fin = np.isfinite(c["ref"])
+        if not np.array_equal(np.isfinite(got), fin):
+            return True
+        return bool((np.abs(got[fin] - c["ref"][fin]) > c["bar"][fin]).any())
+
+    assert not differs(ref(c["emit_rs"], c["s2_rs"], c["mask_rs"]))                              # the backing arrays hold the case
+    assert differs(ref(c["emit_rs"], c["s2_rs"], c["emit_rs"]))                                  # the mask indexed with emit_rs
+    assert differs(ref(c["s2_rs"], c["emit_rs"], c["mask_rs"]))                                  # emit_rs <-> s2_rs
+    assert differs(ref(c["s2_rs"], c["s2_rs"], c["mask_rs"])) and differs(ref(c["emit_rs"], c["emit_rs"], c["mask_rs"]))
 
 
 def test_surface_rows_cover_the_bounds():
     R = cc.SURFACE_ROWS.values()
-    assert {r["w"] for r in R} == {4, 8, 9, 32, 64} and {r["R"] for r in R} == {1, 3, 6, 7, 12, 24} and {r["f"] for r in R} == {1, 2, 6}
+    assert {r["w"] for r in R} == {4, 8, 9, 32, 64} and {r["R"] for r in R} == {1, 3, 4, 5, 6, 7, 8, 9, 12, 24}
+    assert {r["f"] for r in R} == {1, 2, 3, 4, 5, 6, 7, 8}
+    rect = [r for r in R if r["he"] != r["we"]]
+    assert {r["f"] for r in rect} == {3, 4, 5, 6, 7, 8} and {r["dtype"] for r in rect} == {"f32", "u16"}
+    assert any(r["he"] > r["we"] for r in rect) and any(r["he"] < r["we"] for r in rect) and {r["w"] for r in rect} == {8, 9}
+    assert {(r["R"] < r["f"], r["R"] == r["f"], r["R"] > r["f"]) for r in rect} == {(True, False, False), (False, True, False), (False, False, True)}
+    assert any((r["f"], r["R"]) == (8, 24) for r in rect)
+    assert len(OWN_STRIDES) >= 2 and {cc.SURFACE_ROWS[n]["dtype"] for n in OWN_STRIDES} == {"f32", "u16"}
+    off_f = [r for r in R if (r["hs"], r["ws"]) != (r["he"] * r["f"], r["we"] * r["f"])]
+    assert any(r["hs"] < r["he"] * r["f"] and r["ws"] > r["we"] * r["f"] for r in off_f)
+    assert any(r["hs"] > r["he"] * r["f"] and r["ws"] < r["we"] * r["f"] for r in off_f)
+    assert all(r["hs"] <= 384 and r["ws"] <= 384 for r in R)
+    assert all(abs(t % 1.0 - 0.5) > 0.05 for r in rect for t in r["truth"])                      # no planted shift at x.5: two candidates tie
     assert {len(r["origins"]) for r in R} >= {1, 2, 65}
     assert {(r["R"] < r["f"], r["R"] == r["f"], r["R"] > r["f"]) for r in R} == {(True, False, False), (False, True, False), (False, False, True)}
     assert {r["dtype"] for r in R} == {"f32", "u16"} and {r["mask"] for r in R} == {"none", "part", "all"}
@@ -337,6 +442,38 @@ def test_peak_rows_claim_their_status():
     assert rec["inf-entry"][6] == 48 and rec["nan-diagonal"][7] == cc.OK
     assert not table[want != cc.OK, 2:4].any()
     assert (table[:, 0] == cc.PEAK_F * (origins[:, 0] + cc.PEAK_W / 2) - 0.5).all()
+
+
+def test_rect_peak_rows_claim_their_status():
+    """The crafted surfaces on a rectangular pair of planes: the same records but for cy, cx; one OUTSIDE record per axis and side,
+    each outside on that axis alone; cy follows i0 and cx follows j0 on origins with i0 != j0."""
+    names, surf, origins, want = cc.peak_case(rect=True)
+    sq_names, _, sq_origins, _ = cc.peak_case()
+    sh = cc.PEAK_SHAPES_RECT
+    assert len({sh["he"], sh["we"], sh["hs"] // cc.PEAK_F, sh["ws"] // cc.PEAK_F}) == 4
+    table = cc.peaks_ref(surf, origins, cc.PEAK_W, cc.PEAK_F, cc.PEAK_R, min_score=cc.PEAK_MIN_SCORE, **sh)
+    assert np.array_equal(table[:, 7], want), dict(zip(names, table[:, 7]))
+    assert (origins[:, 0] != origins[:, 1]).all()
+    assert (table[:, 0] == cc.PEAK_F * (origins[:, 0] + cc.PEAK_W / 2) - 0.5).all()
+    assert (table[:, 1] == cc.PEAK_F * (origins[:, 1] + cc.PEAK_W / 2) - 0.5).all() and (table[:, 0] != table[:, 1]).all()
+    square = dict(zip(sq_names, cc.peaks_ref(cc.peak_case()[1], sq_origins, cc.PEAK_W, cc.PEAK_F, cc.PEAK_R, min_score=cc.PEAK_MIN_SCORE,
+                                             **cc.PEAK_SHAPES)))
+    for n, rec in zip(names, table):
+        if n not in cc.PEAK_OUTSIDE_RECT:
+            assert np.array_equal(rec[2:], square[n][2:], equal_nan=True), n
+
+    def inside(i0, j0, **kw):
+        return cc.region_inside(i0, j0, cc.PEAK_W, cc.PEAK_F, cc.PEAK_R, **dict(sh, **kw))
+
+    assert set(cc.PEAK_OUTSIDE_RECT) == {"outside-top", "outside-bottom", "outside-left", "outside-right"}
+    for n, (i0, j0) in cc.PEAK_OUTSIDE_RECT.items():
+        rows = n in ("outside-top", "outside-bottom")
+        assert not inside(i0, j0) and inside(5, j0) == rows and inside(i0, 5) == (not rows) and inside(5, 5)
+        step = -1 if n in ("outside-bottom", "outside-right") else 1
+        assert inside(i0 + step, j0) if rows else inside(i0, j0 + step)                         # the first origin past the bound
+    # the bottom bound is the S2 plane's, the right one the EMIT plane's: exchanged extents admit or refuse other origins
+    assert inside(15, 5, hs=10 ** 6) and not inside(15, 5, he=10 ** 6) and inside(5, 23, we=10 ** 6) and not inside(5, 23, ws=10 ** 6)
+    assert inside(15, 5, hs=sh["ws"], ws=sh["hs"]) and inside(5, 23, he=sh["we"], we=sh["he"]) is False
 
 
 # ---- the warp table --------------------------------------------------------------------------------------------------------------------
@@ -375,8 +512,22 @@ def test_warp_row_claims(name):
         assert fill[0].all() != fill[-1].all() and fill[:, 0].all() != fill[:, -1].all() and not fill.all()
     if name in ("wholly-outside", "nan-model"):
         assert np.isnan(raw).all()
-    if "affine" in name or "direct" in name:
+    if name in ("affine", "affine-u16", "direct", "direct-u16", "strides-direct", "strides-u16-direct") or name.startswith("off-centre"):
         assert m[[1, 2, 4, 5]].any()
+    if r["centre"] is not None:
+        # a warp that took the centre from the scene it warps gives another output
+        assert (m[6], m[7]) == r["centre"] != (0.5 * (w - 1), 0.5 * (h - 1)) and m[[1, 2, 4, 5]].all()
+        own = cc.make_model(h, w, **r["model"])
+        other, _ = cc.warp_ref(scene, own, c["nodata"], c["fill"])
+        assert (other != ref).mean() > 0.5 and np.isfinite(raw).mean() > 0.5
+    else:
+        assert (m[6], m[7]) == (0.5 * (w - 1), 0.5 * (h - 1)) or m[9] < 0
+    if name.startswith("thin-"):
+        assert min(h, w) < 4 and r["bad"] == "none"
+        if name.endswith("-frac") or name.endswith("-direct"):
+            assert np.isfinite(raw).any() and ((h, w) == (1, 1) or (not integer and np.isnan(raw).any()))
+        if name.endswith("-outside"):
+            assert np.isnan(raw).all() and r["status"] == 0
 
 
 def test_warp_rows_cover_the_classes():
@@ -387,6 +538,26 @@ def test_warp_rows_cover_the_classes():
     assert {(r["dtype"], r["bad"]) for r in R.values()} >= {("f32", "nan"), ("f32", "nodata"), ("u16", "nodata"), ("f32", "none")}
     assert all(r["h"] <= 384 and r["w"] <= 384 for r in R.values())
     assert any(r["w"] > 2 * cc.TILE_W and r["h"] > 2 * cc.TILE_H for r in R.values())        # more than one tile each way
+    inst = {n: cc.warp_instance(r["dtype"], r["bound"][1]).split(", ")[1][:-1] for n, r in R.items()}
+    # strides of their own in and out: both dtypes on both instances; gaps between the bands on both sides in one row
+    own = {n: r for n, r in R.items() if r["out_extra"] != r["extra"] and r["out_off"] != r["off"]
+           and r["h"] * (r["w"] + r["extra"]) + r["in_gap"] != r["h"] * (r["w"] + r["out_extra"]) + r["out_gap"]}
+    assert {(r["dtype"], inst[n]) for n, r in own.items()} == {(d, i) for d in ("f32", "u16") for i in ("LDS", "DIRECT")}
+    assert any(r["in_gap"] and r["out_gap"] for r in own.values()) and all(r["bands"] > 1 and r["bad"] != "none" for r in own.values())
+    assert all(r["in_gap"] or r["out_gap"] for r in own.values())
+    # a model centred elsewhere, on both instances
+    assert {inst[n] for n, r in R.items() if r["centre"] is not None} == {"LDS", "DIRECT"}
+    # tile multiples, one less and one more, under a fractional shift with two bands
+    tiles = [r for n, r in R.items() if n.startswith("tile-")]
+    assert {r["w"] for r in tiles} == set(cc.WARP_TILE_W) == {cc.TILE_W - 1, cc.TILE_W, cc.TILE_W + 1, 2 * cc.TILE_W}
+    assert {r["h"] for r in tiles} == set(cc.WARP_TILE_H) == {cc.TILE_H - 1, cc.TILE_H, cc.TILE_H + 1, 2 * cc.TILE_H}
+    assert all(r["bands"] == 2 and r["model"]["dy0"] % 1 and r["model"]["dx0"] % 1 for r in tiles)
+    assert {r["dtype"] for r in tiles} == {"f32", "u16"}
+    # planes thinner than the four taps: a fractional and an integer shift on each
+    for h, w in cc.WARP_THIN:
+        assert {f"thin-{h}x{w}-frac", f"thin-{h}x{w}-int"} <= set(R)
+    assert set(cc.WARP_THIN) == {(1, 1), (1, 70), (40, 1), (2, 3), (3, 2)}
+    assert {inst[n] for n in R if n.startswith("thin-")} == {"LDS", "DIRECT"}
     # the Keys weights: a partition of unity, (0, 1, 0, 0) at t = 0
     for t in (0.0, 0.25, 0.5, 0.999):
         assert abs(sum(cc.keys(t)) - 1.0) < 1e-15
@@ -397,7 +568,24 @@ def test_warp_rows_cover_the_classes():
 @pytest.mark.parametrize("dtype", ["f32", "u16"])
 @pytest.mark.parametrize("name", list(cc.E2E_MODELS))
 def test_reference_recovers_the_truth(name, dtype):
-    c = cc.e2e_case(name, dtype)
+    _reference_recovers_the_truth(name, dtype, False)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u16"])
+@pytest.mark.parametrize("name", list(cc.E2E_MODELS))
+def test_reference_recovers_the_truth_rectangular(name, dtype):
+    _reference_recovers_the_truth(name, dtype, True)
+
+
+def _reference_recovers_the_truth(name, dtype, rect):
+    c = cc.e2e_case(name, dtype, rect)
+    p = c["params"]
+    assert c["emit"].shape == (p["he"], p["we"]) and c["s2"].shape == (c["hs"], c["ws"]) and max(c["hs"], c["ws"]) <= 384
+    if rect:
+        assert p["he"] != p["we"] and 0 < c["hs"] - p["f"] * p["he"] < p["f"] and c["ws"] == p["f"] * p["we"]
+        assert len(set(c["origins"][:, 0])) != len(set(c["origins"][:, 1]))
+    assert np.array_equal(c["origins"], s2_emit.tie_point_grid(p["he"], p["we"], c["hs"], c["ws"], window=p["w"], step=p["step"],
+                                                               factor=p["f"], max_shift=p["R"]))
     t0, t, truth = c["table0"], c["table"], c["truth"]
     assert (np.nanmax(c["bar"]) <= cc.BAR_CAP) and min(cc.peak_margin(s) for s in c["surface"]) >= cc.MARGIN
     assert t0[cc.DECOY, 7] == cc.OK and t0[cc.DECOY, 4] > 0.9                                  # a good match at the wrong place ...
@@ -415,3 +603,26 @@ def test_reference_recovers_the_truth(name, dtype):
     assert c["model"][9] == (1 if name == "affine" else 0) and c["model"][8] == ok.sum()
     _, den_min = cc.shift_bar(c["surface"], c["bar"], t0, c["params"]["R"])
     assert den_min.min() >= 1e-3                                                               # every row is admitted by the GPU test
+
+
+@pytest.mark.parametrize("dtype", ["f32", "u16"])
+def test_masked_case_conditions(dtype):
+    """The pair with an EMIT mask and S2 nodata: the bars and margins of the table hold, statuses other than OK occur, and both
+    the mask and the nodata value change the reference."""
+    c = cc.masked_case(dtype)
+    p, surf = c["params"], c["surface"]
+    fin = np.isfinite(surf)
+    assert (c["bar"][fin] <= cc.BAR_CAP).all() and min(cc.peak_margin(s) for s in surf if np.isfinite(s).any()) >= cc.MARGIN
+    status = c["table0"][:, 7].astype(int)
+    assert set(status) == {cc.OK, cc.NO_SCORE} and (status != cc.OK).sum() >= 3 and (status == cc.OK).sum() >= 20
+    per_point = fin.reshape(len(surf), -1).sum(axis=1)
+    assert ((per_point > 0) & (per_point < fin[0].size)).any()                   # a surface with some candidates short of pairs
+    assert c["mask"].dtype == np.uint8 and c["mask"].min() == 0 and c["mask"].max() > 1
+    bad = ~cc.s2_valid(c["s2"], c["nodata"])
+    assert bad.sum() > 1000 and (dtype == "u16" or (np.isnan(c["s2"]).any() and np.isinf(c["s2"]).any()))
+
+    def ref(mask, nodata):
+        return cc.surface_ref(c["emit"], mask, c["s2"], nodata, c["origins"], p["w"], p["f"], p["R"], c["min_valid"])[0]
+
+    for other in (ref(None, c["nodata"]), ref(c["mask"], None)):
+        assert not np.array_equal(np.isfinite(other), fin) or (np.abs(other - surf)[fin] > c["bar"][fin]).any()

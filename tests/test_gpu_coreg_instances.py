@@ -3,8 +3,10 @@ by row of the tables of tests/coreg_cases.py, against their references.
 
 The entry points of include/hsr_coreg.h are called through ctypes.  Planes, scenes and outputs lie in buffers filled with a
 sentinel byte between two guard zones (Buf of gpu_harness.py), some `off` bytes past a 256-byte boundary and with row strides
-larger than their width: nothing outside a payload may be written, the padding of an output row stays as it was, inputs stay as
-they were, and every output element the contract names must be written.  After every call the launch record
+larger than their width - for the rows that say so each operand with a padding and an offset of its own, the warp's output with
+another row stride, band stride (gaps between the bands) and offset than its input: nothing outside a payload may be written,
+the padding of an output row and the gap after a band stay as they were, inputs stay as they were, and every output element the
+contract names must be written.  After every call the launch record
 (hsr_coreg_last_launch) is compared with the instance the tables expect.  Bars: the header of coreg_cases.py - surfaces within
 their bars with NaN in the same places, peak records and warp outputs bit-equal, models within the model bar with equal
 statuses.  The last test checks that the rows reached every name hsr_coreg_instance_name enumerates."""
@@ -28,9 +30,9 @@ def _untouched(buf, back):
 def _surface(torch, name):
     r, c = cc.SURFACE_ROWS[name], cc.surface_case(name)
     P, D = len(c["origins"]), 2 * r["R"] + 1
-    eb = Buf(torch, c["emit_back"].nbytes, 4, c["emit_back"])
-    sb = Buf(torch, c["s2_back"].nbytes, 2 if r["dtype"] == "u16" else 12, c["s2_back"])
-    mb = Buf(torch, c["mask_back"].nbytes, 1, c["mask_back"]) if c["mask"] is not None else None
+    eb = Buf(torch, c["emit_back"].nbytes, r["offs"][0], c["emit_back"])
+    sb = Buf(torch, c["s2_back"].nbytes, r["offs"][1], c["s2_back"])
+    mb = Buf(torch, c["mask_back"].nbytes, r["offs"][2], c["mask_back"]) if c["mask"] is not None else None
     ob = Buf(torch, c["origins"].nbytes, 0, c["origins"])
     out = Buf(torch, P * D * D * 8, 8)
     nd = c["nodata"]
@@ -41,6 +43,8 @@ def _surface(torch, name):
     _untouched(eb, c["emit_back"])
     _untouched(sb, c["s2_back"])
     _untouched(ob, c["origins"])
+    if mb:
+        _untouched(mb, c["mask_back"])
     return got
 
 
@@ -64,6 +68,8 @@ def test_peak_rows(torch_gpu):
     torch = torch_gpu
     names, surf, origins, want = cc.peak_case()
     jobs = [("crafted", surf, origins, cc.PEAK_W, cc.PEAK_F, cc.PEAK_R, cc.PEAK_SHAPES, cc.PEAK_MIN_SCORE)]
+    _, rsurf, rorigins, rwant = cc.peak_case(rect=True)
+    jobs.append(("crafted-rect", rsurf, rorigins, cc.PEAK_W, cc.PEAK_F, cc.PEAK_R, cc.PEAK_SHAPES_RECT, cc.PEAK_MIN_SCORE))
     for name, r in cc.SURFACE_ROWS.items():
         c = cc.surface_case(name)
         jobs.append((name, c["ref"], c["origins"], r["w"], r["f"], r["R"], dict(he=r["he"], we=r["we"], hs=c["hs"], ws=c["ws"]), 0.6))
@@ -79,6 +85,9 @@ def test_peak_rows(torch_gpu):
         _untouched(sb, S)
         if tag == "crafted":
             assert np.array_equal(got[:, 7], want)
+        if tag == "crafted-rect":
+            assert np.array_equal(got[:, 7], rwant) and (got[:, 0] != got[:, 1]).all()
+            assert np.array_equal(got[:, 0], f * (org[:, 0] + w / 2) - 0.5) and np.array_equal(got[:, 1], f * (org[:, 1] + w / 2) - 0.5)
 
 
 def _fit(torch, r):
@@ -86,47 +95,53 @@ def _fit(torch, r):
     tb = Buf(torch, max(table.nbytes, 8), 8, table if table.size else None)
     mb = Buf(torch, cc.MODEL * 8, 8)
     LOG.call(["coreg_fit_model_kernel"], _lib().hsr_coreg_fit_model, tb.ptr, len(table), r["kind"], r["min_points"], r["reject_px"],
-             cc.MODEL_HS, cc.MODEL_WS, mb.ptr, _stream(torch))
+             r["hs"], r["ws"], mb.ptr, _stream(torch))
     return tb.get(np.float64)[:table.size].reshape(-1, cc.REC), mb.get(np.float64)
 
 
-@pytest.mark.parametrize("name", list(cc.MODEL_ROWS))
+@pytest.mark.parametrize("name", list(cc.MODEL_ROWS_ALL))
 def test_model_rows(torch_gpu, name):
     from s2_emit import _engine as eng
-    r = cc.MODEL_ROWS[name]
-    want_t, want_m, coef, bar = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], cc.MODEL_HS, cc.MODEL_WS)
+    r = cc.MODEL_ROWS_ALL[name]
+    hs, ws = r["hs"], r["ws"]
+    want_t, want_m, coef, bar = cc.model_ref(r["table"], r["kind"], r["min_points"], r["reject_px"], hs, ws)
     t, m = _fit(torch_gpu, r)
     same_bits(t, want_t, name + ": records after the rejection pass")
     assert (m[9], m[8]) == (r["kind_used"], r["n_used"])
-    diff = np.abs(cc.scaled_coefficients(m, cc.MODEL_HS, cc.MODEL_WS) - coef).max()
-    print(f"{name}: diff {diff:.3g}, bar {bar:.3g}")
+    diff = np.abs(cc.scaled_coefficients(m, hs, ws) - coef).max()
+    print(f"{name}: diff {diff:.3g}, bar {bar:.3g}, |err| / bar {diff / bar if bar else 0.0:.3g}")
     assert diff <= bar
-    _, host = eng.coreg_fit_model_host(r["table"], r["kind"], r["min_points"], r["reject_px"], (cc.MODEL_HS, cc.MODEL_WS))
-    assert np.abs(cc.scaled_coefficients(host, cc.MODEL_HS, cc.MODEL_WS) - cc.scaled_coefficients(m, cc.MODEL_HS, cc.MODEL_WS)).max() <= bar
+    assert (m[6], m[7]) == ((0.5 * (ws - 1), 0.5 * (hs - 1)) if m[9] >= 0 else (0.0, 0.0))
+    _, host = eng.coreg_fit_model_host(r["table"], r["kind"], r["min_points"], r["reject_px"], (hs, ws))
+    assert np.abs(cc.scaled_coefficients(host, hs, ws) - cc.scaled_coefficients(m, hs, ws)).max() <= bar
     assert np.array_equal(host[6:], m[6:])
 
 
 def _warp(torch, name, row=None):
-    """The warp of case `name` (under the bound of `row`, when given) -> (output without its padding, status word)."""
+    """The warp of case `name` (under the bound of `row`, when given) -> (output without its padding, status word).  The input
+    and the output have their own row padding, gap after every band and base offset; all of it must stay as it was."""
     r, c = row or cc.WARP_ROWS[name], cc.warp_case(name)
     scene = c["scene"]
     bands, h, w = scene.shape
     u16 = r["dtype"] == "u16"
-    inb = cc.pack_scene(scene, r["extra"], scene.dtype.type(3))
+    inb = cc.pack_scene(scene, r["extra"], scene.dtype.type(3), r["in_gap"])
+    irs, ors = w + r["extra"], w + r["out_extra"]
+    ibs, obs = h * irs + r["in_gap"], h * ors + r["out_gap"]
+    assert inb.shape == (bands, ibs)
     ib = Buf(torch, inb.nbytes, r["off"], inb)
-    ob = Buf(torch, inb.nbytes, r["off"])
+    ob = Buf(torch, bands * obs * scene.dtype.itemsize, r["out_off"])
     mb, sb = Buf(torch, cc.MODEL * 8, 8, c["model"]), Buf(torch, 4, 4)
-    rs, bs = w + r["extra"], h * (w + r["extra"])
     nd = c["nodata"]
-    LOG.call([cc.warp_instance(r["dtype"], r["bound"][1])], _lib().hsr_coreg_warp, ib.ptr, 1 if u16 else 0, bands, h, w, bs, rs, mb.ptr,
-             0 if nd is None else 1, 0.0 if nd is None else float(nd), c["fill"], r["bound"][0], r["bound"][1], ob.ptr, bs, rs, sb.ptr,
+    LOG.call([cc.warp_instance(r["dtype"], r["bound"][1])], _lib().hsr_coreg_warp, ib.ptr, 1 if u16 else 0, bands, h, w, ibs, irs, mb.ptr,
+             0 if nd is None else 1, 0.0 if nd is None else float(nd), c["fill"], r["bound"][0], r["bound"][1], ob.ptr, obs, ors, sb.ptr,
              _stream(torch))
-    out = ob.get(scene.dtype).reshape(bands, h, rs)
-    sent = np.frombuffer(bytes([FILL] * scene.dtype.itemsize), scene.dtype)[0]
-    assert (out[:, :, w:].view(np.uint16 if u16 else np.uint32) == sent.view(np.uint16 if u16 else np.uint32)).all()   # the padding
+    out, outside = cc.unpack_scene(ob.get(scene.dtype).reshape(bands, obs), h, w, r["out_extra"])
+    raw = ob.get(np.uint16 if u16 else np.uint32).reshape(bands, obs)
+    sent = np.frombuffer(bytes([FILL] * scene.dtype.itemsize), raw.dtype)[0]
+    assert outside.sum() == bands * (h * r["out_extra"] + r["out_gap"]) and (raw[outside] == sent).all()   # row padding and band gaps
     _untouched(ib, inb)
     _untouched(mb, c["model"])
-    return out[:, :, :w], int(sb.get(np.int32)[0])
+    return out, int(sb.get(np.int32)[0])
 
 
 @pytest.mark.parametrize("name", list(cc.WARP_ROWS))
