@@ -11,6 +11,7 @@
 
 #include "hsr_common.h"
 #include "hsr_solve.h"
+#include "hsr_tree_dev.h"
 #include "../../include/hsr_color.h"
 
 namespace hsr {
@@ -91,19 +92,9 @@ __device__ __forceinline__ void affine_add(double (&acc)[kAM], double x0, double
   acc[19] += y0; acc[20] += y1; acc[21] += y2;
 }
 
-// The workgroup's 256 thread sums to one slot: wave butterfly, then the four wave sums in order (as moments_kernel, hsr_poly.hip).
+// The workgroup's 256 thread sums to one slot (block_join4, hsr_tree_dev.h).
 __device__ __forceinline__ void slot_store(double (&acc)[kAM], double (&red)[4][kAM], double* slot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 0; m < kAM; ++m) {
-    const double s = wave_sum(acc[m]);
-    if (lane == 0) red[wave][m] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < kAM) {
-    const int m = threadIdx.x;
-    slot[m] = ((red[0][m] + red[1][m]) + red[2][m]) + red[3][m];
-  }
+  block_join4<kAM>(acc, red, kAM, [&](int m, double s) { slot[m] = s; });
 }
 
 // Rows of a slot: ceil(npix / slots) rounded up to whole groups of four pixels, so that a group never straddles two slots.
@@ -220,8 +211,8 @@ __host__ __device__ inline void affine_solve_channel(const double* mom, long lon
   for (int i = 0; i < 4; ++i) At[i * 3 + c] = coef[i];
 }
 
-// One workgroup of 1024: "lane" l = thread / 16 adds slots l, l + 64, ... in order for the moments m and m + 16 (m = thread % 16),
-// thread m < 22 walks the butterfly over the 64 lane sums (row_sum's tree, hsr_poly.hip), then threads 0..2 solve a channel each.
+// One workgroup of 1024: "lane" l = thread / 16 takes lane_slot_sum (slots l, l + 64, ... in order) for the moments m and m + 16
+// (m = thread % 16), thread m < 22 walks butterfly_tree64 over the 64 lane sums, then threads 0..2 solve a channel each.
 __global__ __launch_bounds__(1024) void affine_reduce_solve_kernel(const double* __restrict__ partials, int slots,
                                                                    long long min_count, double* __restrict__ moments,
                                                                    double* __restrict__ At) {
@@ -229,14 +220,8 @@ __global__ __launch_bounds__(1024) void affine_reduce_solve_kernel(const double*
   __shared__ double mom[kAM];
   __shared__ double work[3][kSolveWork];
   const int l = threadIdx.x >> 4, m = threadIdx.x & 15;
-  const bool second = m + 16 < kAM;
-  double s0 = 0.0, s1 = 0.0;
-  for (int i = l; i < slots; i += 64) {
-    s0 += partials[(size_t)i * kAM + m];
-    if (second) s1 += partials[(size_t)i * kAM + m + 16];
-  }
-  lsum[l][m] = s0;
-  lsum[l][m + 16] = s1;
+  lsum[l][m] = lane_slot_sum(l, slots, true, [&](int i) { return partials[(size_t)i * kAM + m]; });
+  lsum[l][m + 16] = lane_slot_sum(l, slots, m + 16 < kAM, [&](int i) { return partials[(size_t)i * kAM + m + 16]; });
   __syncthreads();
   if (threadIdx.x < kAM) {
     const double s = butterfly_tree64(&lsum[0][threadIdx.x], 32);

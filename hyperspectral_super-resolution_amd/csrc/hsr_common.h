@@ -156,27 +156,6 @@ inline int partial_slots(int64_t npix) {
   return (int)(tiles < 512 ? tiles : 512);  // 256 CUs x 2 resident workgroups
 }
 
-// Wave-level butterfly sum of a double (fixed tree -> deterministic).
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// The 63 adds of wave_sum's xor butterfly (32, 16, .., 1) over 64 lane sums, done by one thread: t[l] = v[l] + v[l ^ off]
-// for l < off is the value every lane of the pair holds after a level, so a[0] after the last level is wave_sum's result
-// bit for bit.  ``col`` = address of lane 0's sum, ``ld`` doubles between lanes.
-__device__ __forceinline__ double butterfly_tree64(const double* col, int ld) {
-  double a[32];
-#pragma unroll
-  for (int l = 0; l < 32; ++l) a[l] = col[(size_t)l * ld] + col[(size_t)(l + 32) * ld];
-#pragma unroll
-  for (int off = 16; off >= 1; off >>= 1)
-#pragma unroll
-    for (int l = 0; l < off; ++l) a[l] = a[l] + a[l + off];
-  return a[0];
-}
-
 // Streaming (non-temporal) accesses: everything on this path is touched exactly once, and letting
 // the 1.2 GB cube stream allocate in the 4 MB L2s evicts the dirty output lines early - measured on
 // K1: 0.2285 ms with plain loads, 0.2002 ms with `nt` on the LDS-DMA, 0.1957 ms with `nt` stores too.

@@ -18,6 +18,8 @@
 #include <string.h>
 
 #include "hsr_common.h"
+#include "hsr_solve.h"
+#include "hsr_tree_dev.h"
 #include "../../include/hsr_coreg.h"
 
 namespace hsr {
@@ -257,44 +259,6 @@ __host__ __device__ inline void model_shift(const double* m, double y, double x,
   dx = (m[3] + m[4] * (x - m[6])) + m[5] * (y - m[7]);
 }
 
-// Eigen-decomposition of a symmetric 3 x 3 (cyclic Jacobi): A ends diagonal, the columns of V are the eigenvectors.
-__host__ __device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
-  for (int j = 0; j < 3; ++j)
-    for (int k = 0; k < 3; ++k) V[j][k] = j == k ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    double off = 0.0, diag = 0.0;
-    for (int p = 0; p < 3; ++p) {
-      diag += A[p][p] * A[p][p];
-      for (int q = p + 1; q < 3; ++q) off += A[p][q] * A[p][q];
-    }
-    if (off <= 1e-36 * diag) break;
-    for (int p = 0; p < 3; ++p) {
-      for (int q = p + 1; q < 3; ++q) {
-        const double apq = A[p][q];
-        if (fabs(apq) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-        const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(tt * tt + 1.0), sn = tt * c;
-        for (int k = 0; k < 3; ++k) {
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - sn * akq;
-          A[k][q] = sn * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - sn * aqk;
-          A[q][k] = sn * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - sn * vkq;
-          V[k][q] = sn * vkp + c * vkq;
-        }
-      }
-    }
-  }
-}
-
 // One fit on the OK records.
 __host__ __device__ inline void fit_pass(const double* table, int n, int kind, int min_points, int hs, int ws, double* m) {
   const double xc = 0.5 * (double)(ws - 1), yc = 0.5 * (double)(hs - 1);
@@ -323,7 +287,7 @@ __host__ __device__ inline void fit_pass(const double* table, int n, int kind, i
     bx[0] += r[3]; bx[1] += u * r[3]; bx[2] += v * r[3];
   }
   double A[3][3] = {{g[0], g[1], g[2]}, {g[1], g[3], g[4]}, {g[2], g[4], g[5]}}, V[3][3];
-  jacobi3(A, V);
+  jacobi_eigen<3>(&A[0][0], &V[0][0], 3);   // hsr_solve.h: A ends diagonal, the columns of V are the eigenvectors
   double lmin = A[0][0], lmax = A[0][0];
   for (int i = 1; i < 3; ++i) {
     lmin = A[i][i] < lmin ? A[i][i] : lmin;

@@ -6,6 +6,7 @@
 #include "hsr_common.h"
 #include "hsr_solve.h"
 #include "hsr_sync_dev.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 
@@ -21,8 +22,8 @@ __device__ __forceinline__ void stores_done_barrier() {
 // round trips for it - nothing has to cross between running workgroups: a workgroup that has finished its groups draws a
 // ticket, and tickets 0 .. nb-1 reduce + solve one band each while the slower workgroups are still streaming.  Idle tail
 // time instead of a launch of its own, a side stream, two events and CUs kept free for it.  Same tree as
-// hsr_moments_reduce_solve ("lane" l adds slots l, l + 64, ... in batches of eight, butterfly over the 64 lane sums, the
-// same solve), hence the same bits.
+// hsr_moments_reduce_solve (lane_slot_sum for "lane" l, butterfly_tree64 over the 64 lane sums: hsr_tree_dev.h; the same
+// solve), hence the same bits.
 template <int DEG, int T, class Args>
 __device__ __forceinline__ void lazy_fit(const Args& a, unsigned char* smem, int t) {
   constexpr int M = moment_count(DEG);
@@ -41,7 +42,7 @@ __device__ __forceinline__ void lazy_fit(const Args& a, unsigned char* smem, int
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     const int l = pass * 32 + (t >> 4);
-    double s = 0.0;
+    double s = 0.0;                                       // lane_slot_sum (hsr_tree_dev.h), spelled out: K1's device code stays as it is
     for (int i0 = l; i0 < a.lazy_slots; i0 += 64 * 8) {
       double v[8];
 #pragma unroll
@@ -56,16 +57,10 @@ __device__ __forceinline__ void lazy_fit(const Args& a, unsigned char* smem, int
   }
   __syncthreads();
   if (t < M) {
-    double acc[32];
-#pragma unroll
-    for (int l = 0; l < 32; ++l) acc[l] = lsum[l][t] + lsum[l + 32][t];
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1)
-#pragma unroll
-      for (int l = 0; l < off; ++l) acc[l] = acc[l] + acc[l + off];
-    mom[t] = acc[0];
-    if (a.lazy_ready) st_agent(a.lazy_moments + (size_t)b * M + t, acc[0]);     // read by another queue while this launch still runs
-    else a.lazy_moments[(size_t)b * M + t] = acc[0];
+    const double s = butterfly_tree64(&lsum[0][t], 16);
+    mom[t] = s;
+    if (a.lazy_ready) st_agent(a.lazy_moments + (size_t)b * M + t, s);     // read by another queue while this launch still runs
+    else a.lazy_moments[(size_t)b * M + t] = s;
   }
   if (a.lazy_ready) {                                     // exchange pipelines: the all-reduce and the solve follow on the side stream
     stores_done_barrier();
@@ -81,7 +76,7 @@ __device__ __forceinline__ void lazy_fit(const Args& a, unsigned char* smem, int
     // The last tile's own entry comes from LDS (this workgroup has just written it), the others from earlier launches.
     double* gm = mom + 16 + kSolveWork;
     if (t < M) {
-      double acc[32];
+      double acc[32];                                     // butterfly_tree<64> (hsr_tree_dev.h), spelled out: K1's device code stays as it is
 #pragma unroll
       for (int l = 0; l < 32; ++l) {
         const double lo = l < T2 ? 0.0 + (l == T2 - 1 ? mom[t] : a.lazy_group_moments[((size_t)l * a.nb + b) * M + t]) : 0.0;

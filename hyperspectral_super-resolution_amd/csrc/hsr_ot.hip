@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 

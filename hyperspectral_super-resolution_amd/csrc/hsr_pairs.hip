@@ -10,6 +10,7 @@
 // GDAL's bilinear `reproject` of S2 onto the EMIT grid (notebook raw line 377) is NOT reproduced: the block mean is the exact
 // mean of the aligned 6 x 6 windows the tiles are cut as; callers with S2 already on the EMIT grid pass it as `s2_coarse`.
 #include "hsr_common.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 

@@ -10,6 +10,7 @@
 
 #include "hsr_common.h"
 #include "hsr_solve.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 
@@ -90,18 +91,8 @@ __global__ __launch_bounds__(256) void moments_kernel(const MomArgs a) {
       moment_add<DEG, float>(acc, xv, yv);
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const double s = wave_sum(acc[m]);
-    if (lane == 0) red[wave][m] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < M) {
-    const int m = threadIdx.x;
-    const double s = ((red[0][m] + red[1][m]) + red[2][m]) + red[3][m];
-    a.partials[((size_t)blockIdx.x * gridDim.y + b) * M + m] = s;     // slot-major: [slot][band][moment]
-  }
+  double* slot = a.partials + ((size_t)blockIdx.x * gridDim.y + b) * M;     // slot-major: [slot][band][moment]
+  block_join4<M>(acc, red, M, [&](int m, double s) { slot[m] = s; });
 }
 
 // float64 sample columns (no mask, no stretch): the (X, Ybar) columns of fit_ot_poly_rgb
@@ -125,38 +116,16 @@ __global__ __launch_bounds__(256) void moments_f64_kernel(const double* __restri
     const double xv = x[p], yv = y[p];
     if (isfinite(xv) && isfinite(yv)) moment_add<DEG, double>(acc, xv, yv);
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-    const double s = wave_sum(acc[m]);
-    if (lane == 0) red[wave][m] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < M) {
-    const int m = threadIdx.x;
-    partials[((size_t)blockIdx.x * gridDim.y + b) * M + m] = ((red[0][m] + red[1][m]) + red[2][m]) + red[3][m];
-  }
+  double* slot = partials + ((size_t)blockIdx.x * gridDim.y + b) * M;
+  block_join4<M>(acc, red, M, [&](int m, double s) { slot[m] = s; });
 }
 
-// one wave per (band, moment) row; lane-strided partial sums then the fixed butterfly
-// Lane-strided sum of one slot row in a fixed order (slot = lane, lane+64, ...), the loads issued in
-// independent batches of 8 so that the row costs one memory round trip instead of slots/64.
+// One wave per (band, moment) row: lane_slot_sum (slot = lane, lane + 64, ...), then the wave butterfly.
 // The partials are slot-major, [slot][band][moment] (a K1 work unit writes its 2*M*... sums as whole cache lines; the
 // first layout, [band][moment][slot], made every unit of a batch scatter 8-byte stores over nb*M lines shared with
 // units running on other XCDs): row = address of (slot 0, band, moment), stride = nb * M doubles between slots.
 __device__ __forceinline__ double row_sum(const double* __restrict__ row, int slots, int stride, int lane) {
-  double s = 0.0;
-  for (int i0 = lane; i0 < slots; i0 += 64 * 8) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + 64 * u;
-      v[u] = i < slots ? row[(size_t)i * stride] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];   // adding +0.0 for absent slots does not change the sum
-  }
-  return wave_sum(s);
+  return wave_sum(lane_slot_sum(lane, slots, true, [&](int i) { return row[(size_t)i * stride]; }));
 }
 
 // At most 16 workgroups of 4 waves: in the pipelined multi-GPU step this kernel runs on a side stream while the
@@ -178,8 +147,8 @@ __global__ __launch_bounds__(64) void solve_kernel(const double* __restrict__ mo
   if (b < nb) solve_band(moments + (size_t)b * moment_count(deg), deg, min_count, coeffs + (size_t)b * (deg + 1));
 }
 
-// reduce + solve in one launch: one workgroup per band.  Same tree as row_sum / reduce_kernel - "lane" l adds slots
-// l, l + 64, ... in order, then the butterfly over the 64 lane sums - but laid out for the slot-major partials: a
+// reduce + solve in one launch: one workgroup per band.  Same tree as row_sum / reduce_kernel - lane_slot_sum for "lane" l,
+// then butterfly_tree64 over the 64 lane sums - but laid out for the slot-major partials: a
 // 16-lane group reads the band's 3deg+2 moments of ONE slot (112 contiguous bytes for deg 3), so a load instruction
 // touches 4-8 cache lines instead of 64 (the wave-per-moment gather cost ~8000 line requests through one CU's L1,
 // 4 us of the kernel's 8.6).  The lane sums go through LDS; thread m < M walks the butterfly for moment m.
@@ -194,21 +163,8 @@ __global__ __launch_bounds__(1024) void reduce_solve_kernel(const double* __rest
   const int stride = (int)gridDim.x * M;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l = wave * 4 + (lane >> 4), m = lane & 15;
-  {
-    const double* row = partials + (size_t)b * M + (m < M ? m : 0);
-    double s = 0.0;
-    for (int i0 = l; i0 < slots; i0 += 64 * 8) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int i = i0 + 64 * u;
-        v[u] = (i < slots && m < M) ? row[(size_t)i * stride] : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += v[u];   // adding +0.0 for absent slots does not change the sum
-    }
-    lsum[l][m] = s;
-  }
+  const double* row = partials + (size_t)b * M + (m < M ? m : 0);
+  lsum[l][m] = lane_slot_sum(l, slots, m < M, [&](int i) { return row[(size_t)i * stride]; });
   __syncthreads();
   if (threadIdx.x < M) {
     const double s = butterfly_tree64(&lsum[0][threadIdx.x], 16);
@@ -220,11 +176,11 @@ __global__ __launch_bounds__(1024) void reduce_solve_kernel(const double* __rest
 }
 
 // Batch form (hsr_moments_reduce_solve_batched): ONE workgroup per tile, the tile's slot block at slot0 * nb * M of the
-// batch workspace with its own slot count.  Same tree as row_sum -> same bits as the single-tile launch on that tile -
+// batch workspace with its own slot count.  Same tree as row_sum (hsr_tree_dev.h) -> same bits as the single-tile launch on that tile -
 // laid out for the slot-major partials like reduce_solve_kernel: a 16-lane group reads the M moments of one (slot,
 // band) - contiguous - and every thread carries the lane sums of all bands, so the whole tile costs ~2 memory round
 // trips.  Lane sum index l = (lane / 16) * 16 + wave: the butterfly's first two levels (l ^ 32, l ^ 16) are in-wave
-// shuffles, the last four (over the wave index) run from LDS, one thread per (band, moment) row; then one thread per
+// shuffles, the last four (over the wave index) run from LDS (butterfly_tree<16>), one thread per (band, moment) row; then one thread per
 // band solves.  (First version: a (band, tile) grid with thread 0 solving, 49 us for 256 tiles; second: one wave per
 // row gathering 8 bytes per cache line, 14.2 us; this one 13.5 us, 11.1 us of it without the solve: 256 tiles of
 // 100 x 100 pixels hold 157 slots x 1344 B each = 54 MB of partials, so the kernel is an HBM read at ~5 TB/s.)
@@ -277,15 +233,9 @@ __global__ __launch_bounds__(1024) void reduce_solve_batched_kernel(const hsr_ba
   }
   __syncthreads();
   if ((int)threadIdx.x < R) {
-    double a[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) a[w] = lsum[w][threadIdx.x] + lsum[w + 8][threadIdx.x];
-#pragma unroll
-    for (int off = 4; off >= 1; off >>= 1)
-#pragma unroll
-      for (int w = 0; w < off; ++w) a[w] = a[w] + a[w + off];
-    mom[threadIdx.x] = a[0];
-    moments[(size_t)tile * R + threadIdx.x] = a[0];
+    const double s = butterfly_tree<16>([&](int w) { return lsum[w][threadIdx.x]; });
+    mom[threadIdx.x] = s;
+    moments[(size_t)tile * R + threadIdx.x] = s;
   }
   __syncthreads();
   if ((int)threadIdx.x < nb)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "hsr_common.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 
@@ -810,18 +811,18 @@ constexpr int kStatsBlocks = 64;
 
 // per-block sums of d = x - K and d^2 (K = the column's first sample: the "shifted data" form, so that
 // M2 = sum d^2 - (sum d)^2 / n loses nothing to a large mean); fixed order inside the block: every thread walks its rows
-// once with all columns in registers, lanes are joined by the xor butterfly, the four waves in wave order
+// once with all columns in registers (acc[2c] = sum d, acc[2c + 1] = sum d^2 of column c), then block_join4 (hsr_tree_dev.h)
 __global__ __launch_bounds__(256) void ridge_stats_partial_kernel(const float* __restrict__ x, int64_t x_rs, int64_t x_cs,
                                                                   int64_t n, int n_in, double* __restrict__ work) {
   __shared__ double red[4][32];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int64_t rows = (n + gridDim.x - 1) / gridDim.x;
   const int64_t r0 = (int64_t)blockIdx.x * rows;
   const int64_t r1 = r0 + rows < n ? r0 + rows : n;
-  double s1[16], s2[16], K[16];
+  double acc[32], K[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
-    s1[c] = s2[c] = 0.0;
+    acc[2 * c] = acc[2 * c + 1] = 0.0;
     K[c] = c < n_in ? (double)x[c * x_cs] : 0.0;
   }
   // four rows per pass with all their loads issued before the first sum (a block walks <= 1024 rows: one exposed round trip
@@ -842,23 +843,13 @@ __global__ __launch_bounds__(256) void ridge_stats_partial_kernel(const float* _
       for (int c = 0; c < 16; ++c)
         if (c < n_in) {
           const double d = (double)v[q][c] - K[c];
-          s1[c] += d;
-          s2[c] += d * d;
+          acc[2 * c] += d;
+          acc[2 * c + 1] += d * d;
         }
     }
   }
-#pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    if (c < n_in) {
-      const double a1 = wave_sum(s1[c]), a2 = wave_sum(s2[c]);
-      if (lane == 0) {
-        red[wave][2 * c] = a1;
-        red[wave][2 * c + 1] = a2;
-      }
-    }
-  }
-  __syncthreads();
-  if (t < 2 * n_in) work[(size_t)blockIdx.x * n_in * 2 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+  double* out = work + (size_t)blockIdx.x * n_in * 2;
+  block_join4<32, 2>(acc, red, 2 * n_in, [&](int m, double s) { out[m] = s; });
 }
 
 // the blocks' sums joined (one wave per column, a lane per block, xor butterfly: a fixed order) -> [n, mean.., M2..] (the

@@ -1,6 +1,7 @@
 // np.polyfit from the moment sums: the per-band solve shared by the stand-alone solve / reduce+solve kernels
 // (hsr_poly.hip), the host-side hsr_poly_solve_host and the fused tail of K1 (hsr_srf.hip).  One definition, so that
-// every caller produces the same bits.
+// every caller produces the same bits.  jacobi_eigen, the sweep under its rank-revealing path, also serves the affine colour solve
+// (hsr_color.hip, through solve_band_jacobi) and the shift model of the co-registration (hsr_coreg.hip, a 3 x 3 of its own).
 #pragma once
 #include "hsr_common.h"
 
@@ -29,42 +30,50 @@ constexpr double kRankFloor = 4 * 2.220446049250313e-16;
 // kernel.  Same arithmetic in the same order either way.
 constexpr int kSolveLd = HSR_MAX_DEG + 1;
 constexpr int kSolveWork = 2 * kSolveLd * kSolveLd + 2 * kSolveLd;   // doubles of work space per band: A, V, rhs, s
-__host__ __device__ inline void solve_band_jacobi(double* A, double* V, const double* rhs, const double* s, int n,
-                                                  double count, double* coef) {
+
+// Eigen-decomposition of a symmetric n x n matrix (rows of LD doubles) by cyclic Jacobi, at most 40 sweeps: A ends diagonal (the
+// eigenvalues), the columns of V are the eigenvectors.  The sweep only; every caller applies its own pseudo-inverse rule.
+template <int LD>
+__host__ __device__ inline void jacobi_eigen(double* A, double* V, int n) {
   for (int j = 0; j < n; ++j)
-    for (int k = 0; k < n; ++k) V[j * kSolveLd + k] = j == k ? 1.0 : 0.0;
+    for (int k = 0; k < n; ++k) V[j * LD + k] = j == k ? 1.0 : 0.0;
   for (int sweep = 0; sweep < 40; ++sweep) {
     double off = 0.0, diag = 0.0;
     for (int p = 0; p < n; ++p) {
-      diag += A[p * kSolveLd + p] * A[p * kSolveLd + p];
-      for (int q = p + 1; q < n; ++q) off += A[p * kSolveLd + q] * A[p * kSolveLd + q];
+      diag += A[p * LD + p] * A[p * LD + p];
+      for (int q = p + 1; q < n; ++q) off += A[p * LD + q] * A[p * LD + q];
     }
     if (off <= 1e-36 * diag) break;
     for (int p = 0; p < n; ++p) {
       for (int q = p + 1; q < n; ++q) {
-        const double apq = A[p * kSolveLd + q];
+        const double apq = A[p * LD + q];
         if (fabs(apq) < 1e-300) continue;
-        const double theta = (A[q * kSolveLd + q] - A[p * kSolveLd + p]) / (2.0 * apq);
+        const double theta = (A[q * LD + q] - A[p * LD + p]) / (2.0 * apq);
         const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
         const double c = 1.0 / sqrt(tt * tt + 1.0), sn = tt * c;
         for (int k = 0; k < n; ++k) {
-          const double akp = A[k * kSolveLd + p], akq = A[k * kSolveLd + q];
-          A[k * kSolveLd + p] = c * akp - sn * akq;
-          A[k * kSolveLd + q] = sn * akp + c * akq;
+          const double akp = A[k * LD + p], akq = A[k * LD + q];
+          A[k * LD + p] = c * akp - sn * akq;
+          A[k * LD + q] = sn * akp + c * akq;
         }
         for (int k = 0; k < n; ++k) {
-          const double apk = A[p * kSolveLd + k], aqk = A[q * kSolveLd + k];
-          A[p * kSolveLd + k] = c * apk - sn * aqk;
-          A[q * kSolveLd + k] = sn * apk + c * aqk;
+          const double apk = A[p * LD + k], aqk = A[q * LD + k];
+          A[p * LD + k] = c * apk - sn * aqk;
+          A[q * LD + k] = sn * apk + c * aqk;
         }
         for (int k = 0; k < n; ++k) {
-          const double vkp = V[k * kSolveLd + p], vkq = V[k * kSolveLd + q];
-          V[k * kSolveLd + p] = c * vkp - sn * vkq;
-          V[k * kSolveLd + q] = sn * vkp + c * vkq;
+          const double vkp = V[k * LD + p], vkq = V[k * LD + q];
+          V[k * LD + p] = c * vkp - sn * vkq;
+          V[k * LD + q] = sn * vkp + c * vkq;
         }
       }
     }
   }
+}
+
+__host__ __device__ inline void solve_band_jacobi(double* A, double* V, const double* rhs, const double* s, int n,
+                                                  double count, double* coef) {
+  jacobi_eigen<kSolveLd>(A, V, n);
   double lmax = 0.0;
   for (int i = 0; i < n; ++i) lmax = A[i * kSolveLd + i] > lmax ? A[i * kSolveLd + i] : lmax;
   const double rcond = count * 2.220446049250313e-16;

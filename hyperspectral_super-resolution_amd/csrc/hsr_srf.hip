@@ -38,6 +38,7 @@
 #include "hsr_solve.h"
 #include "hsr_sync_dev.h"
 #include "hsr_fused_dev.h"
+#include "hsr_tree_dev.h"
 
 namespace hsr {
 
@@ -409,8 +410,8 @@ __device__ __forceinline__ void flush_moments(double (&acc_m)[2][M], const bool 
 }
 
 // Tail of a single-tile K1+K2 launch with a.fit set: the slot reduction and the solve without a second launch.
-// The summation tree is the one of row_sum (hsr_poly.hip) - lane l of a wave adds slots l, l+64, ... in order, then
-// the xor butterfly 32,16,..,1 over the 64 lanes - cut at the lane sums: the 64 "lanes" are 64 GROUPS of slots
+// The summation tree is the one of hsr_tree_dev.h - lane_slot_sum (lane l of a wave adds slots l, l+64, ... in order), then
+// wave_sum's xor butterfly 32,16,..,1 over the 64 lanes - cut at the lane sums: the 64 "lanes" are 64 GROUPS of slots
 // (group = slot mod 64).  The workgroup whose ticket completes a group adds that group's slots (level A, one thread per
 // (band, moment) row, coalesced over rows) into gpart; the workgroup whose ticket completes the groups runs the
 // butterfly over the 64 group sums (level B, one wave per row), writes the moments, solves the bands (same
@@ -435,9 +436,9 @@ __device__ __forceinline__ void fused_fit(const SrfFit& f, const double* part, i
   }
   __syncthreads();
   if (!*flag) return;
-  if (t < R) {                               // level A: row t of the slots grp, grp + 64, ... (row_sum's lane loop)
+  if (t < R) {                               // level A: row t of the slots grp, grp + 64, ...
     const double* row = part + t;
-    double s = 0.0;
+    double s = 0.0;                          // lane_slot_sum (hsr_tree_dev.h), spelled out: K1's device code stays as it is
     for (int i0 = grp; i0 < S; i0 += 64 * 8) {
       double v[8];
 #pragma unroll

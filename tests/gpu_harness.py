@@ -79,6 +79,48 @@ def same_bits(got, ref, what):
     assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} elements differ, first {got[bad][:4]} vs {ref[bad][:4]}"
 
 
+# ---- the documented summation tree (csrc/hsr_tree_dev.h), written out in NumPy: float64, one rounding per add ----------------------
+def butterfly64(v):
+    """The xor butterfly 32, 16, .., 1 over 64 entries (axis 0): wave_sum / butterfly_tree<64>; every lane's result is the same."""
+    v = np.asarray(v, np.float64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[np.arange(64) ^ off]
+    return v[0]
+
+
+def slot_tree(col):
+    """A slot reduction: lane l adds slots l, l + 64, ... in order from 0.0 (lane_slot_sum); then the xor butterfly over the 64
+    lane sums.  col: (slots,) or (slots, ...) - every trailing element is a sum of its own."""
+    col = np.asarray(col, np.float64)
+    v = np.zeros((64,) + col.shape[1:])
+    for lane in range(64):
+        s = np.zeros(col.shape[1:])
+        for i in range(lane, len(col), 64):
+            s = s + col[i]
+        v[lane] = s
+    return butterfly64(v)
+
+
+def thread_sums(terms, ok, owned):
+    """Per-thread accumulation of a 256-thread moments kernel: thread t starts every sum at 0.0 and adds, in order, the terms of
+    the pixels owned[0][t], owned[1][t], ... that are `ok`.  terms (npix, M) float64 (every product already rounded on its own:
+    the library is built without contraction), ok (npix,) bool, owned (passes, 256) pixel indices, -1 = none.  -> (256, M)."""
+    acc = np.zeros((256, terms.shape[1]))
+    for sel in owned if len(terms) else ():                          # an empty slot: every sum stays 0.0
+        use = (sel >= 0) & ok[np.maximum(sel, 0)]
+        with np.errstate(invalid="ignore", over="ignore"):
+            acc = np.where(use[:, None], acc + terms[np.maximum(sel, 0)], acc)
+    return acc
+
+
+def wave_tree(acc):
+    """The workgroup join (block_join4): acc (256, ...) per-thread sums -> xor butterfly 32..1 over each wave's 64 lanes, then the
+    four wave sums in order, ((w0 + w1) + w2) + w3."""
+    acc = np.asarray(acc, np.float64)
+    w = [butterfly64(acc[64 * k: 64 * k + 64]) for k in range(4)]
+    return ((w[0] + w[1]) + w[2]) + w[3]
+
+
 class LaunchLog:
     """A family's launch record (the hsr_*_last_launch named `reader_name`) as one test module uses it; `seen` collects every
     kernel name its checked calls recorded.  joined: read() splits the record into the list of its names."""

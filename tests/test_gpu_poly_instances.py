@@ -20,7 +20,7 @@ import warnings
 import numpy as np
 import pytest
 
-from gpu_harness import LaunchLog, bits_equal, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import LaunchLog, bits_equal, slot_tree, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
 from gpu_harness import lib as _lib
 from oracle import oracle_np as onp
 
@@ -402,20 +402,7 @@ def test_moments_f64_kernel_vs_float64(torch_gpu, deg, npix):
         _check_moments(got[b], _moments_ref(x[b, :npix][ok], y[b, :npix][ok], deg), f"moments_f64_kernel<{deg}> band {b}")
 
 
-# ---- reduction: the documented tree, bit for bit ----------------------------------------------------------------------------
-def _tree(col):
-    """lane l adds slots l, l + 64, ... in order from 0.0; then the xor butterfly over the 64 lane sums."""
-    v = np.zeros(64)
-    for lane in range(64):
-        s = 0.0
-        for i in range(lane, len(col), 64):
-            s = s + col[i]
-        v[lane] = s
-    for off in (32, 16, 8, 4, 2, 1):
-        v = v + v[np.arange(64) ^ off]
-    return v[0]
-
-
+# ---- reduction: the documented tree (slot_tree of gpu_harness), bit for bit -------------------------------------------------
 def _partials(rng, slots, nb, M):
     return rng.standard_normal((slots, nb, M)) * np.exp2(rng.integers(-40, 40, (slots, nb, M)))
 
@@ -432,7 +419,7 @@ def test_reduce_kernels_follow_the_documented_tree(torch_gpu, slots):
     M = 3 * deg + 2
     p = _partials(rng, slots, nb, M)
     p[..., 0] = np.abs(p[..., 0])                                    # a count-like column: keeps the solve in business
-    ref = np.array([[_tree(p[:, b, m]) for m in range(M)] for b in range(nb)])
+    ref = slot_tree(p)
     pd = torch.from_numpy(p.reshape(-1)).cuda()
     got = _reduce(torch, pd, slots, nb, deg)
     assert np.array_equal(got.view(np.int64), ref.view(np.int64)), "reduce_kernel"
@@ -472,7 +459,7 @@ def test_reduce_solve_batched_follows_the_documented_tree(torch_gpu, nb):
     parts = [_partials(rng, s, nb, M) for s in SLOTS]
     mom, _ = _batched(torch_gpu, parts, nb, deg)
     for t, p in enumerate(parts):
-        ref = np.array([[_tree(p[:, b, m]) for m in range(M)] for b in range(nb)])
+        ref = slot_tree(p)
         assert np.array_equal(mom[t].view(np.int64), ref.view(np.int64)), f"tile {t} ({p.shape[0]} slots)"
 
 
