@@ -268,10 +268,17 @@ for _l in (PADDED, PACKED, PLANAR):
 MOMENT_ROWS["off8-both"] = _mrow(PASS + 7, x=(PACKED, 8), y=(PADDED, 8))
 
 
+moment_row = _mrow                           # the pure constructor, under the name the sweeps use
+
+
 @functools.lru_cache(maxsize=None)
 def moment_case(name):
-    r = MOMENT_ROWS[name]
-    seed = sorted(MOMENT_ROWS).index(name)
+    return moment_case_of(MOMENT_ROWS[name], sorted(MOMENT_ROWS).index(name))
+
+
+def moment_case_of(r, seed):
+    """The images, the mask and the long-double moments of the moment row `r`; `seed` picks the images, the poisoned samples and
+    the mask (a table row's is its place among the sorted names)."""
     x, y = image_pair(r["npix"], seed)
     poison(x, y, r["bad"], seed)
     mask = make_mask(r["npix"], r["mask"], seed)
@@ -316,10 +323,15 @@ for _l in (PADDED, PACKED, PLANAR):
 APPLY_ROWS["off12-both"] = _arow(PASS + 7, x=(PADDED, 12), out=(PACKED, 12), clip=2, bad=True)
 
 
+apply_row = _arow
+
+
 @functools.lru_cache(maxsize=None)
 def apply_case(name):
-    r = APPLY_ROWS[name]
-    seed = 100 + sorted(APPLY_ROWS).index(name)
+    return apply_case_of(APPLY_ROWS[name], 100 + sorted(APPLY_ROWS).index(name))
+
+
+def apply_case_of(r, seed):
     x, y = image_pair(r["npix"], seed)
     if r["bad"]:
         poison(x, y, "x", seed)
@@ -364,10 +376,16 @@ SOLVE_ROWS = {
 }
 
 
+solve_row = _srow
+
+
 @functools.lru_cache(maxsize=None)
 def solve_case(name):
-    r = SOLVE_ROWS[name]
-    xs, ys = _solve_inputs(r["kind"], r["n"], 300 + sorted(SOLVE_ROWS).index(name))
+    return solve_case_of(SOLVE_ROWS[name], 300 + sorted(SOLVE_ROWS).index(name))
+
+
+def solve_case_of(r, seed):
+    xs, ys = _solve_inputs(r["kind"], r["n"], seed)
     W = lstsq_ref(xs, ys, r["min_count"])
     identity = r["n"] < max(r["min_count"], 1)
     bar, kappa = (0.0, 1.0) if identity else solve_bar(xs, W)

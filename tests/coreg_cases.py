@@ -154,12 +154,20 @@ def peak_margin(surface):
 #   hs, ws: the S2 plane, default f he, f we.  pads: (EMIT, S2, mask) row-stride paddings of their own, default `extra` for all
 #   three.  offs: (EMIT, S2, mask) base offsets in bytes past a 256-byte boundary, default (4, 12 or 2 for uint16, 1).
 #   inside: what the region test must say of every origin, for the rows whose origins straddle it
+#   black, corner, hole, emit_nan, s2_inf: where mask == "part" puts what it plants - the black S2 rectangle (r0, r1, c0, c1), whose
+#   last five rows are NaN for float32; the masked EMIT corner (rows, columns); one more masked EMIT pixel; one NaN EMIT pixel; one
+#   +inf S2 sample (float32)
 def _srow(he, we, f, w, R, origins, dtype="f32", extra=0, mask="none", min_valid=None, truth=(0.0, 0.0), seed=1, const=False,
-          hs=None, ws=None, pads=None, offs=None, inside=None):
+          hs=None, ws=None, pads=None, offs=None, inside=None, black=(60, 75, 58, 80), corner=(4, 5), hole=(10, 10),
+          emit_nan=(12, 11), s2_inf=(76, 60)):
     return dict(he=he, we=we, f=f, w=w, R=R, origins=origins, dtype=dtype, extra=extra, mask=mask,
                 min_valid=min_valid if min_valid is not None else max(1, (3 * w * w + 3) // 4), truth=truth, seed=seed, const=const,
                 hs=he * f if hs is None else hs, ws=we * f if ws is None else ws, pads=pads if pads is not None else (extra,) * 3,
-                offs=offs if offs is not None else (4, 2 if dtype == "u16" else 12, 1), inside=inside)
+                offs=offs if offs is not None else (4, 2 if dtype == "u16" else 12, 1), inside=inside, black=black, corner=corner,
+                hole=hole, emit_nan=emit_nan, s2_inf=s2_inf)
+
+
+surface_row = _srow                                # the pure constructor, under the name the sweeps use
 
 
 def _grid65():
@@ -224,7 +232,11 @@ NODATA_F32, NODATA_U16 = -9999.0, 0
 
 @functools.lru_cache(maxsize=None)
 def surface_case(name):
-    r = SURFACE_ROWS[name]
+    return surface_case_of(SURFACE_ROWS[name])
+
+
+def surface_case_of(r):
+    """The inputs, backing arrays and reference of the surface row `r`."""
     he, we, f, w, R = r["he"], r["we"], r["f"], r["w"], r["R"]
     hs, ws = r["hs"], r["ws"]
     emit, s2 = scene_pair(he, we, f, make_model(hs, ws, *r["truth"]), r["seed"], r["dtype"], hs, ws)
@@ -238,15 +250,16 @@ def surface_case(name):
     if r["mask"] == "part":
         nodata = NODATA_U16 if r["dtype"] == "u16" else NODATA_F32
         s2[np.equal(s2, nodata)] = 1                  # no accidental nodata
-        s2[60:75, 58:80] = nodata                     # the black rectangle
+        r0, r1, c0, c1 = r["black"]
+        s2[r0:r1, c0:c1] = nodata                     # the black rectangle
         if r["dtype"] == "f32":
-            s2[70:75, 58:80] = np.nan
-            s2[76, 60] = np.inf
+            s2[max(r0, r1 - 5):r1, c0:c1] = np.nan
+            s2[r["s2_inf"]] = np.inf
         mask = np.ones((he, we), np.uint8)
-        mask[:4, :5] = 0                              # the masked corner
-        mask[10, 10] = 0
+        mask[:r["corner"][0], :r["corner"][1]] = 0    # the masked corner
+        mask[r["hole"]] = 0
         mask[mask != 0] = 1 + (np.arange(int(mask.sum())) % 3).astype(np.uint8)
-        emit[12, 11] = np.nan
+        emit[r["emit_nan"]] = np.nan
     if r["mask"] == "all":
         mask = np.zeros((he, we), np.uint8)
     min_valid = r["min_valid"]
@@ -654,12 +667,13 @@ def warp_instance(dtype, slope_bound):
 # name: dtype, bands, h, w, model terms, bad (none | nan | nodata), bound (max_abs_shift, max_abs_slope), off (base misalignment,
 # bytes), extra (row-stride padding), fill, status (what the device-side check of the bound must say)
 #   out_off, out_extra: the same two of the output, default the input's.  in_gap, out_gap: elements between the bands, so that the
-#   band stride is h rs + gap.  centre: (xc, yc) of the model, default the centre of the scene that is warped
+#   band stride is h rs + gap.  centre: (xc, yc) of the model, default the centre of the scene that is warped.  seed: what picks the
+#   texture and the bad samples, default the length of the row's name
 def _wrow(dtype, bands, h, w, model, bad="none", bound=(13.0, 0.05), off=0, extra=0, fill=None, status=0, kind="texture",
-          out_off=None, out_extra=None, in_gap=0, out_gap=0, centre=None):
+          out_off=None, out_extra=None, in_gap=0, out_gap=0, centre=None, seed=None):
     return dict(dtype=dtype, bands=bands, h=h, w=w, model=model, bad=bad, bound=bound, off=off, extra=extra, fill=fill, status=status,
                 kind=kind, out_off=off if out_off is None else out_off, out_extra=extra if out_extra is None else out_extra,
-                in_gap=in_gap, out_gap=out_gap, centre=centre)
+                in_gap=in_gap, out_gap=out_gap, centre=centre, seed=seed)
 
 
 _STEEP = dict(dy0=0.8, dx0=-1.1, dy_x=0.3, dy_y=-0.2, dx_x=0.25, dx_y=0.3)
@@ -718,9 +732,17 @@ WARP_ROWS["thin-1x1-outside"] = _wrow("f32", 1, 1, 1, dict(dx0=0.25))
 WARP_ROWS["thin-2x3-direct"] = _wrow("u16", 2, 2, 3, dict(dy0=0.25, dx0=-0.375), bound=(13.0, 2.0))
 
 
+warp_row = _wrow                                   # the pure constructor, under the name the sweeps use
+
+
 @functools.lru_cache(maxsize=None)
 def warp_case(name):
-    r = WARP_ROWS[name]
+    return warp_case_of(WARP_ROWS[name], len(name))
+
+
+def warp_case_of(r, seed=None):
+    """The scene, model and reference of the warp row `r`; `seed` (default: the row's) picks the texture and the bad samples."""
+    seed = r["seed"] if seed is None else seed
     bands, h, w = r["bands"], r["h"], r["w"]
     if r["kind"] == "ramp":
         # rows of ramps (results k + 1.5: round half to even both ways) and of 0 / 65535 steps (overshoot past both ends)
@@ -728,15 +750,15 @@ def warp_case(name):
         scene[:, 0::2] = np.arange(w)[None, None, :]
         scene[:, 1::2] = np.where((np.arange(w) // 3) % 2 == 0, 0.0, 65535.0)[None, None, :]
     else:
-        t = texture(max(h, 64), max(w, 64), 30 + len(name))
+        t = texture(max(h, 64), max(w, 64), 30 + seed)
         scene = np.stack([np.roll(t, 11 * b, axis=1)[PAD:PAD + h, PAD:PAD + w] for b in range(bands)])
         scene = scene * 10000.0 if r["dtype"] == "u16" else scene * 2.0 - 0.5
     scene = np.round(scene).astype(np.uint16) if r["dtype"] == "u16" else scene.astype(np.float32)
     nodata = None
-    rng = np.random.default_rng(len(name))
+    rng = np.random.default_rng(seed)
     if r["bad"] == "nan":
         scene[rng.random(scene.shape) < 0.01] = np.nan
-        scene[0, 5, 7] = np.inf
+        scene[0, min(5, h - 1), min(7, w - 1)] = np.inf
     if r["bad"] == "nodata":
         nodata = 0 if r["dtype"] == "u16" else -9999.0
         scene[np.equal(scene, nodata)] = 1

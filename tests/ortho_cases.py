@@ -126,6 +126,29 @@ def glt_of(kind, gh, gw, rows, cols, nodata=0):
     return out
 
 
+def glt_drawn(key, gh, gw, rows, cols, nodata=0):
+    """Every entry on its own: a uniformly random cell of the swath (55 %: neighbours scatter over the swath's rows), a copy of its
+    left neighbour (20 %), no data in x, y or both (12 %), or one of DROP_ENTRIES on one axis (13 %)."""
+    rng = np.random.default_rng(list(key) + [gh, gw])
+    g = np.stack([rng.integers(1, cols + 1, (gh, gw)), rng.integers(1, rows + 1, (gh, gw))], axis=-1).astype(np.int64)
+    common = [e for e in DROP_ENTRIES if not isinstance(e, str)] + ([0] if nodata != 0 else [])
+    bad = np.array([[cols + 1] + common, [rows + 1] + common], np.int64)
+    u, which = rng.random((gh, gw)), rng.integers(0, 3, (gh, gw))
+    pick, axis = rng.integers(0, bad.shape[1], (gh, gw)), rng.integers(0, 2, (gh, gw))
+    nd = (u >= 0.75) & (u < 0.87)
+    g[..., 0][nd & (which != 1)] = nodata
+    g[..., 1][nd & (which != 0)] = nodata
+    dr = u >= 0.87
+    g[..., 0][dr & (axis == 0)] = bad[0][pick][dr & (axis == 0)]
+    g[..., 1][dr & (axis == 1)] = bad[1][pick][dr & (axis == 1)]
+    for j in range(1, gw):
+        same = (u[:, j] >= 0.55) & (u[:, j] < 0.75)
+        g[same, j] = g[same, j - 1]
+    out = g.astype(np.int32)
+    out.setflags(write=False)
+    return out
+
+
 @functools.lru_cache(maxsize=None)
 def qmask_of(rows, cols):
     rng = np.random.default_rng(rows * 31 + cols)
@@ -160,13 +183,18 @@ WIDTHS = (1, 3, PX - 1, PX, PX + 1, 2 * PX + 2)
 MASKS = ((False, 0), (True, 0), (False, 1), (True, 1))                # (quality mask, band mask: 0 none, 1 given)
 
 
-def _row(name, bands, layout, width, height, *, rows=4, cols=5, grid="mixed", q=False, bm=0, extra_bytes=0, window=None, gh=None,
-         gw=None, swath_off=0, out_off=0, fill=-9999.0, masked=-7777.5, nodata=0, count=True):
-    assert name not in ROWS, name
+def make_row(bands, layout, width, height, *, rows=4, cols=5, grid="mixed", q=False, bm=0, extra_bytes=0, window=None, gh=None,
+             gw=None, swath_off=0, out_off=0, fill=-9999.0, masked=-7777.5, nodata=0, count=True):
+    """The row itself, registered nowhere.  grid: one of glt_of's kinds, or ("drawn", seed, index): the table of glt_drawn."""
     gh, gw = gh or height, gw or width
-    ROWS[name] = dict(bands=bands, rows=rows, cols=cols, grid=grid, gh=gh, gw=gw, window=window or (0, 0, height, width), q=q,
-                      bbytes=((bands + 7) // 8 + extra_bytes) if bm else 0, layout=layout, swath_off=swath_off, out_off=out_off,
-                      fill=fill, masked=masked, nodata=nodata, count=count)
+    return dict(bands=bands, rows=rows, cols=cols, grid=grid, gh=gh, gw=gw, window=window or (0, 0, height, width), q=q,
+                bbytes=((bands + 7) // 8 + extra_bytes) if bm else 0, layout=layout, swath_off=swath_off, out_off=out_off,
+                fill=fill, masked=masked, nodata=nodata, count=count)
+
+
+def _row(name, *args, **kw):
+    assert name not in ROWS, name
+    ROWS[name] = make_row(*args, **kw)
 
 
 # every band count x layout x width; heights 1 and 3, the mask combinations and the base offsets rotate through the rows
@@ -212,17 +240,26 @@ for _layout in (BIP, BSQ):
     _row(f"max-bands-{_n}", MAX_BANDS, _layout, PX + 1, 1, bm=1)
 
 
-def row_instance(name):
-    r = ROWS[name]
+def instance_of(r):
     return instance(r["layout"], r["bands"], r["q"] or r["bbytes"] > 0, r["swath_off"], r["out_off"])
+
+
+def row_instance(name):
+    return instance_of(ROWS[name])
 
 
 @functools.lru_cache(maxsize=None)
 def case(name):
+    return case_of(ROWS[name])
+
+
+def case_of(r):
     """-> dict(swath, glt, qmask, bmask, ref (uint32 bits in the row's layout), ref_bip, dropped): the row's inputs and reference."""
-    r = ROWS[name]
     swath = swath_of(r["rows"], r["cols"], r["bands"])
-    glt = glt_of(r["grid"], r["gh"], r["gw"], r["rows"], r["cols"], r["nodata"])
+    if isinstance(r["grid"], tuple):
+        glt = glt_drawn(r["grid"][1:], r["gh"], r["gw"], r["rows"], r["cols"], r["nodata"])
+    else:
+        glt = glt_of(r["grid"], r["gh"], r["gw"], r["rows"], r["cols"], r["nodata"])
     qmask = qmask_of(r["rows"], r["cols"]) if r["q"] else None
     bmask = bmask_of(r["rows"], r["cols"], r["bands"], r["bbytes"]) if r["bbytes"] else None
     kw = dict(window=r["window"], qmask=qmask, bmask=bmask, fill=r["fill"], masked=r["masked"], nodata=r["nodata"])

@@ -130,6 +130,43 @@ def scan_ref(scene, th, tw, **kw):
     return window_counts(black_mask_np(scene, **kw), th, tw)
 
 
+def scan_row(dtype, bands, H, W, th, tw, nodata=None, masked_val=-0.01, nodata_atol=1e-3, zero_atol=1e-6, passed=0.0, key=0, density=0.3):
+    """One scan call on a scene of its own (planted_scene): the shape, the window, the settings of the call - nodata None: the
+    criterion is off and `passed` goes to the entry point instead - and what picks the scene."""
+    return dict(dtype=np.dtype(dtype), bands=bands, H=H, W=W, th=th, tw=tw, nodata=nodata, masked_val=masked_val, nodata_atol=nodata_atol,
+                zero_atol=zero_atol, passed=passed, key=key, density=density)
+
+
+def scan_settings(r):
+    return {k: r[k] for k in ("nodata", "masked_val", "nodata_atol", "zero_atol")}
+
+
+@functools.lru_cache(maxsize=64)
+def planted_scene(dtype, bands, H, W, key, density=0.3):
+    """Valid noise with black pixels planted at random: about `density` of the pixels hold one black value of BLACK_VALUES in
+    every band, and half of those are broken in one random band - by a valid sample or by a sample beside a tolerance edge
+    (f32_edge_values() / U16_SAMPLES) - so that the band which decides a pixel, and ends a wave's band loop, is random."""
+    dtype = np.dtype(dtype)
+    rng = np.random.default_rng([key, bands, H, W, dtype.itemsize])
+    if dtype == F32:
+        scene, near = rng.uniform(0.05, 0.6, (bands, H, W)).astype(np.float32), f32_edge_values()
+    else:
+        scene, near = rng.integers(1, 4000, (bands, H, W)).astype(np.uint16), np.array(U16_SAMPLES, np.uint16)
+    values = np.array(list(BLACK_VALUES[dtype].values()), dtype)
+    black = rng.random((H, W)) < density
+    scene[:, black] = values[rng.integers(0, len(values), int(black.sum()))]
+    ys, xs = np.nonzero(black & (rng.random((H, W)) < 0.5))
+    b = rng.integers(0, bands, len(ys))
+    scene[b, ys, xs] = np.where(rng.random(len(ys)) < 0.5, near[rng.integers(0, len(near), len(ys))], scene[b, (ys + 1) % H, xs])
+    scene.setflags(write=False)
+    return scene
+
+
+def scan_case_of(r):
+    scene = planted_scene(r["dtype"], r["bands"], r["H"], r["W"], r["key"], r["density"])
+    return dict(scene=scene, ref=scan_ref(scene, r["th"], r["tw"], **scan_settings(r)))
+
+
 def scan_tilings(H, W):
     """(1, 1): a wave meets 64 windows in a row; one window; (5, 3); a new window row on every row; window edges on and off the
     wave boundaries."""
@@ -395,9 +432,27 @@ def gather_ref(scene, origins, th, tw, encode):
 GATHER_ROWS = {}
 
 
-def _gather_row(name, dtype, encode, th, tw, off, shape=GATHER_SHAPE, origins=None):
-    org = gather_origins(th, tw, shape[1], shape[2]) if origins is None else np.array(origins, np.int32)
-    GATHER_ROWS[name] = (np.dtype(dtype), encode, shape, org, th, tw, off)
+def gather_row(dtype, encode, th, tw, off, shape=GATHER_SHAPE, origins=None):
+    """The row itself, registered nowhere."""
+    org = gather_origins(th, tw, shape[1], shape[2]) if origins is None else np.array(origins, np.int32).reshape(-1, 2)
+    return (np.dtype(dtype), encode, tuple(shape), org, th, tw, off)
+
+
+def _gather_row(name, *args, **kw):
+    GATHER_ROWS[name] = gather_row(*args, **kw)
+
+
+def gather_case_of(row):
+    """-> dict(scene, want, inside): the row's scene (gather_scene of its dtype and shape) and gather_ref on it."""
+    dtype, encode, shape, org, th, tw, _ = row
+    scene = gather_scene(dtype, shape)
+    want, inside = gather_ref(scene, org, th, tw, encode)
+    return dict(scene=scene, want=want, inside=inside)
+
+
+def gather_instance_of(row):
+    dtype, encode, _, _, _, tw, off = row
+    return gather_instance(dtype, encode is not None, tw, off)
 
 
 for _d, _n, _e, _sz in ((F32, "f32", None, 4), (U16, "u16", None, 2), (F32, "enc_nd", ENC_ND, 2), (F32, "enc_plain", ENC_PLAIN, 2),
@@ -417,8 +472,7 @@ GATHER_CHUNK_ROWS = ("chunk-scalar-u16", "chunk-scalar-enc", "chunk-vec-f32")
 
 
 def gather_row_instance(name):
-    dtype, encode, _, _, _, tw, off = GATHER_ROWS[name]
-    return gather_instance(dtype, encode is not None, tw, off)
+    return gather_instance_of(GATHER_ROWS[name])
 
 
 # =============================================================================================================================
@@ -462,10 +516,15 @@ MOSAIC_ROW_LOOP = {"row-loop-vec": 32, "row-loop-scalar": 32, "z-limit": 1}     
 
 @functools.lru_cache(maxsize=None)
 def mosaic_case(name):
+    return mosaic_case_of(MOSAIC_ROWS[name], sum(map(ord, name)))
+
+
+def mosaic_case_of(row, seed, drawn_slots=False):
     """-> (cubes (P, T, th, tw) with a NaN and a NaN payload, slot (H // th, W // tw)): cubes used once, twice and not at all,
-    -1 (fill), -2 (leave alone) and an index past the stack (leave alone)."""
-    T, H, W, th, tw, P, *_ = MOSAIC_ROWS[name]
-    rng = np.random.default_rng(sum(map(ord, name)))
+    -1 (fill), -2 (leave alone) and an index past the stack (leave alone) - in the table's fixed pattern, or (drawn_slots) every
+    slot drawn on its own from -2 .. P + 2."""
+    T, H, W, th, tw, P, *_ = row
+    rng = np.random.default_rng(seed)
     cubes = rng.standard_normal((P, T, th, tw)).astype(np.float32)
     if P:                                                  # both in cube 0, which every slot grid uses
         cubes[0, 0, th // 2, tw - 1] = np.nan
@@ -473,14 +532,18 @@ def mosaic_case(name):
     ny, nx = H // th, W // tw
     slot = np.full(ny * nx, -1, np.int32)
     pattern = [0, 3, -2, 1, 2, 0, 9, -2, -1, 4]
-    slot[:] = [pattern[i % len(pattern)] for i in range(ny * nx)]
+    slot[:] = rng.integers(-2, P + 3, ny * nx) if drawn_slots else [pattern[i % len(pattern)] for i in range(ny * nx)]
     slot[-1] = -1
     return cubes, slot.reshape(ny, nx)
 
 
-def mosaic_row_instance(name):
-    _, _, W, _, tw, P, out_off, cubes_off, _ = MOSAIC_ROWS[name]
+def mosaic_instance_of(row):
+    _, _, W, _, tw, P, out_off, cubes_off, _ = row
     return mosaic_instance(W, tw, out_off, cubes_off if P else 0)
+
+
+def mosaic_row_instance(name):
+    return mosaic_instance_of(MOSAIC_ROWS[name])
 
 
 # =============================================================================================================================
@@ -514,19 +577,29 @@ for _r in BLEND_ROWS.values():
     _r.setdefault("cubes_off", 0)
 
 
-def blend_row_instance(name):
-    r = BLEND_ROWS[name]
+def blend_row(th, tw, sy, sx, H, W, T=3, kind="lattice", out_off=0, cubes_off=0):
+    """The row itself, registered nowhere."""
+    return dict(th=th, tw=tw, sy=sy, sx=sx, H=H, W=W, T=T, kind=kind, out_off=out_off, cubes_off=cubes_off)
+
+
+def blend_instance_of(r):
     return blend_instance(r["W"], r["th"], r["tw"], r["sy"], r["sx"], r["out_off"], r["cubes_off"])
+
+
+def blend_row_instance(name):
+    return blend_instance_of(BLEND_ROWS[name])
 
 
 @functools.lru_cache(maxsize=None)
 def blend_case(name):
+    return blend_case_of(BLEND_ROWS[name], sum(map(ord, name)))
+
+
+def blend_case_of(r, seed):
     """-> dict(cubes, start, K, ref): make_case of test_gpu_scene_blend.py for the row's geometry (holes, bad and spare entries, NaN,
-    a payload, an all-NaN pixel), with a start table cut short, or whose tile does not fit, or more planes, where the row says
-    so; ref is blend_ref64 of exactly what the kernel is given."""
-    r = BLEND_ROWS[name]
+    a payload, an all-NaN pixel), with a start table cut short, or whose tile does not fit, or more or fewer planes, where the row
+    says so; ref is blend_ref64 of exactly what the kernel is given."""
     th, tw, sy, sx, H, W, T = (r[k] for k in ("th", "tw", "sy", "sx", "H", "W", "T"))
-    seed = sum(map(ord, name))
     if r["kind"] == "nofit":                               # make_case needs room for a window: build the table by hand
         rng = np.random.default_rng(seed)
         cubes = rng.random((2, T, th, tw), dtype=np.float32)
@@ -535,7 +608,9 @@ def blend_case(name):
         cubes, start, K = make_case(th, tw, sy, sx, H, W, seed)
         if r["kind"] == "short":
             start = np.ascontiguousarray(start[:start.shape[0] - 3, :start.shape[1] - 2])
-        if T != cubes.shape[1]:                            # more planes: the first three keep what make_case planted
+        if T < cubes.shape[1]:
+            cubes = np.ascontiguousarray(cubes[:, :T])
+        if T > cubes.shape[1]:                             # more planes: the first three keep what make_case planted
             rng = np.random.default_rng(seed + 1)
             more = rng.random((cubes.shape[0], T, th, tw), dtype=np.float32) * 0.98 + 0.01
             more[rng.random(more.shape) < 0.05] = np.nan

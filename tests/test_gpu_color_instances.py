@@ -12,57 +12,18 @@ import numpy as np
 import pytest
 
 import affine_cases as ac
-from gpu_harness import FILL, SENT32, Buf, LaunchLog, same_bits, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import FILL, Buf, LaunchLog, same_bits, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
 from gpu_harness import lib as _lib, stream as _stream
+from family_runners import REDUCE, color_image as _image, lohi_buf as _lohi, ptr_of as _ptr, run_apply, run_moments, run_moments_f64
 
 pytestmark = pytest.mark.gpu
 
 LOG = LaunchLog("hsr_color_last_launch", joined=True)
-REDUCE = "affine_reduce_solve_kernel"
-
-
-def _image(torch, rows, place):
-    layout, off = place
-    flat = ac.pack(rows, layout)
-    return Buf(torch, flat.nbytes, off, flat), flat
-
-
-def _untouched(buf, flat):
-    np.testing.assert_array_equal(buf.get(np.uint32), flat.view(np.uint32))
-
-
-def _lohi(torch, lohi):
-    return Buf(torch, 48, 0, np.ascontiguousarray(lohi, np.float64)) if lohi is not None else None
-
-
-def _ptr(b):
-    return b.ptr if b is not None else None
 
 
 def _moments(torch, name):
     """The row's moments launch + reduce (min_count above every count: the solve is the identity) -> (22 moments, slots)."""
-    r, c = ac.MOMENT_ROWS[name], ac.moment_case(name)
-    npix = r["npix"]
-    xb, xflat = _image(torch, c["x"], r["x"])
-    yb, yflat = _image(torch, c["y"], r["y"])
-    mb = Buf(torch, npix, 1, c["mask"]) if c["mask"] is not None else None            # the mask needs no alignment: 1 byte off
-    lx, ly = _lohi(torch, r["lohi_x"]), _lohi(torch, r["lohi_y"])
-    nslots = ac.slots(npix)
-    pb = Buf(torch, nslots * ac.NMOM * 8, 0)
-    slots = C.c_int32(-1)
-    xbs, xps, _ = ac.strides(r["x"][0], npix)
-    ybs, yps, _ = ac.strides(r["y"][0], npix)
-    LOG.call([ac.moments_instance(r)], _lib().hsr_affine_moments, xb.ptr, xbs, xps, yb.ptr, ybs, yps, _ptr(mb), npix, _ptr(lx), _ptr(ly),
-             pb.ptr, C.byref(slots), _stream(torch))
-    assert slots.value == nslots == _lib().hsr_affine_partial_slots(npix)
-    partials = pb.get(np.uint64)
-    assert (partials != np.frombuffer(bytes([FILL] * 8), np.uint64)[0]).all()                  # every partial is written
-    mo, at = Buf(torch, ac.NMOM * 8, 0), Buf(torch, 96, 0)
-    LOG.call([REDUCE], _lib().hsr_affine_reduce_solve, pb.ptr, nslots, 1 << 40, mo.ptr, at.ptr, _stream(torch))
-    _untouched(xb, xflat)
-    _untouched(yb, yflat)
-    assert np.array_equal(at.get(np.float64), np.concatenate([np.eye(3).reshape(-1), np.zeros(3)]))
-    return mo.get(np.float64), partials.view(np.float64).reshape(nslots, ac.NMOM)
+    return run_moments(torch, ac.MOMENT_ROWS[name], ac.moment_case(name), LOG)
 
 
 @pytest.mark.parametrize("name", list(ac.MOMENT_ROWS))
@@ -129,16 +90,9 @@ def test_zero_pixels(torch_gpu):
 
 
 # ---- solve ------------------------------------------------------------------------------------------------------------------------------
-def _solve_f64(torch, name, chunks=1):
-    r, c = ac.SOLVE_ROWS[name], ac.solve_case(name)
-    n = r["n"]
-    xb = Buf(torch, max(n, 1) * 24, 0, c["xs"] if n else None)
-    yb = Buf(torch, max(n, 1) * 24, 8, c["ys"] if n else None)
-    nslots = ac.slots(n)
-    pb, mo, at = Buf(torch, nslots * ac.NMOM * 8, 0), Buf(torch, ac.NMOM * 8, 0), Buf(torch, 96, 0)
-    LOG.call(["affine_moments_f64_kernel"], _lib().hsr_affine_moments_f64, xb.ptr, 3, yb.ptr, 3, n, pb.ptr, None, _stream(torch))
-    LOG.call([REDUCE], _lib().hsr_affine_reduce_solve, pb.ptr, nslots, r["min_count"], mo.ptr, at.ptr, _stream(torch))
-    return mo.get(np.float64), at.get(np.float64)
+def _solve_f64(torch, name):
+    mom, at, _ = run_moments_f64(torch, ac.SOLVE_ROWS[name], ac.solve_case(name), LOG, min_count=ac.SOLVE_ROWS[name]["min_count"])
+    return mom, at
 
 
 @pytest.mark.parametrize("name", list(ac.SOLVE_ROWS))
@@ -176,28 +130,7 @@ def test_solve_through_the_image_kernel(torch_gpu):
 # ---- apply ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(ac.APPLY_ROWS))
 def test_apply_rows(torch_gpu, name):
-    torch = torch_gpu
-    r, c = ac.APPLY_ROWS[name], ac.apply_case(name)
-    npix = r["npix"]
-    xb, xflat = _image(torch, c["x"], r["x"])
-    mb = Buf(torch, npix, 3, c["mask"]) if c["mask"] is not None else None
-    at = Buf(torch, 96, 0, np.ascontiguousarray(r["At"], np.float64))
-    lo = _lohi(torch, r["lohi"])
-    olayout, ooff = r["out"]
-    obs, ops, ofloats = ac.strides(olayout, npix)
-    ob = Buf(torch, ofloats * 4, ooff)
-    xbs, xps, _ = ac.strides(r["x"][0], npix)
-    LOG.call([ac.apply_instance(r)], _lib().hsr_affine_apply, xb.ptr, xbs, xps, _ptr(mb), at.ptr, npix, _ptr(lo), r["clip"], ob.ptr,
-             obs, ops, _stream(torch))
-    rows, beside = ac.unpack(ob.get(np.float32), olayout, npix)                               # get(): the guard zones are intact
-    same_bits(np.ascontiguousarray(rows), c["ref"], name)
-    if olayout == ac.PADDED:
-        assert (beside.view(np.uint32) == 0).all()                                             # the fourth float: written, +0.0
-    elif olayout == ac.PLANAR:
-        assert (beside.view(np.uint32) == SENT32).all()                                        # the gap between planes: not written
-    _untouched(xb, xflat)
-    if mb is not None:
-        np.testing.assert_array_equal(mb.get(np.uint8), c["mask"])
+    same_bits(run_apply(torch_gpu, ac.APPLY_ROWS[name], ac.apply_case(name), LOG), ac.apply_case(name)["ref"], name)
 
 
 def test_refused_calls_launch_nothing(torch_gpu):

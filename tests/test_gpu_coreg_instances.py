@@ -16,36 +16,15 @@ import pytest
 import coreg_cases as cc
 from gpu_harness import FILL, Buf, LaunchLog, bits_equal, same_bits, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
 from gpu_harness import lib as _lib, stream as _stream
+from family_runners import SENT64, run_model, run_peaks, run_surface, run_warp
 
 pytestmark = pytest.mark.gpu
 
 LOG = LaunchLog("hsr_coreg_last_launch", joined=True)
-SENT64 = np.frombuffer(bytes([FILL] * 8), np.uint64)[0]
-
-
-def _untouched(buf, back):
-    np.testing.assert_array_equal(buf.get(np.uint8), np.ascontiguousarray(back).reshape(-1).view(np.uint8))
 
 
 def _surface(torch, name):
-    r, c = cc.SURFACE_ROWS[name], cc.surface_case(name)
-    P, D = len(c["origins"]), 2 * r["R"] + 1
-    eb = Buf(torch, c["emit_back"].nbytes, r["offs"][0], c["emit_back"])
-    sb = Buf(torch, c["s2_back"].nbytes, r["offs"][1], c["s2_back"])
-    mb = Buf(torch, c["mask_back"].nbytes, r["offs"][2], c["mask_back"]) if c["mask"] is not None else None
-    ob = Buf(torch, c["origins"].nbytes, 0, c["origins"])
-    out = Buf(torch, P * D * D * 8, 8)
-    nd = c["nodata"]
-    LOG.call([cc.surface_instance(r)], _lib().hsr_coreg_surface, eb.ptr, c["emit_rs"], r["he"], r["we"], mb.ptr if mb else None,
-             c["mask_rs"], sb.ptr, 1 if r["dtype"] == "u16" else 0, c["s2_rs"], c["hs"], c["ws"], 0 if nd is None else 1,
-             0.0 if nd is None else float(nd), ob.ptr, P, r["w"], r["f"], r["R"], c["min_valid"], out.ptr, _stream(torch))
-    got = out.get(np.float64).reshape(P, D, D)
-    _untouched(eb, c["emit_back"])
-    _untouched(sb, c["s2_back"])
-    _untouched(ob, c["origins"])
-    if mb:
-        _untouched(mb, c["mask_back"])
-    return got
+    return run_surface(torch, cc.SURFACE_ROWS[name], cc.surface_case(name), LOG)
 
 
 @pytest.mark.parametrize("name", list(cc.SURFACE_ROWS))
@@ -74,15 +53,8 @@ def test_peak_rows(torch_gpu):
         c = cc.surface_case(name)
         jobs.append((name, c["ref"], c["origins"], r["w"], r["f"], r["R"], dict(he=r["he"], we=r["we"], hs=c["hs"], ws=c["ws"]), 0.6))
     for tag, S, org, w, f, R, sh, min_score in jobs:
-        P = len(org)
-        sb, ob = Buf(torch, S.nbytes, 8, S), Buf(torch, org.nbytes, 4, np.ascontiguousarray(org, np.int32))
-        tb = Buf(torch, P * cc.REC * 8, 8)
-        LOG.call(["coreg_peaks_kernel"], _lib().hsr_coreg_peaks, sb.ptr, ob.ptr, P, w, f, R, sh["he"], sh["we"], sh["hs"], sh["ws"],
-                 min_score, tb.ptr, _stream(torch))
-        got = tb.get(np.float64).reshape(P, cc.REC)
-        assert (got.view(np.uint64) != SENT64).all()
+        got = run_peaks(torch, dict(sh, w=w, f=f, R=R, min_score=min_score), dict(surface=S, origins=org), LOG)
         same_bits(got, cc.peaks_ref(S, org, w, f, R, min_score=min_score, **sh), "peaks " + tag)
-        _untouched(sb, S)
         if tag == "crafted":
             assert np.array_equal(got[:, 7], want)
         if tag == "crafted-rect":
@@ -91,12 +63,7 @@ def test_peak_rows(torch_gpu):
 
 
 def _fit(torch, r):
-    table = np.array(r["table"], np.float64)
-    tb = Buf(torch, max(table.nbytes, 8), 8, table if table.size else None)
-    mb = Buf(torch, cc.MODEL * 8, 8)
-    LOG.call(["coreg_fit_model_kernel"], _lib().hsr_coreg_fit_model, tb.ptr, len(table), r["kind"], r["min_points"], r["reject_px"],
-             r["hs"], r["ws"], mb.ptr, _stream(torch))
-    return tb.get(np.float64)[:table.size].reshape(-1, cc.REC), mb.get(np.float64)
+    return run_model(torch, r, None, LOG)
 
 
 @pytest.mark.parametrize("name", list(cc.MODEL_ROWS_ALL))
@@ -120,28 +87,7 @@ def test_model_rows(torch_gpu, name):
 def _warp(torch, name, row=None):
     """The warp of case `name` (under the bound of `row`, when given) -> (output without its padding, status word).  The input
     and the output have their own row padding, gap after every band and base offset; all of it must stay as it was."""
-    r, c = row or cc.WARP_ROWS[name], cc.warp_case(name)
-    scene = c["scene"]
-    bands, h, w = scene.shape
-    u16 = r["dtype"] == "u16"
-    inb = cc.pack_scene(scene, r["extra"], scene.dtype.type(3), r["in_gap"])
-    irs, ors = w + r["extra"], w + r["out_extra"]
-    ibs, obs = h * irs + r["in_gap"], h * ors + r["out_gap"]
-    assert inb.shape == (bands, ibs)
-    ib = Buf(torch, inb.nbytes, r["off"], inb)
-    ob = Buf(torch, bands * obs * scene.dtype.itemsize, r["out_off"])
-    mb, sb = Buf(torch, cc.MODEL * 8, 8, c["model"]), Buf(torch, 4, 4)
-    nd = c["nodata"]
-    LOG.call([cc.warp_instance(r["dtype"], r["bound"][1])], _lib().hsr_coreg_warp, ib.ptr, 1 if u16 else 0, bands, h, w, ibs, irs, mb.ptr,
-             0 if nd is None else 1, 0.0 if nd is None else float(nd), c["fill"], r["bound"][0], r["bound"][1], ob.ptr, obs, ors, sb.ptr,
-             _stream(torch))
-    out, outside = cc.unpack_scene(ob.get(scene.dtype).reshape(bands, obs), h, w, r["out_extra"])
-    raw = ob.get(np.uint16 if u16 else np.uint32).reshape(bands, obs)
-    sent = np.frombuffer(bytes([FILL] * scene.dtype.itemsize), raw.dtype)[0]
-    assert outside.sum() == bands * (h * r["out_extra"] + r["out_gap"]) and (raw[outside] == sent).all()   # row padding and band gaps
-    _untouched(ib, inb)
-    _untouched(mb, c["model"])
-    return out, int(sb.get(np.int32)[0])
+    return run_warp(torch, row or cc.WARP_ROWS[name], cc.warp_case(name), LOG)
 
 
 @pytest.mark.parametrize("name", list(cc.WARP_ROWS))

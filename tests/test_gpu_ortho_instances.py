@@ -14,6 +14,7 @@ import pytest
 import ortho_cases as oc
 from gpu_harness import FILL, Buf, LaunchLog, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
 from gpu_harness import lib as _lib, stream as _stream
+from family_runners import run_ortho
 
 pytestmark = pytest.mark.gpu
 
@@ -22,27 +23,7 @@ LOG = LaunchLog("hsr_ortho_last_launch")
 
 def _run(torch, name, layout=None, count=None):
     """The row `name` (optionally in the other layout) -> (output bits in that layout's shape, dropped or None)."""
-    r, c = oc.ROWS[name], oc.case(name)
-    layout = r["layout"] if layout is None else layout
-    count = r["count"] if count is None else count
-    swath, glt = c["swath"], c["glt"]
-    r0, c0, h, w = r["window"]
-    sb = Buf(torch, swath.nbytes, r["swath_off"], swath)
-    gb = Buf(torch, glt.nbytes, 0, glt)
-    qb = Buf(torch, c["qmask"].nbytes, 0, c["qmask"]) if r["q"] else None
-    bb = Buf(torch, c["bmask"].nbytes, 0, c["bmask"]) if r["bbytes"] else None
-    db = Buf(torch, 8, 8) if count else None                              # holds the sentinel: the call has to zero it
-    ob = Buf(torch, h * w * r["bands"] * 4, r["out_off"])
-    expect = oc.instance(layout, r["bands"], r["q"] or r["bbytes"] > 0, r["swath_off"], r["out_off"])
-    LOG.call(expect, _lib().hsr_ortho_glt, sb.ptr, r["rows"], r["cols"], r["bands"], gb.ptr, r["gh"], r["gw"], r["nodata"], r0, c0, h, w,
-             qb.ptr if qb else None, bb.ptr if bb else None, r["bbytes"], r["fill"], r["masked"], layout, ob.ptr,
-             db.ptr if db else None, _stream(torch))
-    got = ob.get(np.uint32).reshape((h, w, r["bands"]) if layout == oc.BIP else (r["bands"], h, w))
-    for b in (sb, gb, qb, bb):                                            # the inputs and their guards are as they were
-        if b is not None:
-            b.get(np.uint8)
-    np.testing.assert_array_equal(sb.get(np.float32).view(np.uint32), swath.view(np.uint32).reshape(-1))
-    return got, (int(db.get(np.int64)[0]) if db else None)
+    return run_ortho(torch, oc.ROWS[name], oc.case(name), LOG, layout=layout, count=count)
 
 
 @pytest.mark.parametrize("name", list(oc.ROWS))

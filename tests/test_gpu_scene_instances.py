@@ -12,36 +12,24 @@ import numpy as np
 import pytest
 
 import scene_cases as sc
-from gpu_harness import FILL, SENT16, SENT32, Buf, LaunchLog, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
-from gpu_harness import lib as _lib, stream as _stream
+from gpu_harness import FILL, SENT32, Buf, LaunchLog, torch_gpu  # noqa: F401  (torch_gpu: the fixture)
+from gpu_harness import lib as _lib
+from family_runners import bits as _bits, run_blend, run_gather, run_mosaic, scan_call
 from test_scene_blend_host import check_blend
 
 pytestmark = pytest.mark.gpu
 
 LOG = LaunchLog("hsr_scene_last_launch")
-_call = LOG.call
 WORST = {}                       # K -> largest blend error over its bound
 F32, U16 = sc.F32, sc.U16
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
 
 
 # =============================================================================================================================
 # scan
 # =============================================================================================================================
-def _scan(torch, sb, scene, th, tw, nodata=None, masked_val=-0.01, nodata_atol=1e-3, zero_atol=1e-6, passed=0.0):
-    """hsr_scene_black_counts on the scene in Buf `sb` -> the (H // th, W // tw) counts.  The counts start 4 bytes past a 256-byte
-    boundary - 4-byte but not 16-byte aligned - and hold the sentinel, which the call has to zero."""
-    bands, H, W = scene.shape
-    ny, nx = H // th, W // tw
-    cb = Buf(torch, ny * nx * 4, 4)
-    use, nd = (0, passed) if nodata is None else (1, nodata)
-    _call(sc.scan_instance(scene.dtype), _lib().hsr_scene_black_counts, sb.ptr, sc.DT_CODE[scene.dtype], bands, H, W, th, tw, use, nd,
-          masked_val, nodata_atol, zero_atol, cb.ptr, _stream(torch))
-    return cb.get(np.int32).reshape(ny, nx)
+def _scan(torch, sb, scene, th, tw, **kw):
+    """hsr_scene_black_counts on the scene in Buf `sb` -> the (H // th, W // tw) counts."""
+    return scan_call(torch, sb, scene, th, tw, LOG, **kw)
 
 
 @pytest.mark.parametrize("dtype", [F32, U16], ids=["float32", "uint16"])
@@ -114,21 +102,10 @@ def test_scan_float32_several_rows_per_wave(torch_gpu):
 # =============================================================================================================================
 @pytest.mark.parametrize("name", list(sc.GATHER_ROWS))
 def test_gather_rows(torch_gpu, name):
-    torch, lib = torch_gpu, _lib()
-    dtype, encode, shape, org, th, tw, off = sc.GATHER_ROWS[name]
-    scene = sc.gather_scene(dtype, shape)
-    bands, H, W = shape
-    want, inside = sc.gather_ref(scene, org, th, tw, encode)
-    sb, gb = Buf(torch, scene.nbytes, 0, scene), Buf(torch, org.nbytes, 0, org)
-    ob = Buf(torch, want.nbytes, off)
-    scale, has_nd, nd, nd16 = encode if encode else (1.0, 0, 0.0, 65535)
-    _call(sc.gather_row_instance(name), lib.hsr_scene_gather_tiles, sb.ptr, sc.DT_CODE[dtype], bands, H, W, gb.ptr, len(org), th, tw,
-          int(encode is not None), scale, has_nd, nd, nd16, ob.ptr, _stream(torch))
-    got = ob.get(want.dtype).reshape(want.shape)
-    np.testing.assert_array_equal(_bits(got[inside]), _bits(want[inside]))
-    sentinel = SENT32 if want.dtype == np.float32 else SENT16
-    assert (_bits(got[~inside]) == sentinel).all(), "a window outside the scene was written"
-    sb.get(np.uint8)
+    row = sc.GATHER_ROWS[name]
+    c = sc.gather_case_of(row)
+    got = run_gather(torch_gpu, row, c, LOG)
+    np.testing.assert_array_equal(_bits(got[c["inside"]]), _bits(c["want"][c["inside"]]))
 
 
 # =============================================================================================================================
@@ -136,36 +113,21 @@ def test_gather_rows(torch_gpu, name):
 # =============================================================================================================================
 @pytest.mark.parametrize("name", list(sc.MOSAIC_ROWS))
 def test_mosaic_rows(torch_gpu, name):
-    torch, lib = torch_gpu, _lib()
     T, H, W, th, tw, P, out_off, cubes_off, fills = sc.MOSAIC_ROWS[name]
     cubes, slot = sc.mosaic_case(name)
-    cb = Buf(torch, cubes.nbytes, cubes_off, cubes) if P else None
-    sl = Buf(torch, slot.nbytes, 0, slot)
     pre = np.frombuffer(bytes([FILL]) * (T * H * W * 4), np.float32).reshape(T, H, W)
     for fill, fill_rest in fills:
-        ob = Buf(torch, T * H * W * 4, out_off)
-        _call(sc.mosaic_row_instance(name), lib.hsr_scene_mosaic, cb.ptr if P else None, P, T, th, tw, ob.ptr, H, W, sl.ptr,
-              slot.shape[0], slot.shape[1], float(fill), int(fill_rest), _stream(torch))
-        got = ob.get(np.uint32).reshape(T, H, W)
+        got = run_mosaic(torch_gpu, sc.MOSAIC_ROWS[name], (cubes, slot), LOG, fill, fill_rest)
         want = sc.assemble(cubes, slot, pre, th, tw, fill, fill_rest)
         np.testing.assert_array_equal(got, _bits(want))
         assert (got == SENT32).any() or name == "z-limit"
-    if P:
-        cb.get(np.uint8)
 
 
 # =============================================================================================================================
 # blend
 # =============================================================================================================================
 def _blend(torch, name, case, fill):
-    lib, r = _lib(), sc.BLEND_ROWS[name]
-    cubes, start = case["cubes"], case["start"]
-    P, T, th, tw = cubes.shape
-    cb, sb = Buf(torch, cubes.nbytes, r["cubes_off"], cubes), Buf(torch, start.nbytes, 0, start)
-    ob = Buf(torch, T * r["H"] * r["W"] * 4, r["out_off"])
-    _call(sc.blend_row_instance(name), lib.hsr_scene_mosaic_blend, cb.ptr, P, T, th, tw, r["sy"], r["sx"], sb.ptr, start.shape[0],
-          start.shape[1], ob.ptr, r["H"], r["W"], float(fill), _stream(torch))
-    return ob.get(np.float32).reshape(T, r["H"], r["W"])
+    return run_blend(torch, sc.BLEND_ROWS[name], case, LOG, fill)
 
 
 @pytest.mark.parametrize("name", list(sc.BLEND_ROWS))
