@@ -123,9 +123,18 @@ enum CoregInstance : int {
   kCoregInstances = kCoregWarp + 4
 };
 
+// Kernel instances of hsr_reproject.hip, the index of the name table behind hsr_reproject_last_launch / hsr_reproject_instance_name
+// (csrc/hsr_lib.hip, include/hsr_reproject.h): a table of its own, so the seven others keep their sizes.
+enum ReprojectInstance : int {
+  kReprojectCoords = 0,
+  kReprojectWarp,                          // + 2 * (0 LDS, 1 DIRECT) + (0 STRICT, 1 RENORM)
+  kReprojectInstances = kReprojectWarp + 4
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg}_last_launch, csrc/hsr_lib.hip).
-enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchFamilies };
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject,
+                          kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "hsr_common.h"
+#include "hsr_cubic_dev.h"
 #include "hsr_solve.h"
 #include "hsr_tree_dev.h"
 #include "../../include/hsr_coreg.h"
@@ -350,13 +351,6 @@ struct WarpArgs {
   int cap;                 // elements of the staged footprint (LDS instance)
 };
 
-__device__ __forceinline__ void keys_weights(double t, double (&wt)[4]) {
-  wt[0] = ((-0.5 * t + 1.0) * t - 0.5) * t;
-  wt[1] = ((1.5 * t - 2.5) * t) * t + 1.0;
-  wt[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
-  wt[3] = ((0.5 * t - 0.5) * t) * t;
-}
-
 template <typename T>
 __device__ __forceinline__ T warp_store_value(double v);
 template <>
@@ -365,10 +359,6 @@ template <>
 __device__ __forceinline__ uint16_t warp_store_value<uint16_t>(double v) {
   const double r = rint(v);                                      // round half to even
   return (uint16_t)(r >= 65535.0 ? 65535.0 : (r > 0.0 ? r : 0.0));   // NaN -> 0
-}
-
-__device__ __forceinline__ int clamp_to_int(double v, int lo, int hi) {
-  return v >= (double)hi ? hi : (v > (double)lo ? (int)v : lo);   // NaN -> lo
 }
 
 template <typename T, bool LDS>

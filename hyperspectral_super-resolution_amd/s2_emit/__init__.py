@@ -23,6 +23,8 @@ from .scenes import (Window, SceneOutput, scene_windows, select_tiles, find_vali
 from .ortho import OrthoOutput, apply_glt, ortho_scene, glt_from_xy, quality_mask
 from .coreg import (TiePoints, ShiftModel, CoregOutput, closest_band, tie_point_grid, match_windows, fit_shift_model, warp_scene,
                     coregister_scene)
+from .reproject import (ReprojectOutput, utm_params, tm_forward, tm_inverse, utm_target_grid, reproject_coords, remap_scene,
+                        reproject_scene)
 from ._native import HsrUnavailable, HsrError
 
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
@@ -41,5 +43,7 @@ _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real
           "Window", "SceneOutput",
           "coregister_scene", "match_windows", "fit_shift_model", "warp_scene", "tie_point_grid", "closest_band",
           "TiePoints", "ShiftModel", "CoregOutput",
+          "reproject_scene", "remap_scene", "reproject_coords", "utm_target_grid", "utm_params", "tm_forward", "tm_inverse",
+          "ReprojectOutput",
           "apply_glt", "ortho_scene", "glt_from_xy", "quality_mask", "OrthoOutput"]
 __all__ = _REFERENCE_SURFACE + _COPIED_BY_CALLERS + _FUSED

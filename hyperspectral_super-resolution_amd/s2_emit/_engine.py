@@ -1003,6 +1003,67 @@ def coreg_warp(scene, model, fill: float, max_abs_shift: float, max_abs_slope: f
     return o, status
 
 
+# ---------------------------------------------------------------------------------------------
+# reprojection (include/hsr_reproject.h, csrc/hsr_reproject.hip)
+# ---------------------------------------------------------------------------------------------
+def _reproject_geometry(grid, proj, src_gt):
+    """The 16 geometry arguments of hsr_reproject_coords: grid (e0, n0, dx, dy, h, w), proj (lon0, k0, FE, FN, a, inv_f),
+    src_gt (g0, g1, g3, g5)."""
+    e0, n0, dx, dy, h, w = grid
+    return ([float(e0), float(n0), float(dx), float(dy), int(h), int(w)] + [float(v) for v in proj] + [float(v) for v in src_gt])
+
+
+def reproject_coords(grid, proj, src_gt, device=None, out=None):
+    """The (h, w, 2) float64 field (sy, sx) of source indices on the device."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    h, w = int(grid[4]), int(grid[5])
+    if out is None:
+        if h < 1 or w < 1:
+            raise ValueError(f"the grid must have at least one cell, got {(h, w)}")
+        out = torch.empty((h, w, 2), dtype=torch.float64, device=device if device is not None else "cuda")
+    if not (out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (h, w, 2) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous ({h}, {w}, 2) float64 GPU tensor")
+    with _launch(out) as st:
+        nat.check(lib.hsr_reproject_coords(*_reproject_geometry(grid, proj, src_gt), _ptr(out), st), "hsr_reproject_coords")
+    return out
+
+
+def reproject_coords_host(grid, proj, src_gt) -> np.ndarray:
+    """Host twin of the coordinate kernel (the same C code compiled for the CPU): the (h, w, 2) float64 field as an array."""
+    lib = nat.load()
+    h, w = int(grid[4]), int(grid[5])
+    out = np.empty((max(h, 0), max(w, 0), 2), dtype=np.float64)
+    buf = out if out.size else np.zeros(2)
+    nat.check(lib.hsr_reproject_coords_host(*_reproject_geometry(grid, proj, src_gt), buf.ctypes.data_as(C.POINTER(C.c_double))),
+              "hsr_reproject_coords_host")
+    return out
+
+
+def reproject_warp(scene, coords, fill: float, rule: int, max_footprint: float, nodata=None, out=None, counts=None, status=None):
+    """The cubic remap of a (bands, hs, ws) float32 scene under a (h, w, 2) float64 field -> (out (bands, h, w), counts (2,) int64,
+    status (1,) int32), all on the device."""
+    torch = nat.require_gpu()
+    lib = nat.load()
+    if not (scene.is_cuda and scene.dim() == 3 and scene.dtype == torch.float32 and scene.stride(2) == 1):
+        raise ValueError("scene must be a (bands, rows, cols) float32 GPU tensor with unit column stride")
+    if not (coords.is_cuda and coords.dim() == 3 and coords.shape[2] == 2 and coords.dtype == torch.float64 and coords.is_contiguous()):
+        raise ValueError("coords must be a contiguous (h, w, 2) float64 GPU tensor")
+    b, hs, ws = (int(s) for s in scene.shape)
+    h, w = int(coords.shape[0]), int(coords.shape[1])
+    o = out if out is not None else torch.empty((b, h, w), dtype=torch.float32, device=scene.device)
+    if not (o.is_cuda and o.dtype == torch.float32 and tuple(o.shape) == (b, h, w) and o.stride(2) == 1):
+        raise ValueError(f"out must be a ({b}, {h}, {w}) float32 GPU tensor with unit column stride")
+    counts = counts if counts is not None else torch.empty(2, dtype=torch.int64, device=scene.device)
+    status = status if status is not None else torch.empty(1, dtype=torch.int32, device=scene.device)
+    with _launch(scene) as st:
+        nat.check(lib.hsr_reproject_warp(_ptr(scene), b, hs, ws, int(scene.stride(0)), int(scene.stride(1)), _ptr(coords), h, w,
+                                         0 if nodata is None else 1, 0.0 if nodata is None else float(nodata), float(fill), int(rule),
+                                         float(max_footprint), _ptr(o), int(o.stride(0)), int(o.stride(1)), _ptr(counts), _ptr(status),
+                                         st), "hsr_reproject_warp")
+    return o, counts, status
+
+
 def percentile_limits(x, mask=None, pmin=2.0, pmax=98.0, layout: str = PLANAR, nb: Optional[int] = None,
                       group=None, distributed: Optional[bool] = None, _reduce=None):
     """Exact np.percentile(vals[mask], [pmin, pmax]) per channel -> (nb, 2) float64 on the device.

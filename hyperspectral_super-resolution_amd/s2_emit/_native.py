@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h and include/hsr_coreg.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h and include/hsr_reproject.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -276,6 +276,20 @@ COREG_SIGNATURES = {
     "hsr_coreg_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The reprojection family, include/hsr_reproject.h: a table of its own like the two above; load() types all four.
+HSR_REPROJECT_STRICT, HSR_REPROJECT_RENORM = 0, 1
+HSR_REPROJECT_TILE_W, HSR_REPROJECT_TILE_H = 64, 8
+_REPROJECT_GEOMETRY = [_f64, _f64, _f64, _f64, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _f64]
+REPROJECT_SIGNATURES = {
+    "hsr_reproject_coords": (C.c_int, _REPROJECT_GEOMETRY + [_vp, _vp]),
+    "hsr_reproject_coords_host": (C.c_int, _REPROJECT_GEOMETRY + [_pf64]),
+    "hsr_reproject_warp": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i32, _f64, _f64, _i32, _f64, _vp, _i64, _i64,
+                                     _vp, _vp, _vp]),
+    "hsr_reproject_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_reproject_instance_count": (C.c_int, []),
+    "hsr_reproject_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -299,7 +313,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
+            + list(REPROJECT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -12,8 +12,8 @@ Here that is ``hsr_ortho_glt`` (csrc/hsr_ortho.hip, contract in include/hsr.h): 
 ``ortho_scene`` adds the masks, a window of the GLT grid and the band-sequential layout that ``s2_emit.scenes`` takes.
 
 What the result is NOT: it lies on the GLT's own grid (EMIT's geographic grid).  The reference then runs ``gdalwarp -r cubic``
-onto the Sentinel-2 UTM grid (emit_proj.py:876-940), which is not reproduced here; a caller who builds a lookup table for the
-S2 60 m grid itself lands there directly with the same call.  Reading the netCDF is left to the caller too.
+onto the Sentinel-2 UTM grid (emit_proj.py:876-940): that stage is ``reproject_scene`` (s2_emit/reproject.py), which takes this
+scene and its geotransform; a caller who builds a lookup table for the S2 60 m grid itself lands there directly with the same call.  Reading the netCDF is left to the caller too.
 """
 from __future__ import annotations
 
@@ -171,7 +171,7 @@ def ortho_scene(swath, glt, *, qmask=None, band_mask=None, window=None, layout="
     out      optional preallocated float32 device tensor of the scene's shape.
 
     One launch on the current stream, every output byte written once, no host synchronisation.  The scene lies on the GLT's own
-    grid: the reference's cubic warp onto the Sentinel-2 UTM grid (emit_proj.py:876-940) is NOT applied."""
+    grid, NOT on the Sentinel-2 UTM grid: ``reproject_scene`` is the reference's cubic warp onto it (emit_proj.py:876-940)."""
     plan = _plan_ortho(swath, glt, qmask, band_mask, window, layout, fill_value, masked_value, glt_nodata, out)
     torch = nat.require_gpu()
     lib = nat.load()
@@ -198,7 +198,7 @@ def apply_glt(ds_array, glt_array, fill_value=-9999, GLT_NODATA_VALUE=0):
     gives NumPy out, a tensor in gives a device tensor.  A non-float32 input is cast to float32 first, which is what NumPy's
     assignment into the float32 output does.  One departure: an entry that points outside the swath gives ``fill_value``
     (``ortho_scene``'s dropped rule) where the reference raises an IndexError or wraps a negative index.  The result lies on
-    the GLT's grid, not on the Sentinel-2 UTM grid (no cubic warp)."""
+    the GLT's grid, not on the Sentinel-2 UTM grid (``reproject_scene`` takes it there)."""
     res = ortho_scene(ds_array, glt_array, layout="bip", fill_value=fill_value, glt_nodata=GLT_NODATA_VALUE)
     return res.scene if _is_torch(ds_array) else res.scene.cpu().numpy()
 
