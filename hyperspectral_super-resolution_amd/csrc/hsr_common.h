@@ -131,9 +131,20 @@ enum ReprojectInstance : int {
   kReprojectInstances = kReprojectWarp + 4
 };
 
+// Kernel instances of hsr_scl.hip, the index of the name table behind hsr_scl_last_launch / hsr_scl_instance_name
+// (csrc/hsr_lib.hip, include/hsr_scl.h): a table of its own, so the eight others keep their sizes.
+enum SclInstance : int {
+  kSclCounts = 0,
+  kSclMask,                                // + 0 LOOKUP, 1 DISC, 2 SQUARE
+  kSclCoarse = kSclMask + 3,
+  kSclGather,
+  kSclApply,                               // + 0 UP1, 1 UP2
+  kSclInstances = kSclApply + 2
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject}_last_launch, csrc/hsr_lib.hip).
-enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl}_last_launch, csrc/hsr_lib.hip).
+enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
                           kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h and include/hsr_reproject.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h and include/hsr_scl.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -290,6 +290,25 @@ REPROJECT_SIGNATURES = {
     "hsr_reproject_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The scene-classification family, include/hsr_scl.h: a table of its own like the three above; load() types all five.
+HSR_SCL_BINS = 16
+HSR_SCL_MAX_RADIUS = 32
+HSR_SCL_DISC, HSR_SCL_SQUARE = 0, 1
+HSR_SCL_MAX_K = 16
+_u32 = C.c_uint32
+_SCL_MASK = [_vp, _i32, _i32, _i64, _u32, _u32, _i32, _i32, _vp, _i64]
+SCL_SIGNATURES = {
+    "hsr_scl_class_counts": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp]),
+    "hsr_scl_mask": (C.c_int, _SCL_MASK + [_vp]),
+    "hsr_scl_mask_host": (C.c_int, _SCL_MASK),
+    "hsr_scl_coarse": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "hsr_scl_gather_tiles": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "hsr_scl_apply": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _i32, _i64, _i32, C.c_float, _vp, _vp]),
+    "hsr_scl_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_scl_instance_count": (C.c_int, []),
+    "hsr_scl_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -314,7 +333,7 @@ def load() -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
-            + list(REPROJECT_SIGNATURES.items()):
+            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

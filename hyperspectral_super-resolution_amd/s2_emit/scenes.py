@@ -110,18 +110,37 @@ def _limits(max_black_frac, max_tiles):
     return frac, None if max_tiles is None else _int(max_tiles, "max_tiles")
 
 
+def _cloud_frac(max_cloud_frac) -> float:
+    try:
+        frac = float(max_cloud_frac)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_cloud_frac={max_cloud_frac!r}: must be a number") from None
+    if frac != frac:
+        raise ValueError("max_cloud_frac is NaN")
+    return frac
+
+
 def select_tiles(windows, emit_counts, s2_counts, tile: int = 100, scale: int = 6, max_black_frac: float = 0.0, max_tiles=None,
-                 stride=None):
+                 stride=None, cloud_counts=None, max_cloud_frac: float = 1.0):
     """The reference's selection (:285-302) from the black counts of the window grids: ``emit_counts`` (h_e // tile, w_e // tile)
     and ``s2_counts`` (h_s // (tile scale), w_s // (tile scale)) integers, ``windows`` as ``scene_windows`` returns them.  A window
     pair is kept when ``count / size <= max_black_frac`` (float64) on both sides; ``idx`` counts the kept pairs and the walk stops
     at ``max_tiles``.  Returns the reference's list of dicts: idx, emit_window, s2_window, emit_black_frac, s2_black_frac.
     With ``stride`` the two arrays are grids of cells of ``stride`` (EMIT) and ``stride scale`` (S2) pixels, (h // cell, w // cell),
     the windows lie on the cell grid and a window's count is the integer sum of its ``(tile / stride)^2`` cells: the same
-    fractions as from a count of the window itself.  Host only."""
+    fractions as from a count of the window itself.
+    ``cloud_counts`` (None: nothing changes) is a third grid on the EMIT cells, the not-clear EMIT pixels of every cell
+    (``coarse_clear_mask``'s ``win_counts``): a window is kept when it also has ``cloud cells / tile^2 <= max_cloud_frac``, inside
+    the same walk, so ``max_tiles`` keeps its meaning, and its dict gains ``cloud_frac``.  Host only."""
     tile, scale = _int(tile, "emit_tile_size"), _int(scale, "scale")
     cell = _stride(stride, tile) or tile
     frac, max_tiles = _limits(max_black_frac, max_tiles)
+    cc = None
+    if cloud_counts is not None:
+        cc = np.asarray(cloud_counts)
+        if cc.ndim != 2 or cc.dtype.kind not in "iu":
+            raise ValueError(f"select_tiles: cloud_counts is a 2-d integer array, got {cc.dtype} {cc.shape}")
+        cloud_limit = _cloud_frac(max_cloud_frac)
     ec, sc = np.asarray(emit_counts), np.asarray(s2_counts)
     if ec.ndim != 2 or sc.ndim != 2 or ec.dtype.kind not in "iu" or sc.dtype.kind not in "iu":
         raise ValueError(f"select_tiles: the counts are 2-d integer arrays, got {ec.dtype} {ec.shape} and {sc.dtype} {sc.shape}")
@@ -135,9 +154,17 @@ def select_tiles(windows, emit_counts, s2_counts, tile: int = 100, scale: int = 
             raise ValueError(f"select_tiles: {w_emit} / {w_s2} is not a window of the {ec.shape} / {sc.shape} count grids")
         emit_black_frac = int(ec[ie:ie + k, je:je + k].sum(dtype=np.int64)) / (tile * tile)
         s2_black_frac = int(sc[i_s:i_s + k, j_s:j_s + k].sum(dtype=np.int64)) / (ts * ts)
+        if cc is not None:
+            if not (ie <= cc.shape[0] - k and je <= cc.shape[1] - k):
+                raise ValueError(f"select_tiles: {w_emit} is not a window of the {cc.shape} cloud count grid")
+            cloud_frac = int(cc[ie:ie + k, je:je + k].sum(dtype=np.int64)) / (tile * tile)
+            if cloud_frac > cloud_limit:
+                continue
         if emit_black_frac <= frac and s2_black_frac <= frac:
             tiles.append({"idx": len(tiles), "emit_window": w_emit, "s2_window": w_s2, "emit_black_frac": emit_black_frac,
                           "s2_black_frac": s2_black_frac})
+            if cc is not None:
+                tiles[-1]["cloud_frac"] = cloud_frac
             if max_tiles is not None and len(tiles) >= max_tiles:
                 break
     return tiles
@@ -173,21 +200,28 @@ def _scan(lib, st, scene, dtype: str, shape, th: int, tw: int, nodata, masked_va
                                          float(nodata_atol), float(zero_atol), _ptr(counts), st), "hsr_scene_black_counts")
 
 
-def _find(lib, torch, dev, plan: _FindPlan, E, S, emit_nodata, s2_nodata, masked_val, nodata_atol, zero_atol):
+def _find(lib, torch, dev, plan: _FindPlan, E, S, emit_nodata, s2_nodata, masked_val, nodata_atol, zero_atol, cloud=None):
+    """``cloud``: None, or (grid shape, launch, max_cloud_frac) - a third count grid on the EMIT cells that ``launch(segment)``
+    fills on the current stream; it rides in the same copy to the host as the two black-count grids."""
     if not plan.windows:
         return []
     (_, he, we), (_, hs, ws) = plan.emit_shape, plan.s2_shape
     ce = plan.tile if plan.stride is None else plan.stride               # the cell of the count grids: the window, or the stride
     cs = ce * plan.scale
     ne, ns = (he // ce, we // ce), (hs // cs, ws // cs)
-    counts = torch.empty(ne[0] * ne[1] + ns[0] * ns[1], dtype=torch.int32, device=dev)   # both grids: one copy to the host
+    nc = cloud[0] if cloud is not None else (0, 0)
+    n_black = ne[0] * ne[1] + ns[0] * ns[1]
+    counts = torch.empty(n_black + nc[0] * nc[1], dtype=torch.int32, device=dev)   # every grid: one copy to the host
     st = _stream(torch)
     _scan(lib, st, E, plan.emit_dtype, plan.emit_shape, ce, ce, emit_nodata, masked_val, nodata_atol, zero_atol, counts)
     _scan(lib, st, S, plan.s2_dtype, plan.s2_shape, cs, cs, s2_nodata, masked_val, nodata_atol, zero_atol,
           counts[ne[0] * ne[1]:])
+    if cloud is not None:
+        cloud[1](counts[n_black:])
     host = counts.cpu().numpy()                        # THE host synchronisation: a few hundred int32
-    return select_tiles(plan.windows, host[:ne[0] * ne[1]].reshape(ne), host[ne[0] * ne[1]:].reshape(ns), plan.tile, plan.scale,
-                        plan.frac, plan.max_tiles, plan.stride)
+    clouds = dict(cloud_counts=host[n_black:].reshape(nc), max_cloud_frac=cloud[2]) if cloud is not None else {}
+    return select_tiles(plan.windows, host[:ne[0] * ne[1]].reshape(ne), host[ne[0] * ne[1]:n_black].reshape(ns), plan.tile, plan.scale,
+                        plan.frac, plan.max_tiles, plan.stride, **clouds)
 
 
 def find_valid_paired_tiles(emit_scene, s2_scene, emit_tile_size: int = 100, scale: int = 6, max_black_frac: float = 0.0,
@@ -453,20 +487,33 @@ def fuse_scene(emit_scene, s2_scene, *, tile: int = 100, factor: int = 6, max_bl
     window in tile order, and the one host synchronisation is still the find.
 
     ``report``, ``validate``, ``train_mask`` and ``pool`` of ``fuse_tile_pairs`` are not forwarded: callers who need them chain
-    ``find_valid_paired_tiles``, ``extract_tile_pairs``, ``fuse_tile_pairs`` and ``mosaic_tiles`` themselves."""
+    ``find_valid_paired_tiles``, ``extract_tile_pairs``, ``fuse_tile_pairs`` and ``mosaic_tiles`` themselves;
+    ``s2_emit.clouds.fuse_scene_clear`` forwards a training mask of its own, from the scene classification layer."""
+    return _fuse_scene(emit_scene, s2_scene, None, tile, factor, max_black_frac, max_tiles, batch, bands, degree, alpha, emit_nodata,
+                       s2_nodata, eps, stride, blend)
+
+
+def _fuse_scene(emit_scene, s2_scene, clouds, tile, factor, max_black_frac, max_tiles, batch, bands, degree, alpha, emit_nodata,
+                s2_nodata, eps, stride, blend) -> SceneOutput:
+    """The loop of ``fuse_scene``.  ``clouds``: None, or the cloud-aware pieces of ``fuse_scene_clear`` (s2_emit/clouds.py:
+    ``_Clouds``), each where it belongs - ``check(plan)`` before the GPU is asked for, ``find(...)`` a third count grid for the
+    find, ``train_mask(...)`` the clear cells of a batch's windows, ``finish(...)`` on the finished cube."""
     plan, batch, idx, feather = _plan_fuse(emit_scene, s2_scene, tile, factor, max_black_frac, max_tiles, batch, bands, degree,
                                            stride, blend)
     end, snd = _nodata(emit_nodata, "emit_nodata"), _nodata(s2_nodata, "s2_nodata")
+    if clouds is not None:
+        clouds.check(plan)
     torch = nat.require_gpu()
     lib = nat.load()
     dev = torch.device("cuda", torch.cuda.current_device())
     E, S = _stack_dev(emit_scene, torch, dev), _stack_dev(s2_scene, torch, dev)
-    tiles = _find(lib, torch, dev, plan, E, S, end, snd, -0.01, 1e-3, 1e-6)
+    st = _stream(torch)
+    tiles = _find(lib, torch, dev, plan, E, S, end, snd, -0.01, 1e-3, 1e-6,
+                  clouds.find(lib, torch, dev, st, plan) if clouds is not None else None)
     (_, hs, ws), T, nan = plan.s2_shape, len(idx), float("nan")
     if not tiles:
         return SceneOutput(torch.full((T, hs, ws), nan, dtype=torch.float32, device=dev), [],
                            torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev), idx)
-    st = _stream(torch)
     eo, eth, etw = _origins(tiles, "emit_window", plan.emit_shape)
     so, sth, stw = _origins(tiles, "s2_window", plan.s2_shape)
     if feather:                                                          # every cube is kept until the one blend launch
@@ -482,8 +529,9 @@ def fuse_scene(emit_scene, s2_scene, *, tile: int = 100, factor: int = 6, max_bl
         b1 = min(b0 + batch, len(tiles))
         emits = _gather(lib, torch, st, E, plan.emit_dtype, plan.emit_shape, eo[b0:b1], eth, etw)
         s2s = _gather(lib, torch, st, S, plan.s2_dtype, plan.s2_shape, so[b0:b1], sth, stw)
+        masks = dict(train_mask=clouds.train_mask(lib, torch, st, eo[b0:b1], eth, etw)) if clouds is not None else {}
         out = fuse_tile_pairs(emits, s2s, bands=idx, degree=degree, alpha=alpha, factor=plan.scale, emit_nodata=emit_nodata,
-                              s2_nodata=s2_nodata, eps=eps)
+                              s2_nodata=s2_nodata, eps=eps, **masks)
         if feather:
             stack[b0:b1].copy_(out.cube)
         else:
@@ -497,4 +545,6 @@ def fuse_scene(emit_scene, s2_scene, *, tile: int = 100, factor: int = 6, max_bl
         status.append(out.status)
     if feather:
         _blend_into(lib, torch, st, stack, cube, start, sy, sx, sth, stw, nan)
+    if clouds is not None:
+        clouds.finish(lib, torch, st, cube)
     return SceneOutput(cube, tiles, torch.cat(n_train), torch.cat(status), idx)
