@@ -142,10 +142,19 @@ enum SclInstance : int {
   kSclInstances = kSclApply + 2
 };
 
+// Kernel instances of hsr_s2stack.hip, the index of the name table behind hsr_s2stack_last_launch / hsr_s2stack_instance_name
+// (csrc/hsr_lib.hip, include/hsr_s2stack.h): a table of its own, so the nine others keep their sizes.
+enum S2StackInstance : int {
+  kS2Stack = 0,                            // + 2 * (0 U16, 1 F32) + (0 STRICT, 1 RENORM)
+  kS2Expand = kS2Stack + 4,                // + 0 UP1, 1 UP2
+  kS2StackInstances = kS2Expand + 2
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl}_last_launch, csrc/hsr_lib.hip).
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack}_last_launch,
+// csrc/hsr_lib.hip).
 enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
-                          kLaunchFamilies };
+                          kLaunchS2Stack, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

@@ -22,6 +22,7 @@ from .scenes import (Window, SceneOutput, scene_windows, select_tiles, find_vali
                      mosaic_tiles, fuse_scene)
 from .clouds import (SCL_NAMES, CLOUD_CLASSES, ClearSceneOutput, scl_metrics, count_cloud_pixels, cloud_mask, coarse_clear_mask,
                      mask_cube, fuse_scene_clear)
+from .s2stack import S2_STACK_BANDS, S2StackOutput, s2_crop_window, assemble_s2_stack
 from .ortho import OrthoOutput, apply_glt, ortho_scene, glt_from_xy, quality_mask
 from .coreg import (TiePoints, ShiftModel, CoregOutput, closest_band, tie_point_grid, match_windows, fit_shift_model, warp_scene,
                     coregister_scene)
@@ -29,8 +30,8 @@ from .reproject import (ReprojectOutput, utm_params, tm_forward, tm_inverse, utm
                         reproject_scene)
 from ._native import HsrUnavailable, HsrError
 
-# SCL_NAMES and CLOUD_CLASSES, the reference's two tables, are attributes of the package and stay out of __all__: every name in it
-# is callable (tests/test_host_logic.py).
+# SCL_NAMES, CLOUD_CLASSES and S2_STACK_BANDS, the reference's tables, are attributes of the package and stay out of __all__: every
+# name in it is callable (tests/test_host_logic.py).
 # The public surface: first the 13 names of the reference's __all__ (s2_emit/__init__.py:10-24, same order -
 # tests/test_host_logic.py checks it), then what callers of the reference copy out of poly_regression.py and
 # the notebooks, then this build's fused / pipelined entry points.
@@ -43,6 +44,7 @@ _COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb", "fit_ot_affine_rgb", 
 _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real_linear",
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
+          "assemble_s2_stack", "s2_crop_window", "S2StackOutput",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
           "Window", "SceneOutput",
           "fuse_scene_clear", "cloud_mask", "coarse_clear_mask", "mask_cube", "scl_metrics", "count_cloud_pixels", "ClearSceneOutput",

@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h and include/hsr_scl.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h and include/hsr_s2stack.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -309,6 +309,30 @@ SCL_SIGNATURES = {
     "hsr_scl_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The S2 stack family, include/hsr_s2stack.h: a table of its own like the four above; load() types all six.
+HSR_S2_MAX_BANDS = 16
+HSR_S2_NEAREST, HSR_S2_BILINEAR = 0, 1
+HSR_S2_STRICT, HSR_S2_RENORM = 0, 1
+HSR_S2_U16, HSR_S2_F32 = 0, 1
+HSR_S2_TILE_H, HSR_S2_TILE_W = 16, 512
+
+
+class S2Band(C.Structure):
+    """hsr_s2_band: one band of the table of hsr_s2_stack (40 bytes)."""
+    _fields_ = [("plane_dev", _vp), ("rs", _i64), ("H", _i32), ("W", _i32), ("up", _i32), ("method", _i32), ("add_offset", _i32),
+                ("reserved", _i32)]
+
+
+_S2_STACK = [C.POINTER(S2Band), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _f32, _f64, _vp]
+S2STACK_SIGNATURES = {
+    "hsr_s2_stack": (C.c_int, _S2_STACK + [_vp]),
+    "hsr_s2_stack_host": (C.c_int, _S2_STACK),
+    "hsr_s2_expand_u8": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "hsr_s2stack_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_s2stack_instance_count": (C.c_int, []),
+    "hsr_s2stack_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -333,7 +357,7 @@ def load() -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
-            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()):
+            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
