@@ -150,11 +150,23 @@ enum S2StackInstance : int {
   kS2StackInstances = kS2Expand + 2
 };
 
+// Kernel instances of hsr_hist.hip, the index of the name table behind hsr_hist_last_launch / hsr_hist_instance_name
+// (csrc/hsr_lib.hip, include/hsr_hist.h): a table of its own, so the ten others keep their sizes.
+enum HistInstance : int {
+  kHistKeys = 0,                           // + 0 PIXMAJOR, 1 PLANAR
+  kHistCount = kHistKeys + 2,              // + pass (digit 0..3)
+  kHistScan = kHistCount + 4,
+  kHistScatter,                            // + pass
+  kHistPivots = kHistScatter + 4,
+  kHistLookup,                             // + 0 PIXMAJOR, 1 PLANAR
+  kHistInstances = kHistLookup + 2
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack}_last_launch,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist}_last_launch,
 // csrc/hsr_lib.hip).
 enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
-                          kLaunchS2Stack, kLaunchFamilies };
+                          kLaunchS2Stack, kLaunchHist, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

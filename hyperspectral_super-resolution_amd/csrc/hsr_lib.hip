@@ -8,6 +8,7 @@
 #include "../../include/hsr_reproject.h"
 #include "../../include/hsr_scl.h"
 #include "../../include/hsr_s2stack.h"
+#include "../../include/hsr_hist.h"
 
 namespace hsr {
 
@@ -87,7 +88,7 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack}_last_launch): per family and thread, the kernels launched successfully since the last
+// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist}_last_launch): per family and thread, the kernels launched successfully since the last
 // read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
 // the list is full.  Indices turn into names only when read.
 static const char* const kAuxNames[] = {
@@ -167,6 +168,14 @@ static const char* const kS2StackNames[] = {
     "s2_stack_kernel<U16, STRICT>", "s2_stack_kernel<U16, RENORM>", "s2_stack_kernel<F32, STRICT>", "s2_stack_kernel<F32, RENORM>",
     "s2_expand_kernel<UP1>", "s2_expand_kernel<UP2>",
 };
+static const char* const kHistNames[] = {
+    "hist_keys_kernel<PIXMAJOR>", "hist_keys_kernel<PLANAR>",
+    "hist_count_kernel<0>", "hist_count_kernel<1>", "hist_count_kernel<2>", "hist_count_kernel<3>",
+    "hist_scan_kernel",
+    "hist_scatter_kernel<0>", "hist_scatter_kernel<1>", "hist_scatter_kernel<2>", "hist_scatter_kernel<3>",
+    "hist_pivots_kernel",
+    "hist_lookup_kernel<PIXMAJOR>", "hist_lookup_kernel<PLANAR>",
+};
 template <int N>
 constexpr int length(const char* const (&)[N]) { return N; }
 static_assert(length(kOrthoNames) == kOrthoInstances, "kOrthoNames: one name per OrthoInstance");
@@ -175,6 +184,7 @@ static_assert(length(kCoregNames) == kCoregInstances, "kCoregNames: one name per
 static_assert(length(kReprojectNames) == kReprojectInstances, "kReprojectNames: one name per ReprojectInstance");
 static_assert(length(kSclNames) == kSclInstances, "kSclNames: one name per SclInstance");
 static_assert(length(kS2StackNames) == kS2StackInstances, "kS2StackNames: one name per S2StackInstance");
+static_assert(length(kHistNames) == kHistInstances, "kHistNames: one name per HistInstance");
 static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
 static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
 static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
@@ -183,9 +193,11 @@ static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per
 // Aux, scene and ortho entry points launch one kernel each, so their record keeps the last launch only; K4 and pairs entry points
 // launch up to two, and a caller may read after several calls; a colour fit is a chain of three entry points and a
 // co-registration one of four, read after the chain; a reprojection is two; the SCL chain mask -> coarse -> gather -> apply is four;
-// the S2 stack and the SCL under its window are two.
+// the S2 stack and the SCL under its window are two; a histogram match is keys, four passes of count, scan and scatter, the pivots
+// and the lookup: fifteen.
 constexpr int kRecordCap = 32;
 constexpr int kColorRecordCap = 8;
+constexpr int kHistRecordCap = 16;
 struct Family {
   const char* const* names;
   int count;
@@ -203,6 +215,7 @@ static const Family kFamilies[] = {
     {kReprojectNames, kReprojectInstances, kColorRecordCap, "hsr_reproject_instance_name"},  // kLaunchReproject
     {kSclNames, kSclInstances, kColorRecordCap, "hsr_scl_instance_name"},  // kLaunchScl
     {kS2StackNames, kS2StackInstances, kColorRecordCap, "hsr_s2stack_instance_name"},  // kLaunchS2Stack
+    {kHistNames, kHistInstances, kHistRecordCap, "hsr_hist_instance_name"},  // kLaunchHist
 };
 static_assert(sizeof(kFamilies) / sizeof(kFamilies[0]) == kLaunchFamilies, "kFamilies: one row per LaunchFamily");
 struct Record {
@@ -290,6 +303,10 @@ extern "C" const char* hsr_scl_instance_name(int32_t i) { return hsr::instance_n
 extern "C" int hsr_s2stack_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchS2Stack, names, capacity); }
 extern "C" int hsr_s2stack_instance_count(void) { return hsr::kS2StackInstances; }
 extern "C" const char* hsr_s2stack_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchS2Stack, i); }
+
+extern "C" int hsr_hist_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchHist, names, capacity); }
+extern "C" int hsr_hist_instance_count(void) { return hsr::kHistInstances; }
+extern "C" const char* hsr_hist_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchHist, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

@@ -11,7 +11,7 @@ from .synth import pseudo_s2_srf_integral, pseudo_s2_rgb
 from .viz import show_side_by_side, resize_s2_rgb_to, load_s2_rgb_u8
 from .color import (
     robust_norm, robust_norm_rgb, apply_shared_percentile_stretch,
-    histogram_match_rgb, ot_match_rgb_sinkhorn_pot
+    histogram_match_rgb, ot_match_rgb_sinkhorn_pot, histogram_match_planes
 )
 from .poly_regression import fit_ot_poly_rgb, apply_poly_rgb
 from .affine import fit_ot_affine_rgb, apply_affine_rgb, fit_affine_rgb
@@ -44,6 +44,7 @@ _COPIED_BY_CALLERS = ["fit_ot_poly_rgb", "apply_poly_rgb", "fit_ot_affine_rgb", 
 _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real_linear",
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
+          "histogram_match_planes",
           "assemble_s2_stack", "s2_crop_window", "S2StackOutput",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
           "Window", "SceneOutput",

@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h and include/hsr_s2stack.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h and include/hsr_hist.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -333,6 +333,32 @@ S2STACK_SIGNATURES = {
     "hsr_s2stack_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The histogram-matching family, include/hsr_hist.h: a table of its own like the five above; load() types all seven.
+HSR_HIST_MAX_CHANNELS = 16
+HSR_HIST_SORT_TILE = 8192
+HSR_HIST_SORT_BITS = 8
+HSR_HIST_SCAN_STEP = 4096
+HSR_HIST_PIVOT = 256
+HSR_HIST_MAX_NPIX = 2147483647
+HSR_HIST_SENTINEL = 0xFFFFFFFF
+_HIST_IMAGES = [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i32]          # src, cs, ps, ref, cs, ps, mask, npix, C
+HIST_SIGNATURES = {
+    "hsr_hist_plane_stride": (_i64, [_i64]),
+    "hsr_hist_sort_bytes": (C.c_size_t, [_i64, _i32]),
+    "hsr_hist_pivot_bytes": (C.c_size_t, [_i64, _i32]),
+    "hsr_hist_scratch_bytes": (C.c_size_t, [_i64, _i32]),
+    "hsr_hist_keys": (C.c_int, _HIST_IMAGES + [_vp, _i64, _vp, _vp]),
+    "hsr_hist_sort": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, C.c_size_t, _vp]),
+    "hsr_hist_sort_pass": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, C.c_size_t, _vp]),
+    "hsr_hist_lookup": (C.c_int, [_vp, _i64, _vp, _vp, C.c_size_t] + _HIST_IMAGES + [_vp, _i64, _i64, _vp]),
+    "hsr_hist_match": (C.c_int, _HIST_IMAGES + [_vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "hsr_hist_match_host": (C.c_int, _HIST_IMAGES + [_vp, _i64, _i64, _vp]),
+    "hsr_hist_key_host": (C.c_uint32, [_f32]),
+    "hsr_hist_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_hist_instance_count": (C.c_int, []),
+    "hsr_hist_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -357,7 +383,7 @@ def load() -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
-            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()):
+            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()) + list(HIST_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

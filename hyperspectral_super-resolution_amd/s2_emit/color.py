@@ -5,7 +5,10 @@ On the measured path (reference poly_regression.py:126-127,161) is
 (csrc/hsr_select.hip) and the stretch itself fused into K3 (csrc/hsr_poly.hip).  The remaining
 names are API surface kept for drop-in use: plain host NumPy, no kernels -
 except ``ot_match_rgb_sinkhorn_pot`` given GPU tensors, which runs wholly on the device (.affine,
-csrc/hsr_color.hip); its NumPy-input form is unchanged.
+csrc/hsr_color.hip), and ``histogram_match_rgb`` given GPU tensors, which is a batched keys-only radix
+sort of all six planes and an exact rank lookup per pixel (csrc/hsr_hist.hip, the definition in
+include/hsr_hist.h; equal by value to the NumPy form whenever every masked sample is finite);
+``histogram_match_planes`` is the same for (C, H, W) stacks.  Their NumPy-input forms are unchanged.
 """
 from __future__ import annotations
 
@@ -100,11 +103,79 @@ def _hist_match_channel(src: np.ndarray, ref: np.ndarray, mask: np.ndarray) -> n
     return out
 
 
+def _hist_device_inputs(torch, src, ref, mask, what, channel_axis):
+    """float32 contiguous images of one shape on one device and the flat uint8 mask of their pixels."""
+    for name, t in (("src", src), ("ref", ref)):
+        if not _is_torch(t) or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a GPU tensor like the other image")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {name} must be float32 on the GPU. Got {t.dtype}")
+        if t.ndim != 3:
+            raise ValueError(f"{what}: {name} must have 3 dimensions. Got shape {tuple(t.shape)}")
+    if tuple(src.shape) != tuple(ref.shape) or src.device != ref.device:
+        raise ValueError(f"{what}: src {tuple(src.shape)} on {src.device} and ref {tuple(ref.shape)} on {ref.device} differ")
+    hw = tuple(src.shape[:2]) if channel_axis == 2 else tuple(src.shape[1:])
+    if not _is_torch(mask):
+        mask = torch.from_numpy(np.ascontiguousarray(mask, dtype=np.bool_).view(np.uint8)).to(src.device)
+    if tuple(mask.shape) != hw:
+        raise IndexError(f"boolean index did not match indexed array: mask must be {hw}. Got {tuple(mask.shape)}")
+    m = mask.to(device=src.device)
+    m = (m if m.dtype == torch.bool else m != 0).contiguous().view(torch.uint8).reshape(-1)
+    return src.contiguous(), ref.contiguous(), m
+
+
+def _hist_match_device(torch, src, ref, m, out, npix, C, strides):
+    """hsr_hist_match on the tensors' stream in a workspace from torch's allocator; -> the counts (C,) int64 on the device."""
+    lib = nat.load()
+    n_valid = torch.empty((C,), dtype=torch.int64, device=src.device)
+    need = int(lib.hsr_hist_scratch_bytes(npix, C))
+    if need == 0:
+        raise ValueError(f"histogram matching of {npix} pixels x {C} channels is outside what the kernels hold")
+    work = torch.empty((need + 256,), dtype=torch.uint8, device=src.device)
+    wp = (work.data_ptr() + 255) & ~255
+    cs, ps = strides
+    with torch.cuda.device(src.device):
+        nat.check(lib.hsr_hist_match(src.data_ptr(), cs, ps, ref.data_ptr(), cs, ps, m.data_ptr(), npix, C, out.data_ptr(), cs, ps,
+                                     n_valid.data_ptr(), wp, need, eng._stream(torch)), "hsr_hist_match")
+    return n_valid
+
+
+def histogram_match_planes(src, ref, mask):
+    """Histogram matching of (C, H, W) float32 GPU stacks, C <= 16, every plane on its own inside ``mask`` (H, W) - pseudo-S2 planes
+    against the real ones: the rule of ``histogram_match_rgb`` per plane (include/hsr_hist.h).  -> (out (C, H, W) float32 on the
+    device, n_valid (C,) int64 on the device: the masked pixels whose two samples are finite).  Inputs are not mutated; no host
+    synchronisation."""
+    torch = nat.require_gpu()
+    src, ref, m = _hist_device_inputs(torch, src, ref, mask, "histogram_match_planes", 0)
+    C, H, W = (int(v) for v in src.shape)
+    if not 1 <= C <= nat.HSR_HIST_MAX_CHANNELS:
+        raise ValueError(f"histogram_match_planes: {C} planes outside [1,{nat.HSR_HIST_MAX_CHANNELS}]")
+    if H * W < 1:
+        raise ValueError(f"histogram_match_planes: an empty image {tuple(src.shape)}")
+    out = torch.empty_like(src)
+    n_valid = _hist_match_device(torch, src, ref, m, out, H * W, C, (H * W, 1))
+    return out, n_valid
+
+
 def histogram_match_rgb(src_rgb: np.ndarray, ref_rgb: np.ndarray, mask: np.ndarray) -> np.ndarray:
     """
     Histogram-match each channel independently within mask (color.py:55-63).
-    Inputs assumed in [0,1].  Host NumPy (API surface).
+    Inputs assumed in [0,1].  NumPy in: host NumPy (API surface), unchanged.
+    Float32 GPU tensors (H, W, C >= 3) in: a new float32 GPU tensor, the first three channels matched on the device
+    (csrc/hsr_hist.hip) and the others clipped, as the reference's loop leaves them; inputs are not mutated, nothing synchronises
+    with the host; any other GPU dtype raises ValueError.
     """
+    if _is_torch(src_rgb) or _is_torch(ref_rgb):
+        torch = nat.require_gpu()
+        src, ref, m = _hist_device_inputs(torch, src_rgb, ref_rgb, mask, "histogram_match_rgb", 2)
+        H, W, Cc = (int(v) for v in src.shape)
+        if Cc < 3:
+            raise IndexError(f"index 2 is out of bounds for axis 2 with size {Cc}")
+        if H * W < 1:
+            raise ValueError(f"histogram_match_rgb: an empty image {tuple(src.shape)}")
+        out = torch.empty_like(src) if Cc == 3 else torch.clamp(src, 0.0, 1.0)
+        _hist_match_device(torch, src, ref, m, out, H * W, 3, (1, Cc))
+        return out
     out = src_rgb.copy()
     for c in range(3):
         out[..., c] = _hist_match_channel(out[..., c], ref_rgb[..., c], mask)
