@@ -162,11 +162,19 @@ enum HistInstance : int {
   kHistInstances = kHistLookup + 2
 };
 
+// Kernel instances of hsr_resize.hip, the index of the name table behind hsr_resize_last_launch / hsr_resize_instance_name
+// (csrc/hsr_lib.hip, include/hsr_resize.h): a table of its own, so the eleven others keep their sizes.
+enum ResizeInstance : int {
+  kAreaStaged = 0,                         // + 5 * (0 PLANAR, 1 PIXMAJOR) + pair: 0 <F32, F32>, 1 <U8, U8>, 2 <U8, F32>, 3 <U16, U16>, 4 <U16, F32>
+  kAreaGather = kAreaStaged + 10,          // + pair
+  kResizeInstances = kAreaGather + 5
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist}_last_launch,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize}_last_launch,
 // csrc/hsr_lib.hip).
 enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
-                          kLaunchS2Stack, kLaunchHist, kLaunchFamilies };
+                          kLaunchS2Stack, kLaunchHist, kLaunchResize, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

@@ -9,6 +9,7 @@
 #include "../../include/hsr_scl.h"
 #include "../../include/hsr_s2stack.h"
 #include "../../include/hsr_hist.h"
+#include "../../include/hsr_resize.h"
 
 namespace hsr {
 
@@ -88,7 +89,7 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist}_last_launch): per family and thread, the kernels launched successfully since the last
+// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize}_last_launch): per family and thread, the kernels launched successfully since the last
 // read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
 // the list is full.  Indices turn into names only when read.
 static const char* const kAuxNames[] = {
@@ -176,6 +177,14 @@ static const char* const kHistNames[] = {
     "hist_pivots_kernel",
     "hist_lookup_kernel<PIXMAJOR>", "hist_lookup_kernel<PLANAR>",
 };
+static const char* const kResizeNames[] = {
+    "area_staged_kernel<F32, F32, PLANAR>", "area_staged_kernel<U8, U8, PLANAR>", "area_staged_kernel<U8, F32, PLANAR>",
+    "area_staged_kernel<U16, U16, PLANAR>", "area_staged_kernel<U16, F32, PLANAR>",
+    "area_staged_kernel<F32, F32, PIXMAJOR>", "area_staged_kernel<U8, U8, PIXMAJOR>", "area_staged_kernel<U8, F32, PIXMAJOR>",
+    "area_staged_kernel<U16, U16, PIXMAJOR>", "area_staged_kernel<U16, F32, PIXMAJOR>",
+    "area_gather_kernel<F32, F32>", "area_gather_kernel<U8, U8>", "area_gather_kernel<U8, F32>", "area_gather_kernel<U16, U16>",
+    "area_gather_kernel<U16, F32>",
+};
 template <int N>
 constexpr int length(const char* const (&)[N]) { return N; }
 static_assert(length(kOrthoNames) == kOrthoInstances, "kOrthoNames: one name per OrthoInstance");
@@ -185,6 +194,7 @@ static_assert(length(kReprojectNames) == kReprojectInstances, "kReprojectNames: 
 static_assert(length(kSclNames) == kSclInstances, "kSclNames: one name per SclInstance");
 static_assert(length(kS2StackNames) == kS2StackInstances, "kS2StackNames: one name per S2StackInstance");
 static_assert(length(kHistNames) == kHistInstances, "kHistNames: one name per HistInstance");
+static_assert(length(kResizeNames) == kResizeInstances, "kResizeNames: one name per ResizeInstance");
 static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
 static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
 static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
@@ -194,7 +204,7 @@ static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per
 // launch up to two, and a caller may read after several calls; a colour fit is a chain of three entry points and a
 // co-registration one of four, read after the chain; a reprojection is two; the SCL chain mask -> coarse -> gather -> apply is four;
 // the S2 stack and the SCL under its window are two; a histogram match is keys, four passes of count, scan and scatter, the pivots
-// and the lookup: fifteen.
+// and the lookup: fifteen; an area resampling is one.
 constexpr int kRecordCap = 32;
 constexpr int kColorRecordCap = 8;
 constexpr int kHistRecordCap = 16;
@@ -216,6 +226,7 @@ static const Family kFamilies[] = {
     {kSclNames, kSclInstances, kColorRecordCap, "hsr_scl_instance_name"},  // kLaunchScl
     {kS2StackNames, kS2StackInstances, kColorRecordCap, "hsr_s2stack_instance_name"},  // kLaunchS2Stack
     {kHistNames, kHistInstances, kHistRecordCap, "hsr_hist_instance_name"},  // kLaunchHist
+    {kResizeNames, kResizeInstances, kColorRecordCap, "hsr_resize_instance_name"},  // kLaunchResize
 };
 static_assert(sizeof(kFamilies) / sizeof(kFamilies[0]) == kLaunchFamilies, "kFamilies: one row per LaunchFamily");
 struct Record {
@@ -307,6 +318,10 @@ extern "C" const char* hsr_s2stack_instance_name(int32_t i) { return hsr::instan
 extern "C" int hsr_hist_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchHist, names, capacity); }
 extern "C" int hsr_hist_instance_count(void) { return hsr::kHistInstances; }
 extern "C" const char* hsr_hist_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchHist, i); }
+
+extern "C" int hsr_resize_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchResize, names, capacity); }
+extern "C" int hsr_resize_instance_count(void) { return hsr::kResizeInstances; }
+extern "C" const char* hsr_resize_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchResize, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

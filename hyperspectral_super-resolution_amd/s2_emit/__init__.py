@@ -8,7 +8,8 @@ them raises ``HsrUnavailable`` (no CPU fallback).
 from .srf import load_s2_srf_from_xlsx, S2_BANDS_13, DEFAULT_SRF_XLSX_URL
 from .emit_io import load_emit_envi_rfl, load_emit_wavelengths_from_nc
 from .synth import pseudo_s2_srf_integral, pseudo_s2_rgb
-from .viz import show_side_by_side, resize_s2_rgb_to, load_s2_rgb_u8
+from .viz import show_side_by_side, load_s2_rgb_u8
+from .resize import AreaResampleOutput, resample_area, resample_to_grid, resize_s2_rgb_to
 from .color import (
     robust_norm, robust_norm_rgb, apply_shared_percentile_stretch,
     histogram_match_rgb, ot_match_rgb_sinkhorn_pot, histogram_match_planes
@@ -45,6 +46,7 @@ _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real
           "PolyRidge", "predict_cube_logit", "flatten_pixels", "subsample_bands_evenly",
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
           "histogram_match_planes",
+          "resample_area", "resample_to_grid", "AreaResampleOutput",
           "assemble_s2_stack", "s2_crop_window", "S2StackOutput",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",
           "Window", "SceneOutput",

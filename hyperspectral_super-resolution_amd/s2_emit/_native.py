@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h and include/hsr_hist.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h, include/hsr_hist.h and include/hsr_resize.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -359,6 +359,27 @@ HIST_SIGNATURES = {
     "hsr_hist_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The area-resampling family, include/hsr_resize.h: a table of its own like the six above; load() types all eight.
+HSR_AREA_MAX_SCALE = 64
+HSR_AREA_MAX_CHANNELS = 16
+HSR_AREA_F32, HSR_AREA_U8, HSR_AREA_U16 = 0, 1, 2
+HSR_AREA_STRICT, HSR_AREA_RENORM = 0, 1
+HSR_AREA_TILE_H, HSR_AREA_TILE_W = 8, 32
+HSR_AREA_LDS_BYTES = 81920
+# src, in_dtype, C, h, w, cs, rs, ps, y0, x0, sy, sx, has_nodata, nodata, rule, min_valid_frac, dst, out_dtype, H, W, cs, rs, ps,
+# post_scale, fill, nodata_out, invalid
+_AREA = [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _i32, _f64, _i32, _f64, _vp, _i32, _i32, _i32, _i64, _i64,
+         _i64, _f32, _f32, _i32, _vp]
+RESIZE_SIGNATURES = {
+    "hsr_area_resample": (C.c_int, _AREA + [_vp]),
+    "hsr_area_resample_host": (C.c_int, _AREA),
+    "hsr_area_resample_instance": (C.c_int, [_i32, _i32, _i32, _i64, _i64, _f64, _f64]),
+    "hsr_area_grid_from_geotransforms": (C.c_int, [_pf64, _pf64, _pf64]),
+    "hsr_resize_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_resize_instance_count": (C.c_int, []),
+    "hsr_resize_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -383,7 +404,8 @@ def load() -> C.CDLL:
     except OSError as e:  # e.g. libamdhip64 not resolvable
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
-            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()) + list(HIST_SIGNATURES.items()):
+            + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()) + list(HIST_SIGNATURES.items()) \
+            + list(RESIZE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

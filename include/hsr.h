@@ -638,6 +638,7 @@ int hsr_pool_models(const double* gbp_dev, int64_t group_bp, const double* gb64_
  * (Pairs_EMIT_S2_demo-2.ipynb cell 73, raw lines 4538-4599) for exactly aligned integer-factor grids:
  * an f x f block mean (double accumulate, float32 store, then `* scale` in float32) and a pixel-centre
  * aligned separable bilinear upsampling with edge clamp.  GDAL parity unpinned (rasterio absent).
+ * Shrinking at any ratio and origin (grids that are not aligned): hsr_area_resample, include/hsr_resize.h.
  * in_dtype: 0 float32, 1 uint8, 2 uint16.  Fine grid is (Hc*f, Wc*f); images use (band, pixel) strides. */
 int hsr_block_mean(const void* in_dev, int32_t in_dtype, int64_t in_bs, int64_t in_ps, int32_t nb,
                    int32_t Hc, int32_t Wc, int32_t factor, float scale,
