@@ -170,11 +170,21 @@ enum ResizeInstance : int {
   kResizeInstances = kAreaGather + 5
 };
 
+// Kernel instances of hsr_merge.hip, the index of the name table behind hsr_merge_last_launch / hsr_merge_instance_name
+// (csrc/hsr_lib.hip, include/hsr_merge.h): a table of its own, so the twelve others keep their sizes.
+enum MergeInstance : int {
+  kOrthoMergeBip = 0,                      // + 2 * kMask + kVec
+  kOrthoMergeBsq = kOrthoMergeBip + 4,     // + kMask
+  kMergeScenes = kOrthoMergeBsq + 2,
+  kMergeSource,
+  kMergeInstances
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize}_last_launch,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize,merge}_last_launch,
 // csrc/hsr_lib.hip).
 enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
-                          kLaunchS2Stack, kLaunchHist, kLaunchResize, kLaunchFamilies };
+                          kLaunchS2Stack, kLaunchHist, kLaunchResize, kLaunchMerge, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

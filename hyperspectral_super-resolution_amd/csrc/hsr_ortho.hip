@@ -18,24 +18,11 @@
 //   bsq  (bands, h, w): the spectra land in an LDS tile [64 pixels][bands | 1 floats] (the odd pitch keeps the transposed read off
 //        shared banks); after a barrier wave w stores bands w, w + 8, ...: 64 lanes = 64 consecutive x = one 256-byte segment
 //        of the band's plane per instruction.  Fill and masked pixels never touch the tile: their lane stores the constant.
-#include "hsr_common.h"
-
-#include <type_traits>
+#include "hsr_ortho_dev.h"                // the workgroup geometry, ortho_entry, OrthoVec and ortho_value: shared with hsr_merge.hip
 
 namespace hsr {
 
-constexpr int kOrthoPx = 64;           // output pixels of a workgroup, consecutive in x
-constexpr int kOrthoPxWave = 16;       // ... of one wave
-constexpr int kOrthoAhead = 4;         // spectra a wave has in flight: bip (up to 8 wave slots a SIMD)
-constexpr int kOrthoBsqWaves = 8;      // bsq: 512 threads share the workgroup's pixels, the tile leaves room for two workgroups
-constexpr int kOrthoPxWaveBsq = 8;     // a CU at 285 bands, so a wave takes 8 pixels and has all 8 spectra in flight
-constexpr int kOrthoAheadBsq = 8;
-constexpr int kOrthoMaxBands = 512;    // the bsq tile: 64 x 513 floats = 128.25 KiB of the CU's 160 KiB of LDS
-static_assert(kOrthoPx == 4 * kOrthoPxWave && kOrthoPxWave % kOrthoAhead == 0, "bip: four waves share the workgroup's pixels");
-static_assert(kOrthoPx == kOrthoBsqWaves * kOrthoPxWaveBsq && kOrthoPxWaveBsq % kOrthoAheadBsq == 0, "bsq: eight waves share them");
 static_assert(kOrthoPx * ((kOrthoMaxBands | 1) * 4) + 1024 <= 160 * 1024, "the bsq tile fits the LDS of a CU");
-
-enum OrthoKind : int { kOrthoFill = 0, kOrthoCopy = 1, kOrthoMasked = 2 };
 
 struct OrthoArgs {
   const float* swath;                  // (rows, cols, bands)
@@ -51,7 +38,7 @@ struct OrthoArgs {
 
 // Wave 0: the GLT entries of the workgroup's pixels -> s_src (source pixel index sy cols + sx), s_kind and s_const (what a pixel
 // that is not copied holds in every band: `masked` or `fill`, selected on the bits); ends with a barrier.
-// xv - 1 and yv - 1 are formed in 64 bits, so INT32_MIN stays negative; an entry outside the swath is never used as an index.
+// The decision on an entry is ortho_entry (hsr_ortho_dev.h).
 __device__ __forceinline__ void ortho_resolve(const OrthoArgs& a, int y, int x0, int* s_src, int* s_kind, float* s_const) {
   const int t = threadIdx.x;
   if (t < kOrthoPx) {
@@ -60,16 +47,7 @@ __device__ __forceinline__ void ortho_resolve(const OrthoArgs& a, int y, int x0,
     bool drop = false;
     if (x < a.out_w) {
       const int64_t g = ((int64_t)(a.row0 + y) * a.glt_w + (a.col0 + x)) * 2;
-      const int32_t xv = a.glt[g], yv = a.glt[g + 1];
-      if (xv != a.glt_nodata && yv != a.glt_nodata) {
-        const int64_t sx = (int64_t)xv - 1, sy = (int64_t)yv - 1;
-        if (sx >= 0 && sx < a.cols && sy >= 0 && sy < a.rows) {
-          src = (int)(sy * a.cols + sx);                               // rows cols <= INT32_MAX (checked on the host)
-          kind = (a.qmask && a.qmask[src] == 1) ? kOrthoMasked : kOrthoCopy;
-        } else {
-          drop = true;
-        }
-      }
+      kind = ortho_entry(a.glt[g], a.glt[g + 1], a.glt_nodata, a.rows, a.cols, a.qmask, src, drop);
     }
     s_src[t] = src;
     s_kind[t] = kind;
@@ -81,52 +59,6 @@ __device__ __forceinline__ void ortho_resolve(const OrthoArgs& a, int y, int x0,
     }
   }
   __syncthreads();
-}
-
-// E floats of one lane.  E == 4 moves them as ONE 16-byte access: kAligned says the address lies on 16 bytes; without it the
-// vector type is only dword-aligned, which global loads and stores of gfx950 take as they are (a pixel base is bands * 4 bytes
-// times the pixel index: on 16 bytes for every fourth pixel only when bands % 4 != 0).
-typedef float ortho_f4a __attribute__((ext_vector_type(4)));
-typedef float ortho_f4u __attribute__((ext_vector_type(4), aligned(4)));
-template <int E, bool kAligned>
-struct OrthoVec;
-template <bool kAligned>
-struct OrthoVec<1, kAligned> {
-  float v[1];
-  __device__ __forceinline__ void load(const float* p) { v[0] = p[0]; }
-  __device__ __forceinline__ void store(float* p) const { st_stream(p, v[0]); }
-};
-template <bool kAligned>
-struct OrthoVec<4, kAligned> {
-  using T = std::conditional_t<kAligned, ortho_f4a, ortho_f4u>;
-  float v[4];
-  __device__ __forceinline__ void load(const float* p) {
-    const T q = *reinterpret_cast<const T*>(p);
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  }
-  __device__ __forceinline__ void store(float* p) const {
-    const T q = {v[0], v[1], v[2], v[3]};
-    __builtin_nontemporal_store(q, reinterpret_cast<T*>(p));
-  }
-};
-
-// Bands b .. b + E - 1 (b % E == 0, so they share one byte of the band mask) of pixel `src`: the constant of a fill or masked
-// pixel; else the bits of the swath, `masked` where the band's bit - np.unpackbits' order, the highest bit first - is set.
-template <bool kMask, int E, bool kAligned>
-__device__ __forceinline__ void ortho_value(const OrthoArgs& a, int kind, float constant, int src, int b, OrthoVec<E, kAligned>& o) {
-  if (kind != kOrthoCopy) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) o.v[e] = constant;
-    return;
-  }
-  o.load(a.swath + (int64_t)src * a.bands + b);
-  if constexpr (kMask) {
-    if (a.bmask) {
-      const uint32_t byte = a.bmask[(int64_t)src * a.bmask_bytes + (b >> 3)];
-#pragma unroll
-      for (int e = 0; e < E; ++e) o.v[e] = ((byte >> (7 - ((b + e) & 7))) & 1u) ? a.masked : o.v[e];
-    }
-  }
 }
 
 // Pixels [p0, p0 + kAhead) of the workgroup (those below pend), bands [b, b + E) of each: all loads, then `sink(j, p, value)`.

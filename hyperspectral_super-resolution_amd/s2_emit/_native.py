@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h, include/hsr_hist.h and include/hsr_resize.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h, include/hsr_hist.h, include/hsr_resize.h and include/hsr_merge.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -380,6 +380,36 @@ RESIZE_SIGNATURES = {
     "hsr_resize_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The scene-merging family, include/hsr_merge.h: a table of its own like the seven above; load() types all nine.
+HSR_MERGE_MAX_SOURCES = 8
+HSR_MERGE_MAX_BANDS = 512
+HSR_MERGE_RUN = 1024
+HSR_MERGE_NO_SOURCE = 255
+
+
+class MergeScene(C.Structure):
+    """hsr_merge_scene: one orthorectified scene of hsr_merge_scenes (32 bytes)."""
+    _fields_ = [("scene_dev", _vp), ("h", _i32), ("w", _i32), ("off_y", _i32), ("off_x", _i32), ("bands", _i32), ("reserved", _i32)]
+
+
+class MergeSwath(C.Structure):
+    """hsr_merge_swath: one swath of hsr_ortho_merge (64 bytes)."""
+    _fields_ = [("swath_dev", _vp), ("glt_dev", _vp), ("qmask_dev", _vp), ("bmask_dev", _vp), ("rows", _i32), ("cols", _i32),
+                ("glt_h", _i32), ("glt_w", _i32), ("off_y", _i32), ("off_x", _i32), ("bmask_bytes", _i32), ("bands", _i32)]
+
+
+assert C.sizeof(MergeScene) == 32 and C.sizeof(MergeSwath) == 64
+_MERGE_SCENES = [C.POINTER(MergeScene), _i32, _i32, _i32, _i32, _f32, _i32, _vp, _vp]
+MERGE_SIGNATURES = {
+    "hsr_merge_grid": (C.c_int, [_pf64, _pi32, _i32, _pf64, _pf64, _pi32, _pi32, _pf64]),
+    "hsr_merge_scenes": (C.c_int, _MERGE_SCENES + [_vp]),
+    "hsr_merge_scenes_host": (C.c_int, _MERGE_SCENES),
+    "hsr_ortho_merge": (C.c_int, [C.POINTER(MergeSwath), _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "hsr_merge_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_merge_instance_count": (C.c_int, []),
+    "hsr_merge_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -405,7 +435,7 @@ def load() -> C.CDLL:
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
             + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()) + list(HIST_SIGNATURES.items()) \
-            + list(RESIZE_SIGNATURES.items()):
+            + list(RESIZE_SIGNATURES.items()) + list(MERGE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
