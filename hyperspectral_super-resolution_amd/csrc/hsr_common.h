@@ -180,11 +180,22 @@ enum MergeInstance : int {
   kMergeInstances
 };
 
+// Kernel instances of hsr_roi.hip, the index of the name table behind hsr_roi_last_launch / hsr_roi_instance_name
+// (csrc/hsr_lib.hip, include/hsr_roi.h): a table of its own, so the thirteen others keep their sizes.
+enum RoiInstance : int {
+  kRoiRaster = 0,                          // + rule (0 CENTER, 1 TOUCHED)
+  kRoiCounts = kRoiRaster + 2,             // + rule
+  kRoiRecordInit = kRoiCounts + 2,
+  kRoiGltClip,
+  kRoiGltReindex,
+  kRoiInstances
+};
+
 // HSR_LAUNCH_CHECK of an entry point's one or two launches (second < 0: one) that also appends their instances, in launch order,
-// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize,merge}_last_launch,
+// to the calling thread's record of family f on success (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize,merge,roi}_last_launch,
 // csrc/hsr_lib.hip).
 enum LaunchFamily : int { kLaunchAux, kLaunchScene, kLaunchK4, kLaunchPairs, kLaunchOrtho, kLaunchColor, kLaunchCoreg, kLaunchReproject, kLaunchScl,
-                          kLaunchS2Stack, kLaunchHist, kLaunchResize, kLaunchMerge, kLaunchFamilies };
+                          kLaunchS2Stack, kLaunchHist, kLaunchResize, kLaunchMerge, kLaunchRoi, kLaunchFamilies };
 int launched(LaunchFamily f, const char* what, int first, int second = -1);
 
 // Raises a kernel's dynamic-LDS limit when a launch needs more than `configured` (the caller's cache slot, one per kernel)

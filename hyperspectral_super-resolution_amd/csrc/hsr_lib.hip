@@ -11,6 +11,7 @@
 #include "../../include/hsr_hist.h"
 #include "../../include/hsr_resize.h"
 #include "../../include/hsr_merge.h"
+#include "../../include/hsr_roi.h"
 
 namespace hsr {
 
@@ -90,7 +91,7 @@ static int launch_probe_lds(const void* buf, int64_t bytes, int lds_bytes, int g
   return HSR_OK;
 }
 
-// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize,merge}_last_launch): per family and thread, the kernels launched successfully since the last
+// Launch records (hsr_{aux,scene,k4,pairs,ortho,color,coreg,reproject,scl,s2stack,hist,resize,merge,roi}_last_launch): per family and thread, the kernels launched successfully since the last
 // read, as indices of the family's name table (the instance enums of hsr_common.h) in launch order; the oldest is dropped when
 // the list is full.  Indices turn into names only when read.
 static const char* const kAuxNames[] = {
@@ -191,6 +192,10 @@ static const char* const kMergeNames[] = {
     "ortho_merge_bip_kernel<true, true>", "ortho_merge_bsq_kernel<false>", "ortho_merge_bsq_kernel<true>",
     "merge_scenes_kernel", "merge_source_kernel",
 };
+static const char* const kRoiNames[] = {
+    "roi_raster_kernel<CENTER>", "roi_raster_kernel<TOUCHED>", "roi_counts_kernel<CENTER>", "roi_counts_kernel<TOUCHED>",
+    "roi_record_init_kernel", "roi_glt_clip_kernel", "roi_glt_reindex_kernel",
+};
 template <int N>
 constexpr int length(const char* const (&)[N]) { return N; }
 static_assert(length(kOrthoNames) == kOrthoInstances, "kOrthoNames: one name per OrthoInstance");
@@ -202,6 +207,7 @@ static_assert(length(kS2StackNames) == kS2StackInstances, "kS2StackNames: one na
 static_assert(length(kHistNames) == kHistInstances, "kHistNames: one name per HistInstance");
 static_assert(length(kResizeNames) == kResizeInstances, "kResizeNames: one name per ResizeInstance");
 static_assert(length(kMergeNames) == kMergeInstances, "kMergeNames: one name per MergeInstance");
+static_assert(length(kRoiNames) == kRoiInstances, "kRoiNames: one name per RoiInstance");
 static_assert(length(kAuxNames) == kAuxInstances, "kAuxNames: one name per AuxInstance");
 static_assert(length(kSceneNames) == kSceneInstances, "kSceneNames: one name per SceneInstance");
 static_assert(length(kK4Names) == kK4Instances, "kK4Names: one name per K4Instance");
@@ -211,7 +217,8 @@ static_assert(length(kPairsNames) == kPairsInstances, "kPairsNames: one name per
 // launch up to two, and a caller may read after several calls; a colour fit is a chain of three entry points and a
 // co-registration one of four, read after the chain; a reprojection is two; the SCL chain mask -> coarse -> gather -> apply is four;
 // the S2 stack and the SCL under its window are two; a histogram match is keys, four passes of count, scan and scatter, the pivots
-// and the lookup: fifteen; an area resampling is one; a merge is one, two with its source plane.
+// and the lookup: fifteen; an area resampling is one; a merge is one, two with its source plane; a polygon
+// clip is the record's start values, the clip and the re-index: three.
 constexpr int kRecordCap = 32;
 constexpr int kColorRecordCap = 8;
 constexpr int kHistRecordCap = 16;
@@ -235,6 +242,7 @@ static const Family kFamilies[] = {
     {kHistNames, kHistInstances, kHistRecordCap, "hsr_hist_instance_name"},  // kLaunchHist
     {kResizeNames, kResizeInstances, kColorRecordCap, "hsr_resize_instance_name"},  // kLaunchResize
     {kMergeNames, kMergeInstances, kColorRecordCap, "hsr_merge_instance_name"},  // kLaunchMerge
+    {kRoiNames, kRoiInstances, kColorRecordCap, "hsr_roi_instance_name"},  // kLaunchRoi
 };
 static_assert(sizeof(kFamilies) / sizeof(kFamilies[0]) == kLaunchFamilies, "kFamilies: one row per LaunchFamily");
 struct Record {
@@ -334,6 +342,10 @@ extern "C" const char* hsr_resize_instance_name(int32_t i) { return hsr::instanc
 extern "C" int hsr_merge_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchMerge, names, capacity); }
 extern "C" int hsr_merge_instance_count(void) { return hsr::kMergeInstances; }
 extern "C" const char* hsr_merge_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchMerge, i); }
+
+extern "C" int hsr_roi_last_launch(char* names, int32_t capacity) { return hsr::record_read(hsr::kLaunchRoi, names, capacity); }
+extern "C" int hsr_roi_instance_count(void) { return hsr::kRoiInstances; }
+extern "C" const char* hsr_roi_instance_name(int32_t i) { return hsr::instance_name(hsr::kLaunchRoi, i); }
 
 extern "C" int hsr_abi_version(void) { return HSR_ABI_VERSION; }
 

@@ -26,6 +26,7 @@ from .clouds import (SCL_NAMES, CLOUD_CLASSES, ClearSceneOutput, scl_metrics, co
 from .s2stack import S2_STACK_BANDS, S2StackOutput, s2_crop_window, assemble_s2_stack
 from .ortho import OrthoOutput, apply_glt, ortho_scene, glt_from_xy, quality_mask
 from .merge import MergeGrid, MergeOutput, OrthoMergeOutput, merge_grid, merge_scenes, ortho_merge, is_adjacent, merge_emit
+from .roi import SubsetOutput, rasterize_roi, scl_metrics_roi, count_cloud_pixels_roi, spatial_subset, clip_cube
 from .coreg import (TiePoints, ShiftModel, CoregOutput, closest_band, tie_point_grid, match_windows, fit_shift_model, warp_scene,
                     coregister_scene)
 from .reproject import (ReprojectOutput, utm_params, tm_forward, tm_inverse, utm_target_grid, reproject_coords, remap_scene,
@@ -48,6 +49,7 @@ _FUSED = ["SpectralFusion", "fuse_pair", "match_pair", "calibrate_pseudo_to_real
           "fuse_tile_pair", "fuse_tile_pairs", "TilePairOutput", "TilePairValidation",
           "histogram_match_planes",
           "merge_grid", "merge_scenes", "ortho_merge", "is_adjacent", "merge_emit", "MergeGrid", "MergeOutput", "OrthoMergeOutput",
+          "rasterize_roi", "scl_metrics_roi", "count_cloud_pixels_roi", "spatial_subset", "clip_cube", "SubsetOutput",
           "resample_area", "resample_to_grid", "AreaResampleOutput",
           "assemble_s2_stack", "s2_crop_window", "S2StackOutput",
           "find_valid_paired_tiles", "extract_tile_pairs", "mosaic_tiles", "fuse_scene", "scene_windows", "select_tiles",

@@ -1,4 +1,4 @@
-"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h, include/hsr_hist.h, include/hsr_resize.h and include/hsr_merge.h).
+"""ctypes binding of libhsr_mi355x.so (C ABI: include/hsr.h, include/hsr_color.h, include/hsr_coreg.h, include/hsr_reproject.h, include/hsr_scl.h, include/hsr_s2stack.h, include/hsr_hist.h, include/hsr_resize.h, include/hsr_merge.h and include/hsr_roi.h).
 
 The HIP library is the product path.  There is deliberately NO CPU fallback: if the shared
 library is missing, or no MI355X-class device is visible, every compute entry point raises
@@ -410,6 +410,30 @@ MERGE_SIGNATURES = {
     "hsr_merge_instance_name": (C.c_char_p, [_i32]),
 }
 
+# The polygon family, include/hsr_roi.h: a table of its own like the eight above; load() types all ten.
+HSR_ROI_MAX_EDGES = 8192
+HSR_ROI_CENTER, HSR_ROI_TOUCHED = 0, 1
+HSR_ROI_TILE_H, HSR_ROI_TILE_W = 64, 256
+HSR_ROI_RUN = 16
+HSR_ROI_RECORD = 8
+_u8 = C.c_uint8
+_ROI_GRID = [_vp, _vp, _i32, _i32, _pf64, _i32, _i32]                        # verts, ring_offsets, nrings, nverts, gt, H, W
+_ROI_RASTER = _ROI_GRID + [_i32, _i32, _i32, _i32, _i32, _u8, _u8, _vp, _i64]  # rule, window, inside, outside, out, out_rs
+_ROI_CLIP = _ROI_GRID + [_vp, _i32, _i32, _i32, _i32, _vp, _vp]               # glt, window, out_glt, record
+ROI_SIGNATURES = {
+    "hsr_roi_check_host": (C.c_int, [_vp, _vp, _i32, _i32]),
+    "hsr_roi_rasterize": (C.c_int, _ROI_RASTER + [_vp]),
+    "hsr_roi_rasterize_host": (C.c_int, _ROI_RASTER),
+    "hsr_roi_class_counts": (C.c_int, _ROI_GRID + [_i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
+    "hsr_roi_glt_clip": (C.c_int, _ROI_CLIP + [_vp]),
+    "hsr_roi_glt_clip_host": (C.c_int, _ROI_CLIP),
+    "hsr_roi_glt_reindex": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "hsr_roi_glt_reindex_host": (C.c_int, [_vp, _i32, _i32, _vp]),
+    "hsr_roi_last_launch": (C.c_int, [C.c_char_p, _i32]),
+    "hsr_roi_instance_count": (C.c_int, []),
+    "hsr_roi_instance_name": (C.c_char_p, [_i32]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lib_path: Optional[str] = None
 
@@ -435,7 +459,7 @@ def load() -> C.CDLL:
         raise HsrUnavailable(f"cannot load {path}: {e}") from e
     for name, (res, args) in list(SIGNATURES.items()) + list(COLOR_SIGNATURES.items()) + list(COREG_SIGNATURES.items()) \
             + list(REPROJECT_SIGNATURES.items()) + list(SCL_SIGNATURES.items()) + list(S2STACK_SIGNATURES.items()) + list(HIST_SIGNATURES.items()) \
-            + list(RESIZE_SIGNATURES.items()) + list(MERGE_SIGNATURES.items()):
+            + list(RESIZE_SIGNATURES.items()) + list(MERGE_SIGNATURES.items()) + list(ROI_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
